@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: training throughput (images/s) of BUCTD-CoAM-W48 at 384x288 on MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,8 @@ One "step" = the full per-batch work of reference lib/core/function.py:train (10
 already resident in HBM: forward (train-mode BN, dropout on), JointsMSELoss, zero_grad, backward, gradient
 all-reduce (N > 1), Adam step, plus the arg-max decode of output and target for the accuracy meter.
 Weak scaling: 32 images per GPU (scripts/train/train_BUCTD_COAM_gen_sample.sh:17).  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the steps and prints the line; --full adds the measurements behind the headline
+(step spread, box clocks, kernel timings and rooflines, gradient-exchange timeline, CPU-oracle baseline).
 """
 import argparse
 import json
@@ -590,6 +592,33 @@ def emit(out, rank, world, in_group=False):
         print(json.dumps(out), flush=True)
 
 
+DUMP_BUDGET = 64 << 20      # bytes, all files of --dump-outputs together
+
+
+def param_sample(params, n=1 << 20, seed=0):
+    """A fixed, seeded sample of n entries of the parameters (concatenated flat in parameters() order): what the optimizer
+    step wrote, small enough to dump."""
+    flat = torch.cat([p.detach().reshape(-1) for p in params])
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (min(n, flat.numel()),), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last timed step, one float32 DIR/<name>.npy each.
+    An array that would overflow DUMP_BUDGET keeps its leading entries (the first images of the batch)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float32)
+        if a.nbytes > left and a.ndim > 0:
+            row = a.nbytes // a.shape[0]
+            a = a[:max(0, left // row)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def bench_infer_c5(args, rank, world, device):
     """BASELINE config C5: BUCTD-TransPose-H-A6 256x192, 3x iterative-refinement inference, persons/s:
     one step = three chained passes, each forward -> device arg-max decode -> colored condition re-rendered from the
@@ -619,7 +648,8 @@ def bench_infer_c5(args, rank, world, device):
         mha["pairs"].append((e0, e1))
         return out
 
-    ops.mha_fwd = timed_mha
+    if args.full and not args.no_kernel_timer:
+        ops.mha_fwd = timed_mha
 
     @torch.no_grad()
     def step():
@@ -633,7 +663,7 @@ def bench_infer_c5(args, rank, world, device):
             out = net(x)
             preds, _, _ = ops.argmax_decode(out)
             joints = ops.scale(preds, alpha=4.0)          # heat-map -> crop coordinates (stride 4)
-        return joints
+        return joints, out
 
     def fence():
         if world > 1:
@@ -643,13 +673,16 @@ def bench_infer_c5(args, rank, world, device):
     for _ in range(args.warmup):
         step()
     fence()
-    mha["on"] = not args.no_kernel_timer
+    mha["on"] = args.full and not args.no_kernel_timer
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     dt = time.perf_counter() - t0
     mha["on"] = False
+    if args.dump_outputs and rank == 0:
+        # the refined key points (crop coordinates) and the heat-maps of the third pass
+        dump_outputs(args.dump_outputs, {"joints": last[0], "heatmaps": last[1]})
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -759,8 +792,17 @@ def main():
                          "memory, copied on the compute stream at the top of the step as the reference loop does; prefetch = pinned "
                          "host memory through core.function.DevicePrefetch (what train() does: the next batch's copies beside the "
                          "current step).  copy / prefetch give the PCIe-inclusive rate quoted in DESIGN.md - never the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the line can carry: the spread of the timed steps and the "
+                         "box's clocks (step_ms, box), the in-step and solo kernel timings with the roofline entries, the "
+                         "serialised-stream census, the exposed gradient-exchange time and bucket timeline (--gpus N, "
+                         "--one-rank-exchange) and the CPU-oracle baseline (train_c4); off: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full without the kernel timings and roofline entries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; the inputs are seeded, so two builds can be compared output for output)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, torch.distributed.run on this node,
@@ -815,6 +857,7 @@ def main():
     losses, acc = AverageMeter(), AverageMeter()
     model.train()
     state = {"pending": None}
+    last_out = {"output": None}
 
     graph_step = None
     if args.step_graph:
@@ -852,6 +895,8 @@ def main():
         if state["pending"] is not None:
             state["pending"].resolve(losses, acc)
         state["pending"] = _DeferredStats(loss, out, target_, args.batch)
+        if args.dump_outputs:
+            last_out["output"] = out
 
     def fence():
         if world > 1:
@@ -863,27 +908,38 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # the timed region runs the engine exactly as shipped: no per-launch events, no step-by-step blocks.  ONE event per step
-    # on the main stream (read after the fence) gives the spread of the steps; the clock / power probe is a child process
-    # started in the middle of the region (it reads the SMU while the GPU is under THIS load) and collected afterwards.
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # the timed region runs the engine exactly as shipped: no per-launch events, no step-by-step blocks.  Under --full, ONE
+    # event per step on the main stream (read after the fence) gives the spread of the steps, and the clock / power probe is a
+    # child process started in the middle of the region (it reads the SMU while the GPU is under THIS load) and collected
+    # afterwards.
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     probe = None
     t0 = time.perf_counter()
     for k in range(args.steps):
-        marks[k].record()
-        if k == args.steps // 2 and rank == 0:
-            probe = _box_probe_start()
+        if marks:
+            marks[k].record()
+            if k == args.steps // 2 and rank == 0:
+                probe = _box_probe_start()
         step()
-    marks[args.steps].record()
+    if marks:
+        marks[args.steps].record()
     fence()
     dt = time.perf_counter() - t0
-    step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
-    box = _box_probe_collect(probe) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the heat-maps, the loss and the decoded key points (the pending statistics of
+        # the last step), and a seeded sample of the parameters the Adam step wrote
+        last = state["pending"]
+        last.event.synchronize()
+        dump_outputs(args.dump_outputs, {"output": last_out["output"], "loss": last.loss, "preds": last.p_out,
+                                         "params_sample": param_sample(net.parameters())})
+    if marks:
+        step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
+        box = _box_probe_collect(probe) if rank == 0 else None
     # separate short pass for the in-step kernel durations: HIP events on the launching stream around the launches of the
     # roofline shape (every 4th BasicBlock of that shape goes through the step-by-step path so that its launches can be
     # bracketed); not part of `value`
     in_step = {k: (None, 0) for k in ("fwd", "dgrad", "wgrad")}
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         graph_step = None       # the bracketed launches below are eager launches
         install_timer(timer)
         step()
@@ -896,7 +952,7 @@ def main():
         in_step = {k: timer.mean_us(k) for k in ("fwd", "dgrad", "wgrad")}
     # exposed gradient-exchange time per step (N > 1): a pass with the device drained in front of and behind the exchange
     comm_ms = None
-    if world > 1 or args.one_rank_exchange:
+    if args.full and (world > 1 or args.one_rank_exchange):
         ts = []
         raw_sync = model.sync_gradients
 
@@ -934,7 +990,7 @@ def main():
         model.bucket_trace = None
     solo = {k: (None, 0) for k in in_step}
     grp = None
-    if not args.no_kernel_timer and rank == 0:
+    if args.full and not args.no_kernel_timer and rank == 0:
         # the same kernels alone on the GPU: 60 launches each (after 150 warm-up rounds) on a stage-4-branch-0 sized activation with one of the
         # model's own 48 -> 48 filters (forward with the BN-statistics epilogue, as in the step)
         timer.reset()
@@ -979,11 +1035,13 @@ def main():
                        # HIP streams of this rank: main + branch / weight-gradient streams (+ communication under --gpus N)
                        "hip_streams": 1 + len(ops.compute_streams(device)) + (1 if world > 1 or args.one_rank_exchange else 0),
                        "conv_math": args.conv_math, "loss": round(losses.avg, 6), "step_graph": bool(args.step_graph), "host_input": args.host_input},
+        }
+        if args.full:
             # is a slow line a slow box or a slow build?  the spread of the timed steps (GPU time between one event per step
             # on the main stream) and what the SMU reported in the middle of the timed region
-            "step_ms": {"min": round(step_ms[0], 3), "median": round(step_ms[len(step_ms) // 2], 3), "max": round(step_ms[-1], 3)},
-            "box": box,
-        }
+            out["step_ms"] = {"min": round(step_ms[0], 3), "median": round(step_ms[len(step_ms) // 2], 3),
+                              "max": round(step_ms[-1], 3)}
+            out["box"] = box
         if comm_ms is not None:
             out["allreduce_exposed_ms_per_step"] = comm_ms
             out["allreduce"] = ("flat fp32 gradient arena in ~48 MB buckets (tensors >= a bucket travel alone), one "
@@ -992,11 +1050,12 @@ def main():
             out["allreduce_buckets"] = {"backward_ms": backward_ms, "rank0": bucket_rows,
                                         "note": "start / end of every bucket's all-reduce on the communication stream, ms after "
                                                 "the backward pass started on the GPU (one extra step behind the timed region)"}
-        tag = {"train_c4": "c4", "train_c3": "c3", "train_c2": "c2"}[args.workload]
-        out["serialised"] = _serialised_census(tag)
-        out.update(roofline_objects(args, rshape, tag, in_step, solo, grp))
-        if world == 1 and not args.no_cpu_baseline and args.workload == "train_c4":
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            tag = {"train_c4": "c4", "train_c3": "c3", "train_c2": "c2"}[args.workload]
+            out["serialised"] = _serialised_census(tag)
+            out.update(roofline_objects(args, rshape, tag, in_step, solo, grp))
+            if world == 1 and not args.no_cpu_baseline and args.workload == "train_c4":
+                out["cpu_baseline"] = cpu_baseline()
     emit(out, rank, world, in_group=args.one_rank_exchange)
     if world > 1 or args.one_rank_exchange:
         dist.barrier()

@@ -31,7 +31,7 @@ bash scratch/serial_census.sh r06 > /dev/null 2>&1
 python scratch/r06_collect.py > /dev/null 2>&1
 for w in train_c4 train_c3 train_c2 infer_c5; do
   extra=""; [ $w = train_c4 ] || extra="--no-cpu-baseline"
-  timeout 600 python bench.py --workload $w --steps 20 --warmup 5 $extra 2>/dev/null | tail -1 > $O/bench_line_$w.json
+  timeout 600 python bench.py --full --workload $w --steps 20 --warmup 5 $extra 2>/dev/null | tail -1 > $O/bench_line_$w.json
 done
-timeout 300 python bench.py --condition mono --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_line_train_c4_mono.json
+timeout 300 python bench.py --full --condition mono --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_line_train_c4_mono.json
 ls -la $O

@@ -185,11 +185,11 @@ def test_validate_is_sharded_over_ranks(tmp_path):
 
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` (how the driver calls it) starts its two ranks itself and prints ONE JSON line from rank 0
-    with n_gpus = 2, the max-over-ranks step time and the exposed gradient-exchange time.  On a 1-GPU box both ranks sit on
-    GPU 0 over gloo (BUCTD_SINGLE_DEVICE / BUCTD_DIST_BACKEND are test hooks of engine.init_distributed)."""
+    with n_gpus = 2, the max-over-ranks step time and (--full) the exposed gradient-exchange time.  On a 1-GPU box both
+    ranks sit on GPU 0 over gloo (BUCTD_SINGLE_DEVICE / BUCTD_DIST_BACKEND are test hooks of engine.init_distributed)."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--workload", "train_c2", "--batch", "4", "--no-kernel-timer"],
+                        "--workload", "train_c2", "--batch", "4", "--no-kernel-timer", "--full"],
                        env=_env(BUCTD_DIST_BACKEND="gloo", BUCTD_SINGLE_DEVICE="1"), capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
@@ -224,7 +224,7 @@ def test_bench_with_four_ranks_on_one_device(tmp_path):
     exchange from the backward callbacks and the max-over-ranks clock of the 4-GPU point of the scaling curve."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--workload", "train_c2", "--batch", "2", "--no-kernel-timer"],
+                        "--workload", "train_c2", "--batch", "2", "--no-kernel-timer", "--full"],
                        env=_env(BUCTD_DIST_BACKEND="gloo", BUCTD_SINGLE_DEVICE="1"), capture_output=True, text=True,
                        timeout=1200)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]

@@ -228,6 +228,11 @@ SIGNATURES = {
     "buctd_flipback_avg": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "buctd_sgd_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _I, _I, _F, _P]),
     "buctd_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
+    # bf16 inference mode (csrc/conv_bf16.hip)
+    "buctd_bf16_pack_conv": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "buctd_bf16_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _SZ, _P]),
+    "buctd_bf16_fuse_sum": (_I, [C.POINTER(_P), _PI, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "buctd_bf16_from_f32": (_I, [_P, _L, _P, _P]),
 }
 
 _lib = None

@@ -712,7 +712,7 @@ class ForwardGraph(torch.nn.Module):
         if self._probe is None:
             ps = list(self.module.parameters()) + list(self.module.buffers())
             self._probe = ps[::max(1, len(ps) // 16)]
-        epoch = (ops.weights_epoch(), tuple(p._version for p in self._probe))
+        epoch = self._watch()
         if epoch != self._epoch:
             self.reset()
             self._epoch = epoch
@@ -735,6 +735,12 @@ class ForwardGraph(torch.nn.Module):
             return out
         return [o.clone() for o in out] if isinstance(out, list) else out.clone()
 
+    def _watch(self):
+        """What the graphs depend on besides the input: the optimizer epoch, a sample of tensor versions, and the wrapped
+        module's own `weights_stamp()` where it has one (Bf16Inference: every tensor, every BatchNorm batch count)."""
+        stamp = getattr(self.module, "weights_stamp", None)
+        return (ops.weights_epoch(), tuple(p._version for p in self._probe), stamp() if callable(stamp) else None)
+
     # ---- two lanes: independent requests beside each other -------------------------------------------------------------
     def submit(self, x):
         """Asynchronous forward for a serving loop: returns a handle at once, `handle.result()` makes the current stream wait
@@ -749,8 +755,7 @@ class ForwardGraph(torch.nn.Module):
         g = self._graphs.get(key)
         if g is None or not g["use"]:
             return _Ready(self.forward(x))          # settles / captures lane 0 (and watches the weights)
-        probe = (ops.weights_epoch(), tuple(p._version for p in self._probe))
-        if probe != self._epoch:
+        if self._watch() != self._epoch:
             return _Ready(self.forward(x))
         lanes = g.setdefault("lanes", [g])
         while len(lanes) < self.LANES:              # further lanes: their own graph, buffers and workspaces
@@ -804,6 +809,47 @@ class ForwardGraph(torch.nn.Module):
                 return time.perf_counter() - t0
             use = clock(graph.replay) <= clock(lambda: self.module(static))
         return {"graph": graph, "x": static, "out": out, "keep": keep, "use": use}
+
+
+class Bf16Inference(torch.nn.Module):
+    """bf16 inference mode of a models.pose_hrnet network (with or without the preNet): eval forwards run on folded bf16
+    filter images and bf16 NHWC activations, one bf16 MFMA per product with fp32 accumulation (ops_bf16,
+    csrc/conv_bf16.hip; accuracy bound in DESIGN.md 8).  Opt-in: nothing else dispatches to it.
+
+    `forward(x)` takes what the network takes (fp32 N x (3+Cc) x H x W NCHW, CPU or device) and returns fp32 heat-maps of
+    the network's shape.  Calls in train mode, with gradients enabled or with extra arguments go to the network unchanged.
+    Works as the `model` of core.function.validate(), inside dataset.pipeline.IterativeRefiner and under
+    ForwardGraph(Bf16Inference(net)).  The folded images are built on the first eval forward and rebuilt, in place, when
+    any parameter or buffer of the network changed: a tensor version or storage, the optimizer epoch
+    (ops.weights_epoch(): FusedAdam / FusedSGD), or a BatchNorm's pending batch count (train-mode forwards update running
+    statistics through raw pointers without a version bump).  The images live as long as the wrapper does, so graphs
+    captured through it keep reading valid memory.  CoAM, TransPose and PoseResNet networks raise NotImplementedError."""
+
+    def __init__(self, model):
+        super().__init__()
+        from . import ops_bf16
+        self.module = model
+        self._net = ops_bf16.Bf16Net(model)      # refuses unsupported networks
+        # conv weights channels_last now, as the fp32 engine makes them at first use (values unchanged): otherwise the
+        # preNet's first fp32 forward moves its weights, and the stamp below would repack everything once more
+        bnn.prepare_module(model)
+        self._tensors = list(model.parameters()) + list(model.buffers())
+        self._bns = [m for m in model.modules() if isinstance(m, bnn.BatchNorm2d)]
+        self._stamp = None
+        self.training = model.training          # ForwardGraph and validate() look at the wrapper's own flag
+
+    def weights_stamp(self):
+        return (ops.weights_epoch(), tuple(t._version for t in self._tensors), tuple(t.data_ptr() for t in self._tensors),
+                tuple(b._pending_batches for b in self._bns))
+
+    def forward(self, x, *args, **kwargs):
+        if self.module.training or torch.is_grad_enabled() or args or kwargs:
+            return self.module(x, *args, **kwargs)
+        stamp = self.weights_stamp()
+        if stamp != self._stamp:
+            self._net.repack()
+            self._stamp = stamp
+        return self._net.forward(x)
 
 
 class _Ready:

@@ -634,6 +634,33 @@ int buctd_nms(int* keep_out, int* num_out, const float* boxes, int boxes_num, in
  * order = argsort of the scores, descending, computed by the caller like the .pyx does with numpy. */
 int buctd_cpu_nms(const float* dets, int n, const int* order, float thresh, int* keep_out, int* num_out);
 
+/* ------------------------------------------------------------- bf16 inference --- */
+/* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).
+ * bf16 tensors are passed as raw bit patterns (uint16_t).  Activations bf16 NHWC [N][H][W][C]; a conv layer is a
+ * filter image wimg [Co][Kp] bf16, K = (r * R + s) * Ci + ci, zero-padded from R*R*Ci up to Kp = roundup(R*R*Ci, 32),
+ * plus an fp32 bias [Co]; both come from buctd_bf16_pack_conv.  One bf16 MFMA per product, fp32 accumulation. */
+/* wimg/bias_out = the conv (fp32 weight element (co, ci, r, s) at w[co*s_co + ci*s_ci + r*s_r + s*s_s], optional
+ * conv_bias) with an optional eval BatchNorm folded in: scale = gamma / sqrt(var + eps) evaluated in fp64 and rounded
+ * to fp32, then in fp32 w * scale rounded once to bf16 (nearest even) and bias (conv_bias - mean) * scale + beta.
+ * gamma NULL: no BatchNorm. */
+int buctd_bf16_pack_conv(const float* w, long s_co, long s_ci, long s_r, long s_s, int Co, int Ci, int R,
+                         const float* conv_bias, const float* gamma, const float* beta, const float* running_mean,
+                         const float* running_var, float eps, uint16_t* wimg, float* bias_out, void* stream);
+/* y = relu?(conv(x, wimg) + bias (+ residual)); R in {1, 3}, stride in {1, 2}, Ho = (H + 2 pad - R) / stride + 1.
+ * out_f32_nchw = 0: y is bf16 NHWC [N][Ho][Wo][Co] and residual (optional) bf16 of the same shape;
+ * out_f32_nchw = 1: y is fp32 NCHW [N][Co][Ho][Wo] (the heat-map head), no residual.  The kernels need no workspace
+ * (workspace may be NULL). */
+int buctd_bf16_conv(const uint16_t* x, int N, int H, int W, int Ci, const uint16_t* wimg, const float* bias, int Co,
+                    int R, int stride, int pad, const uint16_t* residual, int relu, int out_f32_nchw, void* y,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* HighResolutionModule fuse row in bf16: out = relu(sum_j upsample_nearest(term_j, 2^shift_j)), terms read as bf16
+ * and summed in fp32 in the order j = 0, 1, ..., rounded once; terms[j] is [N][H>>shift_j][W>>shift_j][C], C % 8 == 0,
+ * up to 4 terms. */
+int buctd_bf16_fuse_sum(const uint16_t* const* terms, const int* shifts, int nterms, int N, int H, int W, int C,
+                        int relu, uint16_t* out, void* stream);
+/* y = bf16(x), nearest even, n elements */
+int buctd_bf16_from_f32(const float* x, long n, uint16_t* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

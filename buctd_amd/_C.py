@@ -222,6 +222,7 @@ SIGNATURES = {
     "buctd_nms": (_I, [_P, _P, _P, _I, _I, _F, _P, _SZ, _P]),
     "buctd_cpu_nms": (_I, [_P, _I, _P, _F, _P, _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
     "buctd_cond_render_workspace": (_SZ, [_I, _I, _I, _I]),
     "buctd_cond_render": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),

@@ -343,7 +343,10 @@ PAIRED_FLIP_FORWARD = True
 
 
 def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_log_dir, writer_dict=None, epoch=-1,
-             print_prefix=''):
+             print_prefix='', use_dark=False):
+    """reference lib/core/function.py:178-296, same positional signature.  use_dark: decode the final predictions with
+    get_final_preds(..., use_dark=True) (the DARK kernel, applied to the flip-merged heat-maps where the flip test is on);
+    the accuracy figure keeps the plain arg-max, as in the reference."""
     batch_time, losses, acc = AverageMeter(), AverageMeter(), AverageMeter()
     model.eval()
     rank, world = _dist_world()
@@ -391,7 +394,7 @@ def validate(config, val_loader, val_dataset, model, criterion, output_dir, tb_l
         target_weight = it.pop('target_weight').cuda(non_blocking=True)
         loss = criterion(output, it['target'], target_weight)
         it['stats'] = _DeferredStats(loss, output, it['target'], it['count'])
-        it['decode'] = DeferredFinalPreds(config, output)
+        it['decode'] = DeferredFinalPreds(config, output, use_dark=use_dark)
         it['output'] = output
 
     def host_part(it, tick):

@@ -52,16 +52,13 @@ extern "C" int buctd_joints_mse(const float* pred, const float* gt, const float*
 }
 
 // ------------------------------------------------------------ argmax decode ----
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ hm, int HW, int W,
-                                                     float* __restrict__ preds, float* __restrict__ maxvals,
-                                                     int32_t* __restrict__ idx, float* __restrict__ quarter) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
-  const long row = blockIdx.x;
+// First-index arg-max of one row h[0..HW) over a 256-thread block (numpy argmax order); the result is valid in thread 0.
+__device__ __forceinline__ void block_argmax_256(const float* __restrict__ h, int HW, float& best_out, int& bi_out,
+                                                 float* sv /* >= 4 */, int* si /* >= 4 */) {
   float best = -INFINITY;
   int bi = 0x7fffffff;
   for (int i = threadIdx.x; i < HW; i += 256) {
-    const float v = hm[row * HW + i];
+    const float v = h[i];
     if (v > best || (v == best && i < bi)) {
       best = v;
       bi = i;
@@ -88,11 +85,32 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ h
         bi = si[k];
       }
     if (bi == 0x7fffffff) bi = 0;  // all-NaN row: numpy argmax would return the first NaN; not reachable here
-    const float m = best > 0.f ? 1.f : 0.f;
-    preds[row * 2 + 0] = (float)(bi % W) * m;
-    preds[row * 2 + 1] = floorf((float)bi / (float)W) * m;
-    maxvals[row] = best;
-    if (idx) idx[row] = bi;
+  }
+  best_out = best;
+  bi_out = bi;
+}
+
+// get_max_preds' outputs for one row from its arg-max (thread 0 only)
+__device__ __forceinline__ void store_max_preds(long row, int W, float best, int bi, float* __restrict__ preds,
+                                                float* __restrict__ maxvals, int32_t* __restrict__ idx) {
+  const float m = best > 0.f ? 1.f : 0.f;
+  preds[row * 2 + 0] = (float)(bi % W) * m;
+  preds[row * 2 + 1] = floorf((float)bi / (float)W) * m;
+  maxvals[row] = best;
+  if (idx) idx[row] = bi;
+}
+
+__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ hm, int HW, int W,
+                                                     float* __restrict__ preds, float* __restrict__ maxvals,
+                                                     int32_t* __restrict__ idx, float* __restrict__ quarter) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const long row = blockIdx.x;
+  float best;
+  int bi;
+  block_argmax_256(hm + row * HW, HW, best, bi, sv, si);
+  if (threadIdx.x == 0) {
+    store_max_preds(row, W, best, bi, preds, maxvals, idx);
     if (quarter) {
       // reference core/inference.py:68-77 (POST_PROCESS): a quarter pixel towards the higher neighbour, only for
       // peaks with 1 < px < W-1 and 1 < py < H-1 (a masked peak decodes to (0,0) and never qualifies)
@@ -126,6 +144,107 @@ extern "C" int buctd_argmax_decode_refined(const float* hm, int rows, int H, int
   hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, hm, H * W, W, preds, maxvals, idx,
                      quarter);
   BUCTD_CHECK_LAUNCH("buctd_argmax_decode_refined");
+  return BUCTD_OK;
+}
+
+// -------------------------------------------------------------- DARK decode ----
+// get_final_preds(use_dark=True) (DarkPose; reference lib/core/inference.py:90-151): arg-max of the unblurred map as
+// above, then, for peaks with 1 < px < W-2 and 1 < py < H-2, the 11x11 Gaussian blur of the zero-padded map (float64,
+// stored to float32), float32 renormalisation to the original peak, log(max(., 1e-10)) and one Newton step at the peak.
+// One 256-thread workgroup per map.  The vertical pass is kept in LDS as float64 ([H*W] doubles, hence the size limit);
+// the horizontal pass reduces the blurred map's max; thread 0 then recomputes the 13 blurred samples it needs and solves
+// the 2x2 system.  Both passes add the taps in the order of core/inference.py's numpy restatement (rows first, tap 0
+// first, -ffp-contract=off), so the blurred float32 values are bit-equal to it.
+// gaussian_kernel_1d(11): sigma 0.3*((11-1)*0.5-1)+0.8 = 2, exp(-x^2/(2 sigma^2)) normalised to sum 1 in float64
+__constant__ double kDarkTaps[11] = {0.008812229292562283, 0.027143577143479373, 0.06511405659938267, 0.1216490730138096,
+                                     0.17699835683135567,  0.20056541423882085,  0.17699835683135567, 0.1216490730138096,
+                                     0.06511405659938267,  0.027143577143479373, 0.008812229292562283};
+
+__device__ __forceinline__ double dark_vpass(const float* __restrict__ h, int H, int W, int y, int x) {
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < 11; ++t) {
+    const int yy = y + t - 5;
+    if (yy >= 0 && yy < H) acc = acc + kDarkTaps[t] * (double)h[yy * W + x];
+  }
+  return acc;
+}
+__device__ __forceinline__ float dark_hpass(const double* mid, int W, int y, int x) {
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < 11; ++t) {
+    const int xx = x + t - 5;
+    if (xx >= 0 && xx < W) acc = acc + kDarkTaps[t] * mid[y * W + xx];
+  }
+  return (float)acc;
+}
+
+__global__ __launch_bounds__(256) void dark_kernel(const float* __restrict__ hm, int H, int W, float* __restrict__ preds,
+                                                   float* __restrict__ maxvals, int32_t* __restrict__ idx,
+                                                   float* __restrict__ offset) {
+  extern __shared__ double mid[];  // [H*W]: the vertical pass
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ int s_peak;           // bi of an eligible peak, -1 when the reference leaves the coordinate unchanged
+  const long row = blockIdx.x;
+  const int HW = H * W;
+  const float* h = hm + row * HW;
+  float best;
+  int bi;
+  block_argmax_256(h, HW, best, bi, sv, si);
+  if (threadIdx.x == 0) {
+    store_max_preds(row, W, best, bi, preds, maxvals, idx);
+    // a masked peak (best <= 0) decodes to (0, 0) and never qualifies
+    const int px = best > 0.f ? bi % W : 0, py = best > 0.f ? bi / W : 0;
+    const bool go = px > 1 && px < W - 2 && py > 1 && py < H - 2;
+    s_peak = go ? bi : -1;
+    if (!go) {
+      offset[row * 2 + 0] = 0.f;
+      offset[row * 2 + 1] = 0.f;
+    }
+  }
+  __syncthreads();
+  const int peak = s_peak;
+  if (peak < 0) return;  // uniform over the workgroup
+  for (int i = threadIdx.x; i < HW; i += 256) mid[i] = dark_vpass(h, H, W, i / W, i % W);
+  __syncthreads();
+  float m = -INFINITY;
+  for (int i = threadIdx.x; i < HW; i += 256) m = fmaxf(m, dark_hpass(mid, W, i / W, i % W));
+  m = block_max_256(m, sv);
+  if (threadIdx.x == 0) {
+    const float ratio = best / m;  // reference: hm *= origin_max / np.max(hm), float32
+    const int px = peak % W, py = peak / W;
+    // log(max(blurred * ratio, 1e-10)) at (y, x), rounded to float32 (np.maximum keeps a NaN)
+    auto L = [&](int y, int x) -> double {
+      float v = dark_hpass(mid, W, y, x) * ratio;
+      v = v < 1e-10f ? 1e-10f : v;
+      return (double)(float)log((double)v);
+    };
+    const double c = L(py, px);
+    const double dx = 0.5 * (L(py, px + 1) - L(py, px - 1));
+    const double dy = 0.5 * (L(py + 1, px) - L(py - 1, px));
+    const double dxx = 0.25 * (L(py, px + 2) - 2.0 * c + L(py, px - 2));
+    const double dxy = 0.25 * (L(py + 1, px + 1) - L(py - 1, px + 1) - L(py + 1, px - 1) + L(py - 1, px - 1));
+    const double dyy = 0.25 * (L(py + 2, px) - 2.0 * c + L(py - 2, px));
+    const double det = dxx * dyy - dxy * dxy;
+    double ox = 0.0, oy = 0.0;
+    if (det != 0.0) {  // offset = -H^-1 [dx, dy]
+      ox = -((dyy * dx - dxy * dy) / det);
+      oy = -((dxx * dy - dxy * dx) / det);
+    }
+    offset[row * 2 + 0] = (float)ox;
+    offset[row * 2 + 1] = (float)oy;
+  }
+}
+extern "C" int buctd_argmax_decode_dark(const float* hm, int rows, int H, int W, float* preds, float* maxvals,
+                                        int32_t* idx, float* offset, void* stream) {
+  BUCTD_CHECK_ARG(hm && preds && maxvals && offset && rows > 0 && H > 0 && W > 0,
+                  "buctd_argmax_decode_dark: bad argument");
+  BUCTD_CHECK_ARG((long)H * W <= BUCTD_DARK_MAX_PIXELS,
+                  "buctd_argmax_decode_dark: %dx%d heat-map exceeds the %d-pixel limit", H, W, BUCTD_DARK_MAX_PIXELS);
+  hipLaunchKernelGGL(dark_kernel, dim3(rows), dim3(256), (size_t)H * W * sizeof(double), (hipStream_t)stream, hm, H, W,
+                     preds, maxvals, idx, offset);
+  BUCTD_CHECK_LAUNCH("buctd_argmax_decode_dark");
   return BUCTD_OK;
 }
 

@@ -242,10 +242,11 @@ class DeviceSamplePipeline:
 
 class IterativeRefiner:
     """BUCTD iterative refinement in one process (README.md:104 '3x iterative refinement'; reference = three CLI runs
-    chained through the results json)."""
+    chained through the results json).  use_dark: decode every pass with get_final_preds(..., use_dark=True)."""
 
-    def __init__(self, cfg, model, pipeline, in_vis_thre=None):
+    def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False):
         self.cfg, self.model, self.pipe = cfg, model, pipeline
+        self.use_dark = bool(use_dark)
         self.in_vis_thre = cfg.TEST.IN_VIS_THRE if in_vis_thre is None else in_vis_thre
 
     @staticmethod
@@ -287,7 +288,7 @@ class IterativeRefiner:
             out = out[-1] if isinstance(out, list) else out
             center = np.stack([g["center"] for g in geos])
             scale = np.stack([g["scale"] for g in geos])
-            coords, maxvals = get_final_preds(self.cfg, out, center, scale)
+            coords, maxvals = get_final_preds(self.cfg, out, center, scale, use_dark=self.use_dark)
             box_score = np.array([float(r.get("score", 1)) for r in records])
             score, kpt_score = self.rescore(maxvals, box_score, self.in_vis_thre)
             preds = np.concatenate([coords, maxvals], axis=2)

@@ -1437,6 +1437,27 @@ def argmax_decode(hm, refine=False, preds_out=None):
     return preds, maxvals, idx
 
 
+# H*W limit of dark_decode (include/buctd_hip.h BUCTD_DARK_MAX_PIXELS)
+DARK_MAX_PIXELS = 8000
+
+
+def dark_decode(hm):
+    """get_final_preds(use_dark=True)'s device half: (preds [N,K,2], maxvals [N,K,1], idx [N,K]) exactly as argmax_decode,
+    and the DARK Taylor offsets [N,K,2] in heat-map pixels ((0, 0) where the reference leaves a coordinate unchanged).
+    hm is not modified.  H*W <= DARK_MAX_PIXELS."""
+    if hm.dim() != 4 or hm.dtype != torch.float32:
+        raise _C.BuctdHipError("dark_decode: heat-maps must be a fp32 [N, K, H, W] tensor")
+    hm = hm.contiguous()
+    N, K, H, W = hm.shape
+    preds = torch.empty((N, K, 2), dtype=torch.float32, device=hm.device)
+    maxvals = torch.empty((N, K, 1), dtype=torch.float32, device=hm.device)
+    idx = torch.empty((N, K), dtype=torch.int32, device=hm.device)
+    offset = torch.empty((N, K, 2), dtype=torch.float32, device=hm.device)
+    check(lib().buctd_argmax_decode_dark(ptr(hm), N * K, H, W, ptr(preds), ptr(maxvals), ptr(idx), ptr(offset),
+                                         stream_ptr()), "argmax_decode_dark")
+    return preds, maxvals, idx, offset
+
+
 def scalar_to_host(src, dst):
     """One float from device memory into a pinned host tensor, written by a kernel on the current stream (no copy engine)."""
     if not (dst.is_pinned() and dst.dtype == torch.float32 and dst.numel() == 1 and src.numel() == 1):

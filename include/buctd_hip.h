@@ -420,6 +420,14 @@ int buctd_argmax_decode(const float* hm, int rows, int H, int W, float* preds, f
  * (+-0.25 | 0, +-0.25 | 0) offset towards the higher neighbour for interior peaks, (0, 0) otherwise. */
 int buctd_argmax_decode_refined(const float* hm, int rows, int H, int W, float* preds, float* maxvals, int32_t* idx,
                                 float* quarter, void* stream);
+/* get_final_preds(use_dark=True) (DarkPose, core/inference.py:90-151): preds / maxvals / idx exactly as
+ * buctd_argmax_decode (from the unblurred map); offset[row] = the Taylor (Newton) step in heat-map pixels on
+ * log(max(renormalised 11x11 Gaussian blur, 1e-10)) for peaks with 1 < px < W-2 and 1 < py < H-2, (0, 0) otherwise
+ * or where the Hessian's determinant is 0.  POST_PROCESS does not apply.  H*W <= BUCTD_DARK_MAX_PIXELS (the float64
+ * vertical pass sits in LDS); larger maps return BUCTD_EINVAL. */
+#define BUCTD_DARK_MAX_PIXELS 8000
+int buctd_argmax_decode_dark(const float* hm, int rows, int H, int W, float* preds, float* maxvals, int32_t* idx,
+                             float* offset, void* stream);
 /* generate_target (dataset/JointsDataset.py:397-453): joints [B][K][3] (crop px), vis [B][K] ->
  * target [B][K][Hh][Wh], weight [B][K]. */
 int buctd_gaussian_target(const float* joints, const float* vis, int B, int K, int Hh, int Wh, float stride_x,

@@ -146,7 +146,6 @@ SIGNATURES = {
     "buctd_gconv_x6_fwd_acc": (_I, [_I] * 6 + [_P] * 6),
     "buctd_conv3x3_bf16x6_group": (_I, [_I, C.POINTER(C3Conv), _P]),
     "buctd_conv3x3_bf16x6_group_eval": (_I, [_I, C.POINTER(C3ConvEval), _P]),
-    "buctd_conv3x3_bf16x6_persistent": (_I, [_I]),
     "buctd_conv3x3_bf16x6_group_workgroups": (_I, [_I, C.POINTER(C3Conv)]),
     "buctd_gconv_wgrad_x6_supported": (_I, [_I] * 6),
     "buctd_gconv_wgrad_x6_workspace": (_SZ, [_I] * 6),
@@ -180,8 +179,6 @@ SIGNATURES = {
     "buctd_nhwc_to_nchw": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "buctd_fuse_sum": (_I, [C.POINTER(_P), _PI, _I, _I, _I, _I, _I, _I, _P, _P]),
     "buctd_fuse_sum_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "buctd_fuse_sum_bwd_bnstat": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
-                                       C.POINTER(_P), _P]),
     "buctd_resize_bilinear": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "buctd_maxpool3x3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "buctd_maxpool3x3s2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

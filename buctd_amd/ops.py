@@ -13,23 +13,11 @@ autograd, so no AccumulateGrad add kernels run.
 """
 import ctypes as C
 import math
-import os
 
 import torch
 
 from . import _C
 from ._C import ConvDesc, MatmulDesc, check, lib, ptr, stream_ptr
-
-# Engine switches and their product defaults.  The product reads NO environment variable for them: experiments (scratch/ A/B
-# scripts) set BUCTD_TUNING=1, and only then buctd_amd/_tuning.py is imported and overrides entries from BUCTD_<NAME>.
-# (The only other variables the package looks at are the two test hooks of engine.init_distributed - BUCTD_SINGLE_DEVICE,
-# BUCTD_DIST_BACKEND - documented there.)
-_SW = {"CONV_MATH": "bf16x6", "PREP_BATCH": "1", "GCONV_X6": "1", "GCONV_MASK": "15", "NATIVE_BLOCK": "1", "FUSED_BOTTLENECK": "1",
-       "FUSE_BN_IN": "1", "FC_O_X6": "1", "MHA_X6": "1", "MHA_PRESPLIT": "1", "ATTN_X6": "1", "WGRAD_STREAM": "1", "WGRAD_STREAMS": "1",
-       "WGRAD_PRIO": "-1", "BRANCH_STREAMS": "1", "BRANCH_MAX": "2", "BRANCH_PRIO": "0", "C3_PERSISTENT": "0", "STATS_ZERO_COPY": "1", "FUSE_BWD_BNSTAT": "0", "FUSE_BWD_BNSTAT_S0": "0"}
-if os.environ.get("BUCTD_TUNING") == "1":
-    from . import _tuning
-    _tuning.override(_SW)
 
 # hipGraph capture of a training step (engine.StepGraph)
 # --------------------------------------------------------------------------------------
@@ -374,7 +362,7 @@ def _memo(key, fn):
 
 
 _CONV_MATH_MODES = ("fp32", "bf16x6", "bf16x3")
-_conv_math = {"mode": _SW["CONV_MATH"]}
+_conv_math = {"mode": "bf16x6"}
 
 
 def set_conv_math(mode):
@@ -389,10 +377,6 @@ def set_conv_math(mode):
     if mode not in _CONV_MATH_MODES:
         raise ValueError(f"conv math mode must be one of {_CONV_MATH_MODES}")
     _conv_math["mode"] = mode
-
-
-if _conv_math["mode"] not in _CONV_MATH_MODES:
-    raise ValueError(f"BUCTD_CONV_MATH must be one of {_CONV_MATH_MODES}")
 
 
 def get_conv_math():
@@ -416,8 +400,7 @@ def _bf16x3_ok(d):
 _weights_epoch = {"n": 0}
 # After an optimizer step every prepared filter image of the model is rebuilt by ONE launch on the stream of the step
 # (refresh_prepared, called by FusedAdam) instead of ~430 small launches in front of the convolutions that need them:
-# off the critical path of the next forward / backward, 430 launches less per step.  BUCTD_PREP_BATCH=0: lazy refresh.
-_PREP_BATCH = _SW["PREP_BATCH"] == "1"
+# off the critical path of the next forward / backward, 430 launches less per step.
 _prep_registry = {"weights": [], "table": None, "table_key": None, "event": None, "stream": None, "waited": set()}
 
 
@@ -433,7 +416,7 @@ def weights_updated():
 
 def refresh_prepared(device):
     """Rebuild all registered prepared filter images now (one launch on the current stream)."""
-    if _PREP_BATCH and _conv_math["mode"] != "fp32":
+    if _conv_math["mode"] != "fp32":
         _prep_all(device)
 
 
@@ -547,7 +530,7 @@ def _conv3x3_prepared(w, flip):
     epoch = _weights_epoch["n"]
     key = (w.data_ptr(), w._version, epoch, _conv_math["mode"])
     cache = getattr(w, "_buctd_prep", None)
-    if cache is not None and cache[0] != key and cache[0][:2] == key[:2] and cache[0][3:] == key[3:] and _PREP_BATCH:
+    if cache is not None and cache[0] != key and cache[0][:2] == key[:2] and cache[0][3:] == key[3:]:
         _prep_all(w.device)       # rewritten in place by the optimizer kernel: batch-refresh all registered images
     if cache is None or cache[0] != key:
         first = cache is None
@@ -612,8 +595,6 @@ def _conv3x3_bf16x3(x, w, flip, cin, cout, bias, scale, shift, residual, relu, s
 
 
 # ---- gathered bf16x6 convolutions (csrc/conv_gather_x6.hip): 1x1 and stride-2 3x3, forward + data gradient ----------------
-_GCONV_X6 = _SW["GCONV_X6"] != "0"
-_GCONV_MASK = int(_SW["GCONV_MASK"])     # experiments: bit 0/1 = 1x1 forward / data gradient, 2/3 = stride-2 3x3
 
 
 def _gconv_kind(d):
@@ -627,11 +608,9 @@ def _gconv_kind(d):
 
 def _gconv_ok(d, direction):
     """True when this convolution (direction 0 forward, 1 data gradient) takes the gathered bf16x6 kernel."""
-    if _conv_math["mode"] != "bf16x6" or not _GCONV_X6:
+    if _conv_math["mode"] != "bf16x6":
         return False
     kind = _gconv_kind(d)
-    if kind and not (_GCONV_MASK >> (2 * (kind - 1) + direction)) & 1:
-        return False
     return kind != 0 and _memo(("gcok", kind, d.N, d.H, d.W, d.Ci, d.Co, direction),
                                lambda: lib().buctd_gconv_x6_supported(kind, d.N, d.H, d.W, d.Ci, d.Co, direction) == 1)
 
@@ -643,7 +622,7 @@ def _gconv_prepared(w, kind, direction):
     Co, Ci = _wshape(w)[0], _wshape(w)[1]
     key = (w.data_ptr(), w._version, _weights_epoch["n"])
     cache = getattr(w, "_buctd_gprep", None)
-    if cache is not None and cache[0] != key and cache[0][:2] == key[:2] and _PREP_BATCH:
+    if cache is not None and cache[0] != key and cache[0][:2] == key[:2]:
         _prep_all(w.device)           # same storage, new optimizer epoch: batch-refresh every registered image
     if cache is None or cache[0] != key or cache[1] != kind:
         first = cache is None
@@ -687,10 +666,7 @@ def _gconv_fwd(x, w, d, bias, scale, shift, residual, relu, stats):
     return (y, part, info) if stats else y
 
 
-_NATIVE_BLOCK = _SW["NATIVE_BLOCK"] == "1"
-if _SW["C3_PERSISTENT"] == "1":      # experiments: the persistent form of the train-mode 3x3 launches (include/buctd_hip.h)
-    lib().buctd_conv3x3_bf16x6_persistent(1)
-_FUSED_BOTTLENECK = {"on": _SW["FUSED_BOTTLENECK"] == "1"}
+_FUSED_BOTTLENECK = {"on": True}
 
 
 def fused_bottleneck_on():
@@ -702,14 +678,11 @@ def set_fused_bottleneck(on):
     old = _FUSED_BOTTLENECK["on"]
     _FUSED_BOTTLENECK["on"] = bool(on)
     return old
-# experiment switches, read ONCE at import (the hot path consults module constants, never the environment)
-_FUSE_BN_IN = _SW["FUSE_BN_IN"] == "1"
-_FUSE_BWD_BNSTAT = _SW["FUSE_BWD_BNSTAT"] == "1"
-_FUSE_BWD_BNSTAT_S0 = _SW["FUSE_BWD_BNSTAT_S0"] == "1"
-_FC_O_X6 = _SW["FC_O_X6"] != "0"
-_MHA_X6 = _SW["MHA_X6"] != "0"
-_MHA_PRESPLIT = _SW["MHA_PRESPLIT"] != "0"
-_ATTN_X6 = _SW["ATTN_X6"] != "0"
+
+
+_FUSE_BN_IN = True        # conv2 of a BasicBlock applies bn1 (+ReLU) while it stages its input (off: the unfused reference; tests)
+_MHA_X6 = True            # multi-head attention on the bf16x6 kernels in the bf16x6 mode (bench.py reads it)
+_MHA_PRESPLIT = True      # ... with keys / values split once into the workspace (off: split in the kernel; tests, bench.py)
 # optional veto: callable(x_shape) -> True sends a BasicBlock through the step-by-step path (bench.py brackets every launch
 # of its roofline shape with HIP events, which it can only do from the host mirror)
 native_block_veto = {"fn": None}
@@ -717,7 +690,7 @@ native_block_veto = {"fn": None}
 
 def native_chain_ok(x_shape):
     """True when a chain of BasicBlocks on this activation shape may take the one-call-per-direction path."""
-    return (_NATIVE_BLOCK and _conv_math["mode"] == "bf16x6" and native_block_veto["fn"] is None)
+    return _conv_math["mode"] == "bf16x6" and native_block_veto["fn"] is None
 
 
 def bn_in_fusable(x_shape, w):
@@ -810,9 +783,6 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, bias=None, stats=False, residual
     return (dx, part, info) if stats else dx
 
 
-_GCONV_WGRAD = {"on": True}      # 1x1 / stride-2 weight gradients on the bf16x6 kernel (off: the exact-fp32 MFMA kernel; tests)
-
-
 def conv_wgrad(x, dy, w_like, stride=1, pad=0, out=None, accumulate=0, x_bn=None, stream=None):
     """x_bn = (mean, invstd, gamma, beta, relu): like conv_fwd's in_bn, for the X operand of the weight gradient.
     stream: a torch.cuda.Stream to launch on WITHOUT making it current (entering a stream context costs ~15 us of host time
@@ -853,7 +823,7 @@ def conv_wgrad(x, dy, w_like, stride=1, pad=0, out=None, accumulate=0, x_bn=None
             return out
     if x_bn is not None:
         raise _C.BuctdHipError("conv_wgrad: x_bn needs the bf16x6 3x3 kernel (check bn_in_fusable first)")
-    kind = _gconv_kind(d) if mode == "bf16x6" and _GCONV_WGRAD["on"] else 0
+    kind = _gconv_kind(d) if mode == "bf16x6" else 0
     if kind:
         need = _memo(("gwg", kind, d.N, d.H, d.W, d.Ci, d.Co),
                      lambda: (int(lib().buctd_gconv_wgrad_x6_workspace(kind, d.N, d.H, d.W, d.Ci, d.Co))
@@ -873,25 +843,24 @@ def conv_wgrad(x, dy, w_like, stride=1, pad=0, out=None, accumulate=0, x_bn=None
 # Weight gradients are off the critical path of the backward pass (nothing downstream of dgrad needs them), so they
 # run on a second HIP stream and fill the CUs that the latency-bound BN / dgrad chain leaves idle.  The join is queued
 # as an autograd end-of-backward callback, so param.grad is complete on the caller's stream when backward() returns.
-_side = {"on": _SW["WGRAD_STREAM"] == "1", "streams": {}, "joined": True, "rr": 0,
-         "n": max(1, int(_SW["WGRAD_STREAMS"]))}   # more than one measured slower (L2 contention)
+# One such stream per device: more than one measured slower (L2 contention).
+_side = {"on": True, "streams": {}, "joined": True}
 
 
 # The weight-gradient stream runs at HIGH HIP priority: the critical path of the backward pass runs along it for half of the
 # time (profiles/r04_critical_path.txt: 12.9 ms of weight gradients + 3.5 ms of their slab reductions on the chain), so its
 # kernels should get free workgroup slots before the main stream's: 454.0 -> 457.2 img/s (interleaved A/B on one box, round
 # 4; the branch streams at high priority cost 1 %).
-_SIDE_PRIO = int(_SW["WGRAD_PRIO"])
+_SIDE_PRIO = -1
 
 
 def _side_stream(device):
-    """Weight-gradient streams, used round-robin (consecutive layers' gradients are independent of each other)."""
-    _side["rr"] = (_side["rr"] + 1) % _side["n"]
-    key = (device.index, _side["rr"])
-    st = _side["streams"].get(key)
+    """The weight-gradient stream of `device`."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    st = _side["streams"].get(idx)
     if st is None:
         st = torch.cuda.Stream(device=device, priority=_SIDE_PRIO)
-        _side["streams"][key] = st
+        _side["streams"][idx] = st
     return st
 
 
@@ -900,23 +869,18 @@ def copy_stream(device):
     idle during the forward pass, and no additional HIP stream.  None where the engine forks no such stream."""
     if not (_side["on"] and device.type == "cuda"):
         return None
-    key = (device.index if device.index is not None else torch.cuda.current_device(), 0)
-    st = _side["streams"].get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=device, priority=_SIDE_PRIO)
-        _side["streams"][key] = st
-    return st
+    return _side_stream(device)
 
 
 def side_streams(device):
-    """The weight-gradient streams created so far on `device`."""
-    return [st for (idx, _), st in _side["streams"].items() if idx == device.index]
+    """The weight-gradient stream of `device`, if it has been created."""
+    return [st for idx, st in _side["streams"].items() if idx == device.index]
 
 
 def wait_side_stream(stream=None):
     """Make `stream` (default: the current one) wait for everything enqueued so far on the streams this module owns
     (weight-gradient stream and branch streams)."""
-    for (idx, _), st in _side["streams"].items():
+    for idx, st in _side["streams"].items():
         target = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", idx))
         target.wait_stream(st)
     for (idx, _), st in _branch["streams"].items():
@@ -929,12 +893,13 @@ def wait_side_stream(stream=None):
 # enqueued on separate HIP streams: the low-resolution branches are launch/latency bound and hide under the
 # bandwidth-bound high-resolution one.  Autograd replays every backward node on the stream of its forward op, so the
 # backward pass inherits the same concurrency.
-_branch = {"on": _SW["BRANCH_STREAMS"] == "1", "streams": {}}
+_branch = {"on": True, "streams": {}}
 
 
 # main + 2 branch streams + the weight-gradient stream = the 4 HIP hardware queues: no two streams share a queue by
 # accident (HRNet branches 2 and 3, the cheapest, share the last stream): 453 -> 468 img/s
-_BRANCH_MAX = int(_SW["BRANCH_MAX"])
+_BRANCH_MAX = 2
+_BRANCH_PRIO = 0
 
 
 def set_stream_forks(branch, wgrad=None):
@@ -961,21 +926,17 @@ def compute_streams(device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     # branch streams above the current cap were created before it was lowered and are no longer handed out
     return ([st for (d, i), st in _branch["streams"].items() if d == idx and i <= _BRANCH_MAX] +
-            [st for (d, _), st in _side["streams"].items() if d == idx])
+            [st for d, st in _side["streams"].items() if d == idx])
 
 
 def reserve_compute_streams(device):
-    """Create the branch streams (up to the cap) and the weight-gradient stream(s) of `device` now; returns them.  See
+    """Create the branch streams (up to the cap) and the weight-gradient stream of `device` now; returns them.  See
     engine.reserve_streams: streams are bound to hardware queues in the order of their first use."""
     out = []
     if _branch["on"]:
         out += [_branch_stream(device, i) for i in range(1, _BRANCH_MAX + 1)]
     if _side["on"]:
-        for rr in range(_side["n"]):
-            key = (device.index, rr)
-            if key not in _side["streams"]:
-                _side["streams"][key] = torch.cuda.Stream(device=device, priority=_SIDE_PRIO)
-            out.append(_side["streams"][key])
+        out.append(_side_stream(device))
     return out
 
 
@@ -984,7 +945,7 @@ def _branch_stream(device, i):
     key = (device.index, i)
     st = _branch["streams"].get(key)
     if st is None:
-        st = torch.cuda.Stream(device=device, priority=int(_SW["BRANCH_PRIO"]))
+        st = torch.cuda.Stream(device=device, priority=_BRANCH_PRIO)
         _branch["streams"][key] = st
     return st
 
@@ -1040,7 +1001,6 @@ def fork_join(fns, inputs, tag=0):
 
 def _join_side():
     _side["joined"] = True
-    _bwd_sums.clear()
     wait_side_stream()
 
 
@@ -1138,7 +1098,7 @@ def _x6_weight_image(w, V, K, transposed):
 
 def fc_o_x6_ok(T, rows):
     """the bf16x6 GEMM pays once the product is large (its images are padded to 128 x 192 x 128 tiles)"""
-    return _conv_math["mode"] == "bf16x6" and T >= 512 and rows >= 192 and _FC_O_X6
+    return _conv_math["mode"] == "bf16x6" and T >= 512 and rows >= 192
 
 
 def bn_finalize(part, info, rows, Cn, eps, momentum, running_mean, running_var):
@@ -1209,9 +1169,8 @@ def bn_apply(z, mean, invstd, gamma, beta, residual=None, relu=False):
     return y
 
 
-def bn_bwd(dy, y, z, mean, invstd, gamma, relu, want_dres, dgamma, dbeta, accumulate, beta=None, acc=None, acc_ready=False):
-    """y=None with relu: the ReLU mask is rebuilt from z, gamma and beta (forward without residual only).
-    acc / acc_ready: an accumulator that already holds the backward sums (formed by the data gradient that produced dy)."""
+def bn_bwd(dy, y, z, mean, invstd, gamma, relu, want_dres, dgamma, dbeta, accumulate, beta=None):
+    """y=None with relu: the ReLU mask is rebuilt from z, gamma and beta (forward without residual only)."""
     Cn = z.shape[-1]
     rows = z.numel() // Cn
     dz = torch.empty_like(z)
@@ -1220,10 +1179,10 @@ def bn_bwd(dy, y, z, mean, invstd, gamma, relu, want_dres, dgamma, dbeta, accumu
         raise _C.BuctdHipError("bn_bwd: ReLU backward needs the forward output or beta")
     if bn_acc_ok(Cn):
         # reduction into an integer accumulator, decoded by the apply kernel: two launches, no finalize in between
-        acc = acc if acc is not None else AccRef(Cn, z.device)
+        acc = AccRef(Cn, z.device)
         check(lib().buctd_bn_bwd_acc(ptr(dy), ptr(y) if relu else None, ptr(z), ptr(mean), ptr(invstd), ptr(gamma),
                                      ptr(beta) if (relu and y is None) else None, int(bool(relu)), rows, Cn, ptr(dz), ptr(dres),
-                                     ptr(dgamma), ptr(dbeta), int(accumulate), C.c_void_p(acc.ptr), int(bool(acc_ready)),
+                                     ptr(dgamma), ptr(dbeta), int(accumulate), C.c_void_p(acc.ptr), 0,
                                      stream_ptr()), "bn_bwd_acc")
         return dz, dres
     need = lib().buctd_bn_bwd_workspace(rows, Cn)
@@ -1354,30 +1313,6 @@ def fuse_sum_bwd(dy, y, shift):
     N, H, W, Cn = dy.shape
     g = torch.empty((N, H >> shift, W >> shift, Cn), dtype=torch.float32, device=dy.device)
     check(lib().buctd_fuse_sum_bwd(ptr(dy), ptr(y), shift, N, H, W, Cn, ptr(g), stream_ptr()), "fuse_sum_bwd")
-    return g
-
-
-# (gradient address, z address) -> AccRef holding the BatchNorm-backward sums of that pair, formed by the kernel that wrote the
-# gradient (fuse_sum_bwd_bnstat); ConvBnAct.backward pops its entry.  Emptied at the end of every backward pass (_join_side).
-_bwd_sums = {}
-
-
-def fuse_sum_bwd_bnstat(dy, y, shift, bns):
-    """fuse_sum_bwd + the BatchNorm-backward sums of up to three conv -> BatchNorm terms of this shift (bns: (z, mean, invstd)
-    each) in one pass; the accumulators are left in _bwd_sums for the terms' ConvBnAct.backward."""
-    N, H, W, Cn = dy.shape
-    g = torch.empty((N, H >> shift, W >> shift, Cn), dtype=torch.float32, device=dy.device)
-    n = len(bns)
-    accs = [AccRef(Cn, dy.device) for _ in bns]
-    zs = (C.c_void_p * n)(*[b[0].data_ptr() for b in bns])
-    ms = (C.c_void_p * n)(*[b[1].data_ptr() for b in bns])
-    iv = (C.c_void_p * n)(*[b[2].data_ptr() for b in bns])
-    ac = (C.c_void_p * n)(*[a.ptr for a in accs])
-    check(lib().buctd_fuse_sum_bwd_bnstat(ptr(dy), ptr(y), shift, N, H, W, Cn, ptr(g), n, zs, ms, iv, ac, stream_ptr()),
-          "fuse_sum_bwd_bnstat")
-    for b, a in zip(bns, accs):
-        _bwd_sums[(g.data_ptr(), b[0].data_ptr())] = a
-    _queue_join()       # the registry is emptied with the backward pass
     return g
 
 
@@ -1607,10 +1542,6 @@ class ConvBnAct(torch.autograd.Function):
             ctx.has_res = residual is not None
             # without a residual the ReLU mask is rebuilt from z in the backward kernels: y is not kept (nor re-read)
             ctx.save_for_backward(x, z, mean, invstd, y if (relu and ctx.has_res) else None)
-            if _FUSE_BWD_BNSTAT and info[0] == "acc" and not relu and residual is None and bn_acc_ok(Cn):
-                # a plain conv -> BatchNorm output: a FuseSum consuming it can form this BatchNorm's backward sums while it
-                # writes the gradient (FuseSum.backward); z / mean / invstd are kept alive by this node anyway
-                y._buctd_bn = (z, mean, invstd)
             return y
         scale, shift = bn_fold_cached(bn, gamma, beta, eps)
         if transposed_shape is None:
@@ -1634,9 +1565,7 @@ class ConvBnAct(torch.autograd.Function):
         dgamma, acc_g = grad_target(bn.weight)
         dbeta, acc_b = grad_target(bn.bias)
         assert acc_g == acc_b
-        ready = _bwd_sums.pop((dy.data_ptr(), z.data_ptr()), None) if _bwd_sums else None
-        dz, dres = bn_bwd(dy, y, z, mean, invstd, bn.weight, relu, ctx.has_res and relu, dgamma, dbeta, acc_g,
-                          beta=bn.bias, acc=ready, acc_ready=ready is not None)
+        dz, dres = bn_bwd(dy, y, z, mean, invstd, bn.weight, relu, ctx.has_res and relu, dgamma, dbeta, acc_g, beta=bn.bias)
         if ctx.has_res and not relu:
             dres = dy
         dx = None
@@ -1792,7 +1721,7 @@ class BasicBlockFn(torch.autograd.Function):
         # same way).  Bit-identical to the unfused sequence: the staged value is bn_apply's own expression.
         fuse = bn_in_fusable(tuple(x.shape), w2)
         veto = native_block_veto["fn"]
-        if (fuse and _NATIVE_BLOCK and bn_in_fusable(tuple(x.shape), w1) and bn1.track_running_stats == bn2.track_running_stats
+        if (fuse and bn_in_fusable(tuple(x.shape), w1) and bn1.track_running_stats == bn2.track_running_stats
                 and not (veto is not None and veto(tuple(x.shape)))):
             return BasicBlockFn._forward_native(ctx, x, w1, bn1, w2, bn2)
         z1, part, info = conv_fwd(x, w1, None, 1, 1, stats="acc")
@@ -2082,19 +2011,8 @@ def set_group_parts(n):
     return old
 
 
-_GROUP_PARTITION = {}      # branches -> explicit partition (experiments: ops.set_group_partition)
-
-
-def set_group_partition(nb, parts):
-    """Explicit assignment of the branches of an nb-branch module to group-launch families, e.g. (3, [[0, 1], [2]])."""
-    assert sorted(i for p in parts for i in p) == list(range(nb))
-    _GROUP_PARTITION[nb] = [list(p) for p in parts]
-
-
 def group_branch_partition(nb):
     """Branch indices per group launch family: one group of all branches, or two groups side by side on two streams."""
-    if nb in _GROUP_PARTITION:
-        return _GROUP_PARTITION[nb]
     if _GROUP_PARTS["n"] <= 1 or nb < 3:
         return [list(range(nb))]
     if nb == 3:
@@ -2334,8 +2252,6 @@ class FuseSum(torch.autograd.Function):
         out = fuse_sum(list(terms), list(shifts), relu)
         ctx.shifts, ctx.relu = shifts, relu
         ctx.save_for_backward(out if relu else None)
-        # terms that are plain conv -> BatchNorm outputs (ConvBnAct.forward tags them): (z, mean, invstd) of their BatchNorm
-        ctx.term_bn = tuple(getattr(t, "_buctd_bn", None) for t in terms) if _FUSE_BWD_BNSTAT else None
         return out
 
     @staticmethod
@@ -2349,18 +2265,8 @@ class FuseSum(torch.autograd.Function):
                 grads.append(None)
                 continue
             if s not in cache:
-                if s > 0 or ctx.relu:
-                    bns = []
-                    # s > 0 only: the shift-0 gradient also feeds the identity term - the branch chain, which is the critical
-                    # path of the backward pass - and must not wait for extra passes over the terms' z (measured: -0.8 %)
-                    if ctx.term_bn is not None and (s > 0 or _FUSE_BWD_BNSTAT_S0):
-                        bns = [ctx.term_bn[k] for k, sk in enumerate(ctx.shifts)
-                               if sk == s and ctx.needs_input_grad[2 + k] and ctx.term_bn[k] is not None][:3]
-                    cache[s] = fuse_sum_bwd_bnstat(dy, y, s, bns) if bns else fuse_sum_bwd(dy, y, s)
-                else:
-                    cache[s] = dy
+                cache[s] = fuse_sum_bwd(dy, y, s) if s > 0 or ctx.relu else dy
             grads.append(cache[s])
-        ctx.term_bn = None
         return (None, None, *grads)
 
 
@@ -2609,8 +2515,6 @@ class SmallQKAttention(torch.autograd.Function):
         # contractions over T and C on the bf16 matrix cores: two pieces per operand in the bf16x3 mode, three (fp32
         # class) in the default bf16x6 mode, the exact fp32 MFMA kernels in the fp32 mode
         b3 = {"bf16x3": 1, "bf16x6": 2}.get(_conv_math["mode"], 0)
-        if not _ATTN_X6 and b3 == 2:
-            b3 = 0
         check(lib().buctd_attn_smallqk_fwd(B, T, R4, Cn, ptr(qp), ptr(kp), ptr(v), scale, p_eff, seed, b3, ptr(out), ptr(m),
                                            ptr(linv), stream_ptr()), "attn_smallqk_fwd")
         ctx.meta = (d, R4, scale, p_eff, seed, b3)

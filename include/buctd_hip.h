@@ -149,12 +149,7 @@ typedef struct {
 } buctd_c3_conv_eval;
 int buctd_conv3x3_bf16x6_group_eval(int n, const buctd_c3_conv_eval* convs, void* stream);
 /* Train-mode launches (the option sets of block.hip: statistics accumulator, input BatchNorm from an accumulator, skip
- * gradient, BatchNorm-backward sums) run kernels specialised on the option set (csrc/conv3x3_lean.hip).  Their PERSISTENT
- * form (csrc/conv3x3_pers.hip: a grid of resident workgroups, each walking its share of the tiles as one software pipeline
- * across tile boundaries) is an opt-in: bit-identical results, measured slower than the dispatcher-scheduled launches on
- * HRNet-W48.  on = 1 / 0 switches it, on < 0 only queries; returns the previous setting.  Process-wide; call
- * it before launching from several threads. */
-int buctd_conv3x3_bf16x6_persistent(int on);
+ * gradient, BatchNorm-backward sums) run kernels specialised on the option set (csrc/conv3x3_lean.hip). */
 /* The number of workgroups buctd_conv3x3_bf16x6_group(n, convs) launches as ONE kernel (0: the members share no kernel and go
  * out one launch each; < 0: error).  No launch - for tools that find a launch in a kernel trace by its grid (bench.py). */
 int buctd_conv3x3_bf16x6_group_workgroups(int n, const buctd_c3_conv* convs);
@@ -312,14 +307,6 @@ typedef struct {
   int acc_ready;
 } buctd_bn_bwd_item;
 int buctd_bn_bwd_acc_group(int n, const buctd_bn_bwd_item* items, void* stream);
-/* Backward of a fuse row (lib/models/pose_hrnet.py:257-265, y = relu(sum_j upsample(term_j))) for the terms of one shift,
- * exactly buctd_fuse_sum_bwd (g [N][H>>shift][W>>shift][C] = window sum of dy * (y > 0); y may be NULL), plus the
- * BatchNorm-backward sums of nt <= 3 terms that are conv -> BatchNorm outputs of that resolution: sum(g) and
- * sum(g * (z_t - mean_t) * invstd_t) are added into acc[t] (buctd_bn_acc_bytes(C) each, zero on entry), so that
- * buctd_bn_bwd_acc(..., acc[t], acc_ready = 1) can follow without its reduction launch. */
-int buctd_fuse_sum_bwd_bnstat(const float* dy, const float* y, int shift, int N, int H, int W, int C, float* g, int nt,
-                              const float* const* z, const float* const* mean, const float* const* invstd,
-                              void* const* acc, void* stream);
 /* eval-mode helpers: scale = gamma/sqrt(var+eps), shift = beta - mean*scale */
 int buctd_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                   float eps, int C, float* scale, float* shift, void* stream);

@@ -18,8 +18,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeat-masks", action="store_true")
     ap.add_argument("--streams", default="single")
+    ap.add_argument("--serial", action="store_true", help="the eager engine without its branch and weight-gradient streams")
     args = ap.parse_args()
     from buctd_amd import engine, models, ops
+    if args.serial:
+        ops.set_stream_forks(False, False)
     from buctd_amd.core.loss import JointsMSELoss
     rank, world, device = engine.init_distributed()
     ops.set_conv_math("bf16x6")

@@ -1,9 +1,10 @@
 #!/bin/bash
 # C2: serialised kernel census of the eager engine + kernel trace of the replayed linear graph (kernel time against wall time)
+R=$(cd "$(dirname "$0")/.." && pwd)
 bash scratch/serial_census.sh ser_c2 train_c2 > gpurun_out/ser_c2_head.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/trg
-BUCTD_TUNING=1 BUCTD_BRANCH_STREAMS=0 BUCTD_WGRAD_STREAM=0 timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/trg -o t -- python $GRAFT_REPO_ROOT/scratch/step_graph_probe.py --workload train_c2 --steps 10 > /tmp/trg.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/trg -o t -- python $R/scratch/step_graph_probe.py --serial --workload train_c2 --steps 10 > /tmp/trg.log 2>&1
 cd $GRAFT_REPO_ROOT
 f=$(find /tmp/trg -name "*kernel_trace.csv" | head -1)
 python - $f <<'PY' > gpurun_out/sg_linear_trace.txt 2>&1

@@ -14,7 +14,7 @@ def run(N, H, W, Ci, Co, k, reps=20, check=False):
     w = torch.empty(Co, Ci, k, k, device=dev).contiguous(memory_format=torch.channels_last)
     res = {}
     for on in (True, False):
-        ops._GCONV_WGRAD["on"] = on
+        ops.set_conv_math("bf16x6" if on else "fp32")
         for _ in range(3):
             out = ops.conv_wgrad(x, dy, w, stride, pad)
         torch.cuda.synchronize()
@@ -24,7 +24,7 @@ def run(N, H, W, Ci, Co, k, reps=20, check=False):
             out = ops.conv_wgrad(x, dy, w, stride, pad)
         b.record(); b.synchronize()
         res[on] = (a.elapsed_time(b) / reps * 1e3, out.clone())
-    ops._GCONV_WGRAD["on"] = True
+    ops.set_conv_math("bf16x6")
     msg = f"{k}x{k} {Ci:3d}->{Co:3d} @{H}x{W} N={N}: bf16x6 {res[True][0]:7.1f} us, fp32 MFMA {res[False][0]:7.1f} us"
     if check:
         ref = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2).cpu(), (Co, Ci, k, k), dy.double().permute(0, 3, 1, 2).cpu(),

@@ -184,10 +184,16 @@ SIGNATURES = {
     "buctd_maxpool3x3s2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "buctd_softmax_dropout_fwd": (_I, [_P, _L, _I, _F, _F, _U64, _P, _P, _P]),
     "buctd_softmax_dropout_bwd": (_I, [_P, _P, _L, _I, _F, _F, _U64, _P, _P]),
+    "buctd_softmax_dropout_fwd_dseed": (_I, [_P, _L, _I, _F, _F, _P, _P, _P, _P]),
+    "buctd_softmax_dropout_bwd_dseed": (_I, [_P, _P, _L, _I, _F, _F, _P, _P, _P]),
     "buctd_dropout": (_I, [_P, _P, _L, _F, _U64, _P]),
+    "buctd_dropout_dseed": (_I, [_P, _P, _L, _F, _P, _P]),
+    "buctd_dropout_seed_fill": (_I, [_P, _I, _U64, _U64, _P]),
     "buctd_attn_smallqk_supported": (_I, [_I, _I, _I]),
     "buctd_attn_smallqk_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _F, _F, _U64, _I, _P, _P, _P, _P]),
     "buctd_attn_smallqk_bwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _U64, _I, _P, _P, _P, _P, _P]),
+    "buctd_attn_smallqk_fwd_dseed": (_I, [_I, _I, _I, _I, _P, _P, _P, _F, _F, _P, _I, _P, _P, _P, _P]),
+    "buctd_attn_smallqk_bwd_dseed": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _P, _P, _P, _P, _P]),
     "buctd_layernorm_fwd": (_I, [_P, _P, _P, _L, _I, _F, _P, _P, _P, _P]),
     "buctd_add_layernorm_fwd": (_I, [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P]),
     "buctd_layernorm_bwd_workspace": (_SZ, [_L, _I]),
@@ -215,6 +221,8 @@ SIGNATURES = {
     "buctd_mha_fwd_train": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _U64, _P, _P, _P]),
     "buctd_mha_bwd_workspace": (_SZ, [_I, _I]),
     "buctd_mha_bwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _U64, _P, _P, _I, _P, _I, _P, _SZ, _P]),
+    "buctd_mha_fwd_train_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "buctd_mha_bwd_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
     "buctd_nms_workspace": (_SZ, [_I]),
     "buctd_nms": (_I, [_P, _P, _P, _I, _I, _F, _P, _SZ, _P]),
     "buctd_cpu_nms": (_I, [_P, _I, _P, _F, _P, _P]),

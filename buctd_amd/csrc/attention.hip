@@ -10,9 +10,11 @@
 
 // ------------------------------------------------------ softmax, one block per row ----
 #define SM_NPT 32  // values cached per thread: rows up to 8192 columns stay in registers
+template <bool DSEED>
 __global__ __launch_bounds__(256) void softmax_fwd_block_kernel(const float* __restrict__ s, int L, float scale,
-                                                                float p_drop, uint64_t seed, float* __restrict__ p,
+                                                                float p_drop, SeedArg<DSEED> seed_arg, float* __restrict__ p,
                                                                 float* __restrict__ pd) {
+  const uint64_t seed = load_seed(seed_arg);
   __shared__ float sm[4];
   const long row = blockIdx.x;
   const float* sr = s + row * L;
@@ -47,9 +49,12 @@ __global__ __launch_bounds__(256) void softmax_fwd_block_kernel(const float* __r
   }
 }
 
+template <bool DSEED>
 __global__ __launch_bounds__(256) void softmax_bwd_block_kernel(const float* __restrict__ dpd,
                                                                 const float* __restrict__ p, int L, float scale,
-                                                                float p_drop, uint64_t seed, float* __restrict__ ds) {
+                                                                float p_drop, SeedArg<DSEED> seed_arg,
+                                                                float* __restrict__ ds) {
+  const uint64_t seed = load_seed(seed_arg);
   __shared__ float sm[4];
   const long row = blockIdx.x;
   float g[SM_NPT], pv[SM_NPT];
@@ -77,9 +82,11 @@ __global__ __launch_bounds__(256) void softmax_bwd_block_kernel(const float* __r
 
 // ------------------------------------------------------- softmax, one wave per row ----
 #define SW_NPT 8  // rows up to 512 columns
+template <bool DSEED>
 __global__ __launch_bounds__(256) void softmax_fwd_wave_kernel(const float* __restrict__ s, long rows, int L,
-                                                               float scale, float p_drop, uint64_t seed,
+                                                               float scale, float p_drop, SeedArg<DSEED> seed_arg,
                                                                float* __restrict__ p, float* __restrict__ pd) {
+  const uint64_t seed = load_seed(seed_arg);
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -113,10 +120,12 @@ __global__ __launch_bounds__(256) void softmax_fwd_wave_kernel(const float* __re
     }
   }
 }
+template <bool DSEED>
 __global__ __launch_bounds__(256) void softmax_bwd_wave_kernel(const float* __restrict__ dpd,
                                                                const float* __restrict__ p, long rows, int L,
-                                                               float scale, float p_drop, uint64_t seed,
+                                                               float scale, float p_drop, SeedArg<DSEED> seed_arg,
                                                                float* __restrict__ ds) {
+  const uint64_t seed = load_seed(seed_arg);
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -143,51 +152,94 @@ __global__ __launch_bounds__(256) void softmax_bwd_wave_kernel(const float* __re
   }
 }
 
-extern "C" int buctd_softmax_dropout_fwd(const float* s, long rows, int L, float scale, float p_drop, uint64_t seed,
-                                         float* p, float* pd, void* stream) {
-  BUCTD_CHECK_ARG(s && p && pd && rows > 0 && L > 0, "buctd_softmax_dropout_fwd: bad argument");
-  BUCTD_CHECK_ARG(L <= 256 * SM_NPT, "buctd_softmax_dropout_fwd: row length %d > %d unsupported", L, 256 * SM_NPT);
-  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "buctd_softmax_dropout_fwd: p_drop out of range");
-  BUCTD_CHECK_ARG(p_drop == 0.f || p != pd, "buctd_softmax_dropout_fwd: p and pd must differ when dropping");
+template <bool DSEED>
+static int softmax_dropout_fwd(const char* who, const float* s, long rows, int L, float scale, float p_drop,
+                               SeedArg<DSEED> seed, float* p, float* pd, void* stream) {
+  BUCTD_CHECK_ARG(s && p && pd && rows > 0 && L > 0 && seed_ok(seed), "%s: bad argument", who);
+  BUCTD_CHECK_ARG(L <= 256 * SM_NPT, "%s: row length %d > %d unsupported", who, L, 256 * SM_NPT);
+  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop out of range", who);
+  BUCTD_CHECK_ARG(p_drop == 0.f || p != pd, "%s: p and pd must differ when dropping", who);
   hipStream_t st = (hipStream_t)stream;
   if (L <= 64 * SW_NPT)
-    hipLaunchKernelGGL(softmax_fwd_wave_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, s, rows, L, scale, p_drop,
+    hipLaunchKernelGGL(softmax_fwd_wave_kernel<DSEED>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, s, rows, L, scale, p_drop,
                        seed, p, pd);
   else
-    hipLaunchKernelGGL(softmax_fwd_block_kernel, dim3((unsigned)rows), dim3(256), 0, st, s, L, scale, p_drop, seed, p,
-                       pd);
-  BUCTD_CHECK_LAUNCH("buctd_softmax_dropout_fwd");
+    hipLaunchKernelGGL(softmax_fwd_block_kernel<DSEED>, dim3((unsigned)rows), dim3(256), 0, st, s, L, scale, p_drop, seed,
+                       p, pd);
+  BUCTD_CHECK_LAUNCH(who);
   return BUCTD_OK;
+}
+template <bool DSEED>
+static int softmax_dropout_bwd(const char* who, const float* dpd, const float* p, long rows, int L, float scale,
+                               float p_drop, SeedArg<DSEED> seed, float* ds, void* stream) {
+  BUCTD_CHECK_ARG(dpd && p && ds && rows > 0 && L > 0 && seed_ok(seed), "%s: bad argument", who);
+  BUCTD_CHECK_ARG(L <= 256 * SM_NPT, "%s: row length %d > %d unsupported", who, L, 256 * SM_NPT);
+  hipStream_t st = (hipStream_t)stream;
+  if (L <= 64 * SW_NPT)
+    hipLaunchKernelGGL(softmax_bwd_wave_kernel<DSEED>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, dpd, p, rows, L, scale,
+                       p_drop, seed, ds);
+  else
+    hipLaunchKernelGGL(softmax_bwd_block_kernel<DSEED>, dim3((unsigned)rows), dim3(256), 0, st, dpd, p, L, scale, p_drop,
+                       seed, ds);
+  BUCTD_CHECK_LAUNCH(who);
+  return BUCTD_OK;
+}
+extern "C" int buctd_softmax_dropout_fwd(const float* s, long rows, int L, float scale, float p_drop, uint64_t seed,
+                                         float* p, float* pd, void* stream) {
+  return softmax_dropout_fwd<false>("buctd_softmax_dropout_fwd", s, rows, L, scale, p_drop, seed, p, pd, stream);
+}
+extern "C" int buctd_softmax_dropout_fwd_dseed(const float* s, long rows, int L, float scale, float p_drop,
+                                               const uint64_t* seed, float* p, float* pd, void* stream) {
+  return softmax_dropout_fwd<true>("buctd_softmax_dropout_fwd_dseed", s, rows, L, scale, p_drop, seed, p, pd, stream);
 }
 extern "C" int buctd_softmax_dropout_bwd(const float* dpd, const float* p, long rows, int L, float scale,
                                          float p_drop, uint64_t seed, float* ds, void* stream) {
-  BUCTD_CHECK_ARG(dpd && p && ds && rows > 0 && L > 0, "buctd_softmax_dropout_bwd: bad argument");
-  BUCTD_CHECK_ARG(L <= 256 * SM_NPT, "buctd_softmax_dropout_bwd: row length %d > %d unsupported", L, 256 * SM_NPT);
-  hipStream_t st = (hipStream_t)stream;
-  if (L <= 64 * SW_NPT)
-    hipLaunchKernelGGL(softmax_bwd_wave_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, dpd, p, rows, L, scale,
-                       p_drop, seed, ds);
-  else
-    hipLaunchKernelGGL(softmax_bwd_block_kernel, dim3((unsigned)rows), dim3(256), 0, st, dpd, p, L, scale, p_drop, seed,
-                       ds);
-  BUCTD_CHECK_LAUNCH("buctd_softmax_dropout_bwd");
-  return BUCTD_OK;
+  return softmax_dropout_bwd<false>("buctd_softmax_dropout_bwd", dpd, p, rows, L, scale, p_drop, seed, ds, stream);
+}
+extern "C" int buctd_softmax_dropout_bwd_dseed(const float* dpd, const float* p, long rows, int L, float scale,
+                                               float p_drop, const uint64_t* seed, float* ds, void* stream) {
+  return softmax_dropout_bwd<true>("buctd_softmax_dropout_bwd_dseed", dpd, p, rows, L, scale, p_drop, seed, ds, stream);
 }
 
 // ------------------------------------------------------------------- dropout ----
+template <bool DSEED>
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n,
-                                                      float p_drop, uint64_t seed) {
+                                                      float p_drop, SeedArg<DSEED> seed_arg) {
+  const uint64_t seed = load_seed(seed_arg);
   const float inv_keep = 1.f / (1.f - p_drop);
   const long step = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step)
     y[i] = x[i] * keep_scale(seed, (uint64_t)i, p_drop, inv_keep);
 }
-extern "C" int buctd_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed, void* stream) {
-  BUCTD_CHECK_ARG(x && y && n > 0 && p_drop >= 0.f && p_drop < 1.f, "buctd_dropout: bad argument");
+template <bool DSEED>
+static int dropout(const char* who, const float* x, float* y, long n, float p_drop, SeedArg<DSEED> seed, void* stream) {
+  BUCTD_CHECK_ARG(x && y && n > 0 && p_drop >= 0.f && p_drop < 1.f && seed_ok(seed), "%s: bad argument", who);
   long b = (n + 255) / 256;
   if (b > 4096) b = 4096;
-  hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, x, y, n, p_drop, seed);
-  BUCTD_CHECK_LAUNCH("buctd_dropout");
+  hipLaunchKernelGGL(dropout_kernel<DSEED>, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, x, y, n, p_drop, seed);
+  BUCTD_CHECK_LAUNCH(who);
+  return BUCTD_OK;
+}
+extern "C" int buctd_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed, void* stream) {
+  return dropout<false>("buctd_dropout", x, y, n, p_drop, seed, stream);
+}
+extern "C" int buctd_dropout_dseed(const float* x, float* y, long n, float p_drop, const uint64_t* seed, void* stream) {
+  return dropout<true>("buctd_dropout_dseed", x, y, n, p_drop, seed, stream);
+}
+
+// The device form of ops.next_seed(): table[i] = the seed of the (i + 1)-th draw after draw number counter0 of the stream
+// keyed by `base`.  A replayed step graph reads its seeds from this table; the fill runs in front of each replay.
+__global__ __launch_bounds__(256) void dropout_seed_fill_kernel(uint64_t* __restrict__ table, int n, uint64_t base,
+                                                                uint64_t counter0) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) table[i] = base * 0x9E3779B97F4A7C15ull + (counter0 + (uint64_t)i + 1) * 0xD1B54A32D192ED03ull;
+}
+extern "C" int buctd_dropout_seed_fill(uint64_t* table, int n, uint64_t base, uint64_t counter0, void* stream) {
+  BUCTD_CHECK_ARG(table && n >= 0, "buctd_dropout_seed_fill: bad argument");
+  if (n == 0) return BUCTD_OK;
+  hipLaunchKernelGGL(dropout_seed_fill_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, table, n, base,
+                     counter0);
+  BUCTD_CHECK_LAUNCH("buctd_dropout_seed_fill");
   return BUCTD_OK;
 }
 

@@ -29,11 +29,12 @@
 // ---------------------------------------------------------------------------------------------------------- forward ----
 // mha_fwd_kernel of attn_mha.hip plus attention dropout on the probabilities that enter P V (the soft-max normaliser uses
 // the undropped ones) and the log-sum-exp row statistic for the backward.
-template <int DF>
+template <int DF, bool DSEED>
 __global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                const float* __restrict__ v, int T, int ldqk, int ldv,
-                                                               float scale, float p_drop, uint64_t seed,
+                                                               float scale, float p_drop, SeedArg<DSEED> seed_arg,
                                                                float* __restrict__ out, float* __restrict__ lse) {
+  const uint64_t seed = load_seed(seed_arg);
   constexpr int D = DF * 16, LDK = D + 8, LDV = MT_BS + 8, LDP = MT_BS + 8;
   constexpr int C4 = D / 4;
   constexpr int PL = (MT_BS * C4 + 511) / 512;
@@ -188,8 +189,17 @@ struct MhaBwdArgs {
   uint64_t seed;
 };
 
-template <int DF, bool DKV>
-__global__ __launch_bounds__(512, 1) void mha_bwd_kernel(MhaBwdArgs p) {
+// the _dseed launch: the arguments plus a device pointer to the seed (p.seed of the value form)
+__device__ __forceinline__ const MhaBwdArgs& with_seed(const MhaBwdArgs& a) { return a; }
+__device__ __forceinline__ MhaBwdArgs with_seed(const DevSeeded<MhaBwdArgs>& d) {
+  MhaBwdArgs a = d.a;
+  a.seed = *d.seedp;
+  return a;
+}
+
+template <int DF, bool DKV, bool DSEED>
+__global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, DSEED> args) {
+  const MhaBwdArgs& p = with_seed(args);
   constexpr int D = DF * 16, LDK = D + 8;
   constexpr int C4 = D / 4;
   constexpr int PL = (MT_BS * C4 + 511) / 512;
@@ -354,58 +364,53 @@ static int mt_attr(F fn, unsigned char (&done)[BUCTD_MAX_DEVICES], const char* w
   return buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, done, who);
 }
 
-template <int DF>
+template <int DF, bool DSEED>
 static int mt_fwd_launch(int B, int T, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                         float p_drop, uint64_t seed, float* out, float* lse, hipStream_t st) {
+                         float p_drop, SeedArg<DSEED> seed, float* out, float* lse, hipStream_t st) {
   static unsigned char done[BUCTD_MAX_DEVICES] = {0};
-  const int rc = mt_attr(mha_fwd_train_kernel<DF>, done, "buctd_mha_fwd_train");
+  const int rc = mt_attr(mha_fwd_train_kernel<DF, DSEED>, done, "buctd_mha_fwd_train");
   if (rc) return rc;
-  hipLaunchKernelGGL(mha_fwd_train_kernel<DF>, dim3(T / MT_BO, B), dim3(512), mt_fwd_lds(DF * 16), st, q, k, v, T, ldqk, ldv,
-                     scale, p_drop, seed, out, lse);
+  hipLaunchKernelGGL((mha_fwd_train_kernel<DF, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_fwd_lds(DF * 16), st, q, k, v, T,
+                     ldqk, ldv, scale, p_drop, seed, out, lse);
   BUCTD_CHECK_LAUNCH("buctd_mha_fwd_train");
   return BUCTD_OK;
 }
 
-template <int DF>
-static int mt_bwd_launch(int B, const MhaBwdArgs& a, hipStream_t st) {
+template <int DF, bool DSEED>
+static int mt_bwd_launch(int B, int T, const SeededArgs<MhaBwdArgs, DSEED>& a, hipStream_t st) {
   static unsigned char done[2][BUCTD_MAX_DEVICES] = {{0}};
-  int rc = mt_attr(mha_bwd_kernel<DF, false>, done[0], "buctd_mha_bwd");
+  int rc = mt_attr(mha_bwd_kernel<DF, false, DSEED>, done[0], "buctd_mha_bwd");
   if (rc) return rc;
-  rc = mt_attr(mha_bwd_kernel<DF, true>, done[1], "buctd_mha_bwd");
+  rc = mt_attr(mha_bwd_kernel<DF, true, DSEED>, done[1], "buctd_mha_bwd");
   if (rc) return rc;
-  hipLaunchKernelGGL((mha_bwd_kernel<DF, true>), dim3(a.T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
+  hipLaunchKernelGGL((mha_bwd_kernel<DF, true, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dK, dV)");
-  hipLaunchKernelGGL((mha_bwd_kernel<DF, false>), dim3(a.T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
+  hipLaunchKernelGGL((mha_bwd_kernel<DF, false, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dQ)");
   return BUCTD_OK;
 }
 
-/* softmax(scale q k^T) -> dropout(p_drop, seed) -> . v for one head, fused (no T x T tensor), train mode: also writes the
- * row statistic lse[B][T] the backward needs.  q, k: rows of stride ldqk floats, v: ldv; out: [B][T][d] contiguous.
- * Reference: nn.MultiheadAttention in transpose_h.py:192-197 (forward of the training step). */
-extern "C" int buctd_mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                                   float scale, float p_drop, uint64_t seed, float* out, float* lse, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && lse && B > 0, "buctd_mha_fwd_train: null pointer");
+template <bool DSEED>
+static int mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
+                         float p_drop, SeedArg<DSEED> seed, float* out, float* lse, void* stream) {
+  BUCTD_CHECK_ARG(q && k && v && out && lse && B > 0 && seed_ok(seed), "buctd_mha_fwd_train: null pointer");
   BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "buctd_mha_fwd_train: unsupported shape T%d d%d", T, d);
   BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && ldqk % 4 == 0 && ldv % 4 == 0 && p_drop >= 0.f && p_drop < 1.f,
                   "buctd_mha_fwd_train: bad strides or dropout probability");
   hipStream_t st = (hipStream_t)stream;
   switch (d / 16) {
-#define MT_CASE(n) case n: return mt_fwd_launch<n>(B, T, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, st);
+#define MT_CASE(n) case n: return mt_fwd_launch<n, DSEED>(B, T, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, st);
     MT_CASE(1) MT_CASE(2) MT_CASE(3) MT_CASE(4) MT_CASE(5) MT_CASE(6) MT_CASE(7) MT_CASE(8)
 #undef MT_CASE
   }
   return BUCTD_EINVAL;
 }
 
-/* backward of buctd_mha_fwd_train: dq, dk (rows of stride lddqk), dv (stride lddv) from q, k, v, the forward's out and lse,
- * and dout [B][T][d].  workspace: B * T floats (the row dots dout . out). */
-extern "C" size_t buctd_mha_bwd_workspace(int B, int T) { return (size_t)B * T * sizeof(float); }
-extern "C" int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                             const float* out, const float* dout, const float* lse, float scale, float p_drop, uint64_t seed,
-                             float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && B > 0, "buctd_mha_bwd: null pointer");
+template <bool DSEED>
+static int mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
+                   const float* dout, const float* lse, float scale, float p_drop, SeedArg<DSEED> seed, float* dq, float* dk,
+                   int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream) {
+  BUCTD_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && B > 0 && seed_ok(seed), "buctd_mha_bwd: null pointer");
   BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "buctd_mha_bwd: unsupported shape T%d d%d", T, d);
   BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && lddqk >= d && lddv >= d && ldqk % 4 == 0 && ldv % 4 == 0,
                   "buctd_mha_bwd: bad strides");
@@ -417,15 +422,53 @@ extern "C" int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k
   const long rows = (long)B * T;
   hipLaunchKernelGGL(mha_rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, dout, out, rows, d, (float*)workspace);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (row dots)");
-  MhaBwdArgs a;
+  SeededArgs<MhaBwdArgs, DSEED> args;
+  MhaBwdArgs& a = kernel_args(args);
   a.q = q; a.k = k; a.v = v; a.dout = dout; a.lse = lse; a.dvec = (const float*)workspace;
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.T = T; a.ldqk = ldqk; a.ldv = ldv; a.lddqk = lddqk; a.lddv = lddv;
-  a.scale = scale; a.p_drop = p_drop; a.seed = seed;
+  a.scale = scale; a.p_drop = p_drop;
+  if constexpr (DSEED) {
+    a.seed = 0;
+    args.seedp = seed;
+  } else {
+    a.seed = seed;
+  }
   switch (d / 16) {
-#define MT_CASE(n) case n: return mt_bwd_launch<n>(B, a, st);
+#define MT_CASE(n) case n: return mt_bwd_launch<n, DSEED>(B, T, args, st);
     MT_CASE(1) MT_CASE(2) MT_CASE(3) MT_CASE(4) MT_CASE(5) MT_CASE(6) MT_CASE(7) MT_CASE(8)
 #undef MT_CASE
   }
   return BUCTD_EINVAL;
+}
+
+/* softmax(scale q k^T) -> dropout(p_drop, seed) -> . v for one head, fused (no T x T tensor), train mode: also writes the
+ * row statistic lse[B][T] the backward needs.  q, k: rows of stride ldqk floats, v: ldv; out: [B][T][d] contiguous.
+ * Reference: nn.MultiheadAttention in transpose_h.py:192-197 (forward of the training step). */
+extern "C" int buctd_mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
+                                   float scale, float p_drop, uint64_t seed, float* out, float* lse, void* stream) {
+  return mha_fwd_train<false>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
+}
+extern "C" int buctd_mha_fwd_train_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
+                                         int ldv, float scale, float p_drop, const uint64_t* seed, float* out, float* lse,
+                                         void* stream) {
+  return mha_fwd_train<true>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
+}
+
+/* backward of buctd_mha_fwd_train: dq, dk (rows of stride lddqk), dv (stride lddv) from q, k, v, the forward's out and lse,
+ * and dout [B][T][d].  workspace: B * T floats (the row dots dout . out). */
+extern "C" size_t buctd_mha_bwd_workspace(int B, int T) { return (size_t)B * T * sizeof(float); }
+extern "C" int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
+                             const float* out, const float* dout, const float* lse, float scale, float p_drop, uint64_t seed,
+                             float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  return mha_bwd<false>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
+                        workspace_bytes, stream);
+}
+extern "C" int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
+                                   const float* out, const float* dout, const float* lse, float scale, float p_drop,
+                                   const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return mha_bwd<true>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
+                       workspace_bytes, stream);
 }

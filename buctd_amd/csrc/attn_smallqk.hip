@@ -53,6 +53,15 @@ struct AttnArgs {
   uint32_t s0, s1, thr;
 };
 
+// the _dseed launch: the arguments plus a device pointer to the seed, split into (s0, s1) as attn_args() splits a value
+__device__ __forceinline__ const AttnArgs& with_seed(const AttnArgs& a) { return a; }
+__device__ __forceinline__ AttnArgs with_seed(const DevSeeded<AttnArgs>& d) {
+  AttnArgs a = d.a;
+  const uint64_t seed = *d.seedp;
+  a.s0 = (uint32_t)seed; a.s1 = (uint32_t)(seed >> 32);
+  return a;
+}
+
 template <int R4>
 __device__ __forceinline__ float dotr(const float (&a)[R4], const float* b) {
   float s = a[0] * b[0];     // explicit FMAs: the file is compiled with -ffp-contract=off
@@ -107,8 +116,9 @@ __global__ __launch_bounds__(256) void attn_stats_kernel(AttnArgs p) {
 
 // --------------------------------------------------------------------------------------------- fwd ----
 // workgroup = 64 query rows (16 per wave); key blocks of 64
-template <int R4, int CF, bool DROP>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   // B-operand reads touch rows 4s+kq at columns nf*16 + i16: conflict-free when the row stride is 16 mod 64 floats
   constexpr int C = CF * 16, LDV = C + (80 - C % 64) % 64;
   __shared__ __attribute__((aligned(16))) float ks[64 * R4];
@@ -244,8 +254,9 @@ struct SplitRow {
 // the key-major bf16 tile through the transpose read.  The soft-max statistics are computed on the fly (running row
 // maximum, accumulators rescaled when it moves - rare after the first tiles), so the separate statistics pass of the
 // fp32 path is gone; m and 1/l are written at the end for the backward kernels.
-template <int R4, int CF, bool DROP, int NP>
-__global__ __launch_bounds__(256) void attn_fwd_b3_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, int NP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_fwd_b3_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   constexpr int C = CF * 16, LO = SplitRow<C, NP>::LO, RS = SplitRow<C, NP>::RS;   // V rows: NP pieces of C bf16 | pad
   __shared__ __attribute__((aligned(16))) float ks[64 * R4];
   __shared__ __attribute__((aligned(16))) unsigned char vt[64 * RS];
@@ -364,8 +375,9 @@ __device__ __forceinline__ void load_split8(const float* row, int c0, int C, bf1
 
 // dq' pass: dP = dO V^T with the channel contraction on the bf16 MFMA (dO fragments live in registers for the whole
 // kernel, V rows come out of the bf16 tile with plain 16-byte reads); everything else as attn_bwd_q_kernel.
-template <int R4, int CF, bool DROP, int NP>
-__global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, int NP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   constexpr int C = CF * 16, CS = C / 4, LO = SplitRow<C, NP>::LO, RS = SplitRow<C, NP>::RS, NK = (C + 31) / 32;
   __shared__ __attribute__((aligned(16))) float ks[64 * R4];
   __shared__ __attribute__((aligned(16))) unsigned char vt[64 * RS];
@@ -483,8 +495,9 @@ __global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(AttnArgs p) {
 // eight dropped probabilities of its key - the A operand of ONE K = 32 MFMA of dV += Pd^T dO when the reduction slot
 // e of lane group g is enumerated as query 16 (e >> 2) + 4 g + (e & 3); the dO fragments in that enumeration come
 // out of the query-major bf16 tile through two transpose reads.
-template <int R4, int CF, bool DROP, int NP>
-__global__ __launch_bounds__(256) void attn_bwd_kv_b3_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, int NP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_bwd_kv_b3_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   constexpr int C = CF * 16, LO = SplitRow<C, NP>::LO, RS = SplitRow<C, NP>::RS, NK = (C + 31) / 32;
   __shared__ __attribute__((aligned(16))) float qs[64 * R4];
   __shared__ __attribute__((aligned(16))) unsigned char dt[64 * RS];     // dO tile: [query][hi C | lo C]
@@ -608,8 +621,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_b3_kernel(AttnArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------- bwd_q ----
-template <int R4, int CF, bool DROP>
-__global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_bwd_q_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   constexpr int C = CF * 16, CS = C / 4, LDV = C + 8;  // b128 row reads: stride 32 mod 64 bytes
   __shared__ __attribute__((aligned(16))) float ks[64 * R4];
   __shared__ __attribute__((aligned(16))) float vs[64 * LDV];
@@ -704,8 +718,9 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnArgs p) {
 //   i = 4 kq + reg, which is exactly the A-operand layout of Pd^T for  dV += Pd^T dO  when the reduction index of that
 //   MFMA is enumerated as i = 4 kq + s (legal: A and B use the same permutation).  So P, the dropout hash and dS are
 //   computed ONCE per element and feed both the dk' accumulation (lane-local) and the dV MFMA.
-template <int R4, int CF, bool DROP>
-__global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnArgs p) {
+template <int R4, int CF, bool DROP, bool DSEED>
+__global__ __launch_bounds__(256) void attn_bwd_kv_kernel(SeededArgs<AttnArgs, DSEED> args) {
+  const AttnArgs& p = with_seed(args);
   constexpr int C = CF * 16, CS = C / 4, LDV = C + 8;  // b128 row reads: stride 32 mod 64 bytes
   __shared__ __attribute__((aligned(16))) float qs[64 * R4];
   __shared__ __attribute__((aligned(16))) float dos[64 * LDV];
@@ -807,52 +822,55 @@ static bool attn_shape_ok(int T, int R4, int C) {
 
 extern "C" int buctd_attn_smallqk_supported(int T, int R4, int C) { return attn_shape_ok(T, R4, C) ? 1 : 0; }
 
-template <int R4, int CF>
-static void attn_launch(int which, const AttnArgs& a, int B, hipStream_t st) {
+template <int R4, int CF, bool DSEED>
+static void attn_launch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
+  const AttnArgs& a = kernel_args(ka);     // without dropout the seed is not read: the value kernels run
   const dim3 grid(a.T / 64, B);
   const bool drop = a.p_drop > 0.f;
 #define ATTN_SPLIT(kern)                                                                                         \
   do {                                                                                                           \
     if (a.b3 == 3) {                                                                                             \
-      if (drop) hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, true, 3>), grid, dim3(256), 0, st, a);            \
-      else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 3>), grid, dim3(256), 0, st, a);                \
+      if (drop) hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, true, 3, DSEED>), grid, dim3(256), 0, st, ka);    \
+      else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 3, false>), grid, dim3(256), 0, st, a);         \
     } else {                                                                                                     \
-      if (drop) hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, true, 2>), grid, dim3(256), 0, st, a);            \
-      else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 2>), grid, dim3(256), 0, st, a);                \
+      if (drop) hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, true, 2, DSEED>), grid, dim3(256), 0, st, ka);    \
+      else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 2, false>), grid, dim3(256), 0, st, a);         \
     }                                                                                                            \
   } while (0)
   if (which == 1 && a.b3 && R4 <= 8) {
     ATTN_SPLIT(attn_fwd_b3_kernel);
   } else if (which == 1) {
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, false>), grid, dim3(256), 0, st, a);
+    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, true, DSEED>), grid, dim3(256), 0, st, ka);
+    else hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, false, false>), grid, dim3(256), 0, st, a);
   } else if (which == 2 && a.b3 && R4 <= 8) {
     ATTN_SPLIT(attn_bwd_q_b3_kernel);
   } else if (which == 3 && a.b3 && R4 <= 8) {
     ATTN_SPLIT(attn_bwd_kv_b3_kernel);
 #undef ATTN_SPLIT
   } else if (which == 2) {
-    if (drop) hipLaunchKernelGGL((attn_bwd_q_kernel<R4, CF, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_q_kernel<R4, CF, false>), grid, dim3(256), 0, st, a);
+    if (drop) hipLaunchKernelGGL((attn_bwd_q_kernel<R4, CF, true, DSEED>), grid, dim3(256), 0, st, ka);
+    else hipLaunchKernelGGL((attn_bwd_q_kernel<R4, CF, false, false>), grid, dim3(256), 0, st, a);
   } else {
-    if (drop) hipLaunchKernelGGL((attn_bwd_kv_kernel<R4, CF, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_bwd_kv_kernel<R4, CF, false>), grid, dim3(256), 0, st, a);
+    if (drop) hipLaunchKernelGGL((attn_bwd_kv_kernel<R4, CF, true, DSEED>), grid, dim3(256), 0, st, ka);
+    else hipLaunchKernelGGL((attn_bwd_kv_kernel<R4, CF, false, false>), grid, dim3(256), 0, st, a);
   }
 }
-template <int R4>
-static void attn_dispatch_c(int which, const AttnArgs& a, int B, hipStream_t st) {
-  switch (a.C) {
-    case 16: attn_launch<R4, 1>(which, a, B, st); break;
-    case 32: attn_launch<R4, 2>(which, a, B, st); break;
-    case 48: attn_launch<R4, 3>(which, a, B, st); break;
-    case 64: attn_launch<R4, 4>(which, a, B, st); break;
-    case 96: attn_launch<R4, 6>(which, a, B, st); break;
-    case 128: attn_launch<R4, 8>(which, a, B, st); break;
-    default: attn_launch<R4, 12>(which, a, B, st); break;
+template <int R4, bool DSEED>
+static void attn_dispatch_c(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
+  switch (kernel_args(ka).C) {
+    case 16: attn_launch<R4, 1, DSEED>(which, ka, B, st); break;
+    case 32: attn_launch<R4, 2, DSEED>(which, ka, B, st); break;
+    case 48: attn_launch<R4, 3, DSEED>(which, ka, B, st); break;
+    case 64: attn_launch<R4, 4, DSEED>(which, ka, B, st); break;
+    case 96: attn_launch<R4, 6, DSEED>(which, ka, B, st); break;
+    case 128: attn_launch<R4, 8, DSEED>(which, ka, B, st); break;
+    default: attn_launch<R4, 12, DSEED>(which, ka, B, st); break;
   }
 }
-static void attn_dispatch(int which, const AttnArgs& a, int R4, int B, hipStream_t st) {
+template <bool DSEED>
+static void attn_dispatch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int R4, int B, hipStream_t st) {
   if (which == 0) {
+    const AttnArgs& a = kernel_args(ka);
     const dim3 grid(ceil_div(a.T, 256), B);
     if (R4 == 4) hipLaunchKernelGGL((attn_stats_kernel<4>), grid, dim3(256), 0, st, a);
     else if (R4 == 8) hipLaunchKernelGGL((attn_stats_kernel<8>), grid, dim3(256), 0, st, a);
@@ -860,10 +878,10 @@ static void attn_dispatch(int which, const AttnArgs& a, int R4, int B, hipStream
     else hipLaunchKernelGGL((attn_stats_kernel<20>), grid, dim3(256), 0, st, a);
     return;
   }
-  if (R4 == 4) attn_dispatch_c<4>(which, a, B, st);
-  else if (R4 == 8) attn_dispatch_c<8>(which, a, B, st);
-  else if (R4 == 16) attn_dispatch_c<16>(which, a, B, st);
-  else attn_dispatch_c<20>(which, a, B, st);
+  if (R4 == 4) attn_dispatch_c<4, DSEED>(which, ka, B, st);
+  else if (R4 == 8) attn_dispatch_c<8, DSEED>(which, ka, B, st);
+  else if (R4 == 16) attn_dispatch_c<16, DSEED>(which, ka, B, st);
+  else attn_dispatch_c<20, DSEED>(which, ka, B, st);
 }
 
 // flag of the C ABI -> pieces per operand: 0 fp32 MFMA kernels, 1 -> two bf16 pieces, 2 -> three (bf16x6; its 192-channel
@@ -880,39 +898,75 @@ static AttnArgs attn_args(int T, int C, float scale, float p_drop, uint64_t seed
   a.thr = th >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)th;
   return a;
 }
+// the _dseed form: (s0, s1) stay zero here, the kernels split *seedp
+static DevSeeded<AttnArgs> attn_args(int T, int C, float scale, float p_drop, const uint64_t* seedp) {
+  return DevSeeded<AttnArgs>{attn_args(T, C, scale, p_drop, (uint64_t)0), seedp};
+}
+
+template <bool DSEED>
+static int attn_smallqk_fwd(const char* who, int B, int T, int R4, int C, const float* q, const float* k, const float* v,
+                            float scale, float p_drop, SeedArg<DSEED> seed, int bf16x3, float* out, float* m, float* linv,
+                            void* stream) {
+  BUCTD_CHECK_ARG(q && k && v && out && m && linv && B > 0 && seed_ok(seed), "%s: null argument", who);
+  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "%s: unsupported T=%d R4=%d C=%d", who, T, R4, C);
+  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f && (long)B * T < 2147483647L, "%s: bad p_drop / size", who);
+  SeededArgs<AttnArgs, DSEED> ka = attn_args(T, C, scale, p_drop, seed);
+  AttnArgs& a = kernel_args(ka);
+  a.q = q; a.k = k; a.v = v; a.m = m; a.linv = linv; a.out = out; a.b3 = attn_split_mode(bf16x3, C);
+  if (!(a.b3 && R4 <= 8)) {            // the bf16x3 forward kernel computes the soft-max statistics on the fly
+    attn_dispatch<DSEED>(0, ka, R4, B, (hipStream_t)stream);
+    BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_fwd(stats)");
+  }
+  attn_dispatch<DSEED>(1, ka, R4, B, (hipStream_t)stream);
+  BUCTD_CHECK_LAUNCH(who);
+  return BUCTD_OK;
+}
+
+template <bool DSEED>
+static int attn_smallqk_bwd(const char* who, int B, int T, int R4, int C, const float* q, const float* k, const float* v,
+                            const float* o, const float* dout, const float* m, const float* linv, float scale, float p_drop,
+                            SeedArg<DSEED> seed, int bf16x3, float* dq, float* dk, float* dv, float* dvec_workspace,
+                            void* stream) {
+  BUCTD_CHECK_ARG(q && k && v && o && dout && m && linv && dq && dk && dv && dvec_workspace && B > 0 && seed_ok(seed),
+                  "%s: null argument", who);
+  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "%s: unsupported T=%d R4=%d C=%d", who, T, R4, C);
+  SeededArgs<AttnArgs, DSEED> ka = attn_args(T, C, scale, p_drop, seed);
+  AttnArgs& a = kernel_args(ka);
+  a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout;
+  a.m = const_cast<float*>(m); a.linv = const_cast<float*>(linv); a.dvec = dvec_workspace; a.b3 = attn_split_mode(bf16x3, C);
+  a.out = dq;
+  attn_dispatch<DSEED>(2, ka, R4, B, (hipStream_t)stream);
+  BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(q)");
+  a.out = dk; a.out2 = dv;
+  attn_dispatch<DSEED>(3, ka, R4, B, (hipStream_t)stream);
+  BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(kv)");
+  return BUCTD_OK;
+}
 
 extern "C" int buctd_attn_smallqk_fwd(int B, int T, int R4, int C, const float* q, const float* k, const float* v,
                                       float scale, float p_drop, uint64_t seed, int bf16x3, float* out, float* m,
                                       float* linv, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && m && linv && B > 0, "buctd_attn_smallqk_fwd: null argument");
-  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "buctd_attn_smallqk_fwd: unsupported T=%d R4=%d C=%d", T, R4, C);
-  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f && (long)B * T < 2147483647L, "buctd_attn_smallqk_fwd: bad p_drop / size");
-  AttnArgs a = attn_args(T, C, scale, p_drop, seed);
-  a.q = q; a.k = k; a.v = v; a.m = m; a.linv = linv; a.out = out; a.b3 = attn_split_mode(bf16x3, C);
-  if (!(a.b3 && R4 <= 8)) {            // the bf16x3 forward kernel computes the soft-max statistics on the fly
-    attn_dispatch(0, a, R4, B, (hipStream_t)stream);
-    BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_fwd(stats)");
-  }
-  attn_dispatch(1, a, R4, B, (hipStream_t)stream);
-  BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_fwd");
-  return BUCTD_OK;
+  return attn_smallqk_fwd<false>("buctd_attn_smallqk_fwd", B, T, R4, C, q, k, v, scale, p_drop, seed, bf16x3, out, m, linv,
+                                 stream);
+}
+extern "C" int buctd_attn_smallqk_fwd_dseed(int B, int T, int R4, int C, const float* q, const float* k, const float* v,
+                                            float scale, float p_drop, const uint64_t* seed, int bf16x3, float* out,
+                                            float* m, float* linv, void* stream) {
+  return attn_smallqk_fwd<true>("buctd_attn_smallqk_fwd_dseed", B, T, R4, C, q, k, v, scale, p_drop, seed, bf16x3, out, m,
+                                linv, stream);
 }
 
 extern "C" int buctd_attn_smallqk_bwd(int B, int T, int R4, int C, const float* q, const float* k, const float* v,
                                       const float* o, const float* dout, const float* m, const float* linv,
                                       float scale, float p_drop, uint64_t seed, int bf16x3, float* dq, float* dk,
                                       float* dv, float* dvec_workspace, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && o && dout && m && linv && dq && dk && dv && dvec_workspace && B > 0,
-                  "buctd_attn_smallqk_bwd: null argument");
-  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "buctd_attn_smallqk_bwd: unsupported T=%d R4=%d C=%d", T, R4, C);
-  AttnArgs a = attn_args(T, C, scale, p_drop, seed);
-  a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout;
-  a.m = const_cast<float*>(m); a.linv = const_cast<float*>(linv); a.dvec = dvec_workspace; a.b3 = attn_split_mode(bf16x3, C);
-  a.out = dq;
-  attn_dispatch(2, a, R4, B, (hipStream_t)stream);
-  BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(q)");
-  a.out = dk; a.out2 = dv;
-  attn_dispatch(3, a, R4, B, (hipStream_t)stream);
-  BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(kv)");
-  return BUCTD_OK;
+  return attn_smallqk_bwd<false>("buctd_attn_smallqk_bwd", B, T, R4, C, q, k, v, o, dout, m, linv, scale, p_drop, seed, bf16x3,
+                                 dq, dk, dv, dvec_workspace, stream);
+}
+extern "C" int buctd_attn_smallqk_bwd_dseed(int B, int T, int R4, int C, const float* q, const float* k, const float* v,
+                                            const float* o, const float* dout, const float* m, const float* linv,
+                                            float scale, float p_drop, const uint64_t* seed, int bf16x3, float* dq,
+                                            float* dk, float* dv, float* dvec_workspace, void* stream) {
+  return attn_smallqk_bwd<true>("buctd_attn_smallqk_bwd_dseed", B, T, R4, C, q, k, v, o, dout, m, linv, scale, p_drop, seed,
+                                bf16x3, dq, dk, dv, dvec_workspace, stream);
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #define BUCTD_OK 0
 #define BUCTD_EINVAL (-1)
@@ -97,3 +98,24 @@ __device__ __forceinline__ float keep_scale(uint64_t seed, uint64_t idx, float p
   return u >= p_drop ? inv_keep : 0.f;
 }
 
+// Dropout seed of a launch.  The value form (DSEED = false) takes it as a launch argument; the device form (the _dseed
+// entries, replayed step graphs) reads it from device memory once, at kernel start - one wave-uniform 64-bit load - and
+// runs the value form's code from there.  load_seed of a value is the value itself, so the value instantiations compile
+// as before.
+template <bool DSEED> using SeedArg = typename std::conditional<DSEED, const uint64_t*, uint64_t>::type;
+__device__ __forceinline__ uint64_t load_seed(uint64_t seed) { return seed; }
+__device__ __forceinline__ uint64_t load_seed(const uint64_t* seedp) { return *seedp; }
+// argument struct of a _dseed launch whose value form carries the seed in an argument struct A
+template <typename A> struct DevSeeded {
+  A a;
+  const uint64_t* seedp;
+};
+template <typename A, bool DSEED> using SeededArgs = typename std::conditional<DSEED, DevSeeded<A>, A>::type;
+// host side: the value form's argument struct inside either form
+template <typename A> static inline A& kernel_args(A& a) { return a; }
+template <typename A> static inline A& kernel_args(DevSeeded<A>& d) { return d.a; }
+template <typename A> static inline const A& kernel_args(const A& a) { return a; }
+template <typename A> static inline const A& kernel_args(const DevSeeded<A>& d) { return d.a; }
+// host-side argument check: every value is a seed, a device seed needs its pointer
+static inline bool seed_ok(uint64_t) { return true; }
+static inline bool seed_ok(const uint64_t* seedp) { return seedp != nullptr; }

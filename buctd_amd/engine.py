@@ -532,11 +532,16 @@ class StepGraph:
     ragged batch of an epoch) runs the eager engine.  `output` and `loss` are the graph's static tensors: read or copy them
     before the next call.
 
-    Not capturable, and refused loudly: train-mode dropout (the mask seed is a launch argument: CoAM / TransPose run eager),
-    a gradient exchange over a process group (the buckets are launched from host callbacks)."""
+    Train-mode dropout (CoAM, TransPose) needs `fresh_dropout_masks=True`: the capture hands the dropout kernels device
+    seeds - slots of a table they read when they run - and each replay is preceded by one uncaptured kernel that writes the
+    seeds of the next eager step there (ops.fill_seed_table), so replay n draws the masks the n-th eager step would have and
+    training stays bit-identical to the eager engine; ops.manual_seed and eager steps in between (warm-up, a ragged batch)
+    continue the same seed sequence.  Without it such models are refused (`allow_repeated_dropout_masks`, for measurements
+    only, replays one mask forever).  Not capturable, and refused loudly: a gradient exchange over a process group (the
+    buckets are launched from host callbacks)."""
 
     def __init__(self, model, criterion, optimizer, warmup=3, streams="single", allow_repeated_dropout_masks=False,
-                 autoselect=False):
+                 autoselect=False, fresh_dropout_masks=False):
         if streams not in ("single", "engine"):
             raise ValueError("streams: 'single' (a linear graph) or 'engine' (the engine's branch / weight-gradient streams "
                              "become parallel branches of the graph)")
@@ -548,7 +553,10 @@ class StepGraph:
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self.warmup = int(warmup)
         self.streams = streams
+        if allow_repeated_dropout_masks and fresh_dropout_masks:
+            raise ValueError("StepGraph: allow_repeated_dropout_masks and fresh_dropout_masks exclude each other")
         self._allow_seeds = bool(allow_repeated_dropout_masks)     # measurement only: every replay repeats one mask
+        self._fresh_masks = bool(fresh_dropout_masks)
         # autoselect: the last eager settling step and the first two replays of a signature are timed (device drained around
         # them - they are ordinary training steps on the caller's batches) and the signature keeps the faster path: a linear
         # graph wins below ~batch 32 on HRNet-W32 and loses the stream concurrency of the eager engine above
@@ -581,9 +589,10 @@ class StepGraph:
         static = [t.clone() for t in (x, target, weight)]
         bns = [m for m in self.model.modules() if isinstance(m, bnn.BatchNorm2d)]
         before = [m._pending_batches for m in bns]
+        drawn = ops.seeds_drawn()
         graph = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad()
-        ops.begin_capture(self._allow_seeds)
+        ops.begin_capture(self._allow_seeds, seeds_on=dev if self._fresh_masks else None)
         forks = ops.set_stream_forks(self.streams == "engine")
         try:
             with torch.cuda.graph(graph, capture_error_mode=_CAPTURE_MODE):
@@ -594,21 +603,29 @@ class StepGraph:
                 used = ops.acc_pool.used(dev)
         except BaseException:
             # a failed capture must not leave the pool ordered behind a captured event, nor gradient views of a graph that
-            # does not exist: the eager engine stays usable
+            # does not exist, nor batch or seed counts of a step that never ran: the eager engine stays usable
             ops.set_stream_forks(*forks)
             ops.end_capture()
             ops.acc_pool.rebase(dev, ops.acc_pool.used(dev))
             self.optimizer.zero_grad()
+            for m, b in zip(bns, before):
+                m._pending_batches = b
+            ops._seed_state["counter"] = drawn
             raise
         ops.set_stream_forks(*forks)
+        seeds = ops.capture_seeds()
         keep = ops.end_capture()
         ops.acc_pool.rebase(dev, used)                # eager edge: zero before the first replay, fresh (uncaptured) event
         grads = [(p, p.grad) for p in flat.params if p.grad is not None]
         counts = [(m, m._pending_batches - b) for m, b in zip(bns, before) if m._pending_batches != b]
         for m, b in zip(bns, before):
             m._pending_batches = b                    # the capture enqueued nothing: its batches are counted per replay
+        if seeds is not None:
+            ops._seed_state["counter"] = drawn        # likewise its dropout draws: each replay draws them (fill_seed_table)
+            if seeds[1] == 0:
+                seeds = None
         return {"graph": graph, "static": static, "out": out, "loss": loss, "bn_counts": counts, "keep": keep, "clocked": 0,
-                "grads": grads, "zeroed": getattr(self.optimizer, "zeroed", 0)}
+                "grads": grads, "zeroed": getattr(self.optimizer, "zeroed", 0), "seeds": seeds}
 
     def __call__(self, x, target, weight):
         key = self._signature((x, target, weight))
@@ -629,9 +646,10 @@ class StepGraph:
                     self._eager_s[key] = time.perf_counter() - t0
                 self._dropout = self._dropout or ops.seeds_drawn() != drawn
                 return out, loss
-            if self._dropout and not self._allow_seeds:
+            if self._dropout and not (self._allow_seeds or self._fresh_masks):
                 raise NotImplementedError("StepGraph: this model draws train-mode dropout masks; the mask seed is a launch "
-                                          "argument, a replay would repeat one mask - run the eager engine")
+                                          "argument, a replay would repeat one mask - pass fresh_dropout_masks=True or run "
+                                          "the eager engine")
             g = self._graphs[key] = self._capture(x, target, weight)
         for dst, src in zip(g["static"], (x, target, weight)):
             if dst.data_ptr() != src.data_ptr():
@@ -640,6 +658,8 @@ class StepGraph:
         if clocked:
             torch.cuda.synchronize(x.device)
             t0 = time.perf_counter()
+        if g["seeds"] is not None:
+            ops.fill_seed_table(*g["seeds"])          # stream order puts it in front of every branch of the replay
         g["graph"].replay()
         for m, c in g["bn_counts"]:
             m._pending_batches += c

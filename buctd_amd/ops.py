@@ -25,7 +25,12 @@ from ._C import ConvDesc, MatmulDesc, check, lib, ptr, stream_ptr
 # refuses it (hipErrorStreamCaptureIsolation), and it is not needed - the capture starts behind a device synchronisation
 # and a replay is launched into the stream that carried the eager work in front of it.  Events recorded inside the capture
 # are registered here and waited on as usual (they are edges of the graph).
-_capture = {"on": False, "events": set(), "allow_seeds": False}
+#
+# Dropout seeds drawn during a capture: refused (default), allowed as values (every replay repeats the captured masks), or
+# device seeds - slot i of a per-capture uint64 table that the _dseed kernels read at replay time (engine.StepGraph,
+# fresh_dropout_masks=True, fills the table in front of each replay).
+_capture = {"on": False, "events": set(), "allow_seeds": False, "seed_table": None, "seed_draws": 0}
+_SEED_TABLE_SLOTS = 1024      # dropout draws one captured step may make (CoAM-W48: 6, TransPose-H-A6: 24)
 
 
 def capturing():
@@ -48,14 +53,27 @@ def _wait_event(stream, ev):
     stream.wait_event(ev)
 
 
-def begin_capture(allow_seeds=False):
-    _capture.update(on=True, events=set(), keep=[], allow_seeds=bool(allow_seeds))
+def begin_capture(allow_seeds=False, seeds_on=None):
+    """allow_seeds: next_seed() hands out values during the capture.  seeds_on (a device): it hands out DeviceSeed slots of
+    a table allocated here (capture_seeds() returns it and the number of draws)."""
+    table = None
+    if seeds_on is not None:
+        table = torch.zeros(_SEED_TABLE_SLOTS, dtype=torch.int64, device=seeds_on)
+    _capture.update(on=True, events=set(), keep=[] if table is None else [table], allow_seeds=bool(allow_seeds),
+                    seed_table=table, seed_draws=0)
+
+
+def capture_seeds():
+    """-> (table, draws) of a capture in the device-seed mode, else None"""
+    t = _capture["seed_table"]
+    return None if t is None else (t, _capture["seed_draws"])
 
 
 def end_capture():
-    """-> what must stay alive as long as the captured graph does (events, workspaces outgrown during the capture)"""
+    """-> what must stay alive as long as the captured graph does (events, workspaces outgrown during the capture, the
+    device seed table)"""
     keep = _capture.get("keep", [])
-    _capture.update(on=False, events=set(), keep=[], allow_seeds=False)
+    _capture.update(on=False, events=set(), keep=[], allow_seeds=False, seed_table=None, seed_draws=0)
     return keep
 
 
@@ -241,11 +259,7 @@ def seeds_drawn():
     return _seed_state["counter"]
 
 
-def next_seed():
-    if _capture["on"] and not _capture["allow_seeds"]:
-        raise _C.BuctdHipError("a dropout seed was drawn while a step graph was being captured: the seed is a launch argument, "
-                               "a replay would repeat this step's mask - models with train-mode dropout (CoAM, TransPose) "
-                               "run the eager engine")
+def _seed_base():
     if _seed_state["seed"] is None:
         # first use without an explicit ops.manual_seed: follow torch.manual_seed (and the rank, if a process group
         # is up), so that runs honour the user's seed and replicas draw different masks
@@ -253,8 +267,52 @@ def next_seed():
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             rank = torch.distributed.get_rank()
         manual_seed(mix_seed(torch.initial_seed(), rank))
+    return _seed_state["seed"]
+
+
+class DeviceSeed:
+    """A dropout seed that lives in device memory: slot `index` of a capture's seed table.  The draw sites pass it where
+    they pass an int seed and call the _dseed entries, which read the seed when the kernel runs."""
+    __slots__ = ("table", "index", "ptr")
+
+    def __init__(self, table, index):
+        self.table, self.index = table, index
+        self.ptr = table.data_ptr() + 8 * index
+
+
+def next_seed():
+    """The seed of the next dropout draw: an int (splitmix-keyed counter stream), or a DeviceSeed during a capture in the
+    device-seed mode (the counter does not move: the replays draw, see fill_seed_table)."""
+    if _capture["on"] and not _capture["allow_seeds"]:
+        table = _capture["seed_table"]
+        if table is None:
+            raise _C.BuctdHipError("a dropout seed was drawn while a step graph was being captured: the seed is a launch "
+                                   "argument, a replay would repeat this step's mask - capture with "
+                                   "StepGraph(..., fresh_dropout_masks=True) or run the eager engine")
+        i = _capture["seed_draws"]
+        if i >= table.numel():
+            raise _C.BuctdHipError(f"a captured step draws more than {table.numel()} dropout seeds")
+        _capture["seed_draws"] = i + 1
+        return DeviceSeed(table, i)
+    base = _seed_base()
     _seed_state["counter"] += 1
-    return (_seed_state["seed"] * 0x9E3779B97F4A7C15 + _seed_state["counter"] * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+    return (base * 0x9E3779B97F4A7C15 + _seed_state["counter"] * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
+
+def fill_seed_table(table, n):
+    """Enqueue on the current stream the seeds of the next n draws into table[0:n] (what n next_seed() calls would return)
+    and count them as drawn: the device half of a fresh-mask step-graph replay."""
+    base = _seed_base()
+    check(lib().buctd_dropout_seed_fill(table.data_ptr(), n, base, _seed_state["counter"] & 0xFFFFFFFFFFFFFFFF, stream_ptr()),
+          "dropout_seed_fill")
+    _seed_state["counter"] += n
+
+
+def _seeded(name, seed):
+    """-> (entry, seed argument): the value entry for an int seed, its _dseed twin for a DeviceSeed"""
+    if isinstance(seed, DeviceSeed):
+        return getattr(lib(), name + "_dseed"), seed.ptr
+    return getattr(lib(), name), seed
 
 
 def _f32(t, name="tensor"):
@@ -1328,16 +1386,16 @@ def softmax_dropout_fwd(s, L, scale, p_drop, seed, inplace=True):
     rows = s.numel() // L
     p = s if inplace else torch.empty_like(s)
     pd = torch.empty_like(s) if p_drop > 0 else p
-    check(lib().buctd_softmax_dropout_fwd(ptr(s), rows, L, scale, p_drop, seed, ptr(p), ptr(pd), stream_ptr()),
-          "softmax_dropout_fwd")
+    fn, seed = _seeded("buctd_softmax_dropout_fwd", seed)
+    check(fn(ptr(s), rows, L, scale, p_drop, seed, ptr(p), ptr(pd), stream_ptr()), "softmax_dropout_fwd")
     return p, pd
 
 
 def softmax_dropout_bwd(dpd, p, L, scale, p_drop, seed, inplace=True):
     rows = p.numel() // L
     ds = dpd if inplace else torch.empty_like(dpd)
-    check(lib().buctd_softmax_dropout_bwd(ptr(dpd), ptr(p), rows, L, scale, p_drop, seed, ptr(ds), stream_ptr()),
-          "softmax_dropout_bwd")
+    fn, seed = _seeded("buctd_softmax_dropout_bwd", seed)
+    check(fn(ptr(dpd), ptr(p), rows, L, scale, p_drop, seed, ptr(ds), stream_ptr()), "softmax_dropout_bwd")
     return ds
 
 
@@ -1481,7 +1539,8 @@ def layernorm_bwd(dy, x, mean, invstd, gamma, dgamma, dbeta, accumulate):
 
 def dropout(x, p_drop, seed):
     y = torch.empty_like(x)
-    check(lib().buctd_dropout(ptr(x), ptr(y), x.numel(), p_drop, seed, stream_ptr()), "dropout")
+    fn, seed = _seeded("buctd_dropout", seed)
+    check(fn(ptr(x), ptr(y), x.numel(), p_drop, seed, stream_ptr()), "dropout")
     return y
 
 
@@ -2449,8 +2508,9 @@ class FusedMHA(torch.autograd.Function):
         seed = next_seed()
         out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
         lse = torch.empty((B, T), dtype=torch.float32, device=qk.device)
-        check(lib().buctd_mha_fwd_train(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], scale,
-                                        p_eff, seed, ptr(out), ptr(lse), stream_ptr()), "mha_fwd_train")
+        fn, s = _seeded("buctd_mha_fwd_train", seed)
+        check(fn(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], scale, p_eff, s, ptr(out),
+                 ptr(lse), stream_ptr()), "mha_fwd_train")
         ctx.meta = (scale, p_eff, seed)
         ctx.save_for_backward(qk, v, out, lse)
         return out
@@ -2465,9 +2525,10 @@ class FusedMHA(torch.autograd.Function):
         dqk = torch.empty_like(qk)
         dv = torch.empty_like(v)
         ws = workspace(lib().buctd_mha_bwd_workspace(B, T), qk.device)
-        check(lib().buctd_mha_bwd(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], ptr(out),
-                                  ptr(dout), ptr(lse), scale, p_eff, seed, ptr(dqk), C.c_void_p(dqk.data_ptr() + 4 * d), two_d,
-                                  ptr(dv), dv.shape[2], ptr(ws), ws.numel(), stream_ptr()), "mha_bwd")
+        fn, s = _seeded("buctd_mha_bwd", seed)
+        check(fn(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], ptr(out), ptr(dout), ptr(lse),
+                 scale, p_eff, s, ptr(dqk), C.c_void_p(dqk.data_ptr() + 4 * d), two_d, ptr(dv), dv.shape[2], ptr(ws),
+                 ws.numel(), stream_ptr()), "mha_bwd")
         return dqk, dv, None, None
 
 
@@ -2515,8 +2576,9 @@ class SmallQKAttention(torch.autograd.Function):
         # contractions over T and C on the bf16 matrix cores: two pieces per operand in the bf16x3 mode, three (fp32
         # class) in the default bf16x6 mode, the exact fp32 MFMA kernels in the fp32 mode
         b3 = {"bf16x3": 1, "bf16x6": 2}.get(_conv_math["mode"], 0)
-        check(lib().buctd_attn_smallqk_fwd(B, T, R4, Cn, ptr(qp), ptr(kp), ptr(v), scale, p_eff, seed, b3, ptr(out), ptr(m),
-                                           ptr(linv), stream_ptr()), "attn_smallqk_fwd")
+        fn, s = _seeded("buctd_attn_smallqk_fwd", seed)
+        check(fn(B, T, R4, Cn, ptr(qp), ptr(kp), ptr(v), scale, p_eff, s, b3, ptr(out), ptr(m), ptr(linv), stream_ptr()),
+              "attn_smallqk_fwd")
         ctx.meta = (d, R4, scale, p_eff, seed, b3)
         ctx.save_for_backward(qp, kp, k, v, out, m, linv, w4t, wq, bq)
         return out
@@ -2532,9 +2594,9 @@ class SmallQKAttention(torch.autograd.Function):
         dkp = torch.empty_like(kp)
         dv = torch.empty_like(v)
         dvec = torch.empty((B, T), dtype=torch.float32, device=dev)
-        check(lib().buctd_attn_smallqk_bwd(B, T, R4, Cn, ptr(qp), ptr(kp), ptr(v), ptr(out), ptr(dout), ptr(m), ptr(linv),
-                                           scale, p_eff, seed, b3, ptr(dqp), ptr(dkp), ptr(dv), ptr(dvec), stream_ptr()),
-              "attn_smallqk_bwd")
+        fn, s = _seeded("buctd_attn_smallqk_bwd", seed)
+        check(fn(B, T, R4, Cn, ptr(qp), ptr(kp), ptr(v), ptr(out), ptr(dout), ptr(m), ptr(linv), scale, p_eff, s, b3, ptr(dqp),
+                 ptr(dkp), ptr(dv), ptr(dvec), stream_ptr()), "attn_smallqk_bwd")
         # k' = k w4t^T  ->  dk = dk' w4t ; dw4t = dk'^T k
         dk = torch.empty_like(k)
         matmul(dkp, w4t, dk, batch=1, M=B * T, N=Cn, K=R4, a_layout=0, b_layout=1, lda=R4, ldb=Cn, ldc=Cn)

@@ -363,6 +363,13 @@ int buctd_softmax_dropout_fwd(const float* s, long rows, int L, float scale, flo
 /* ds = scale * p * (g - sum_j g_j p_j), g = dpd * keep/(1-p_drop) */
 int buctd_softmax_dropout_bwd(const float* dpd, const float* p, long rows, int L, float scale, float p_drop,
                               uint64_t seed, float* ds, void* stream);
+/* Device-seed forms (_dseed) of the dropout entries: the same signature with `const uint64_t* seed` in place of the value -
+ * the kernels read *seed once, at start, so a captured step graph draws fresh masks per replay (engine.StepGraph,
+ * fresh_dropout_masks=True).  Output equals the value entry's with seed = *seed, bit for bit.  Same reference call sites. */
+int buctd_softmax_dropout_fwd_dseed(const float* s, long rows, int L, float scale, float p_drop, const uint64_t* seed,
+                                    float* p, float* pd, void* stream);
+int buctd_softmax_dropout_bwd_dseed(const float* dpd, const float* p, long rows, int L, float scale, float p_drop,
+                                    const uint64_t* seed, float* ds, void* stream);
 /* Fused position attention for narrow query/key contractions (self_attention.py:74-86 with fc_q folded into the
  * keys: logits = scale * q' k'^T with q' = [y_cond, 1, 0-pad] and k' = fc_k(y) [Wq | bq | 0], both [B][T][R4]).
  * out = dropout(softmax(logits)) v, v and out [B][T][C]; nothing of size T x T is written to memory.
@@ -380,8 +387,21 @@ int buctd_attn_smallqk_bwd(int B, int T, int R4, int C, const float* q, const fl
                            const float* o, const float* dout, const float* m, const float* linv, float scale,
                            float p_drop, uint64_t seed, int bf16x3, float* dq, float* dk, float* dv,
                            float* dvec_workspace, void* stream);
+/* device-seed forms (self_attention.py:74-86 in a captured training step) */
+int buctd_attn_smallqk_fwd_dseed(int B, int T, int R4, int C, const float* q, const float* k, const float* v, float scale,
+                                 float p_drop, const uint64_t* seed, int bf16x3, float* out, float* m, float* linv,
+                                 void* stream);
+int buctd_attn_smallqk_bwd_dseed(int B, int T, int R4, int C, const float* q, const float* k, const float* v,
+                                 const float* o, const float* dout, const float* m, const float* linv, float scale,
+                                 float p_drop, const uint64_t* seed, int bf16x3, float* dq, float* dk, float* dv,
+                                 float* dvec_workspace, void* stream);
 /* elementwise inverted dropout (transpose_h.py:180-183), mask rebuilt from (seed, index) */
 int buctd_dropout(const float* x, float* y, long n, float p_drop, uint64_t seed, void* stream);
+int buctd_dropout_dseed(const float* x, float* y, long n, float p_drop, const uint64_t* seed, void* stream);
+/* The device form of the host's dropout seed stream (ops.next_seed, the step-graph replay of
+ * lib/core/function.py:102-175): table[i] = base * 0x9E3779B97F4A7C15 + (counter0 + i + 1) * 0xD1B54A32D192ED03 (mod 2^64),
+ * the seed of the (i + 1)-th draw after draw number counter0. */
+int buctd_dropout_seed_fill(uint64_t* table, int n, uint64_t base, uint64_t counter0, void* stream);
 /* LayerNorm over the last dim (transpose_h.py:178-179) */
 int buctd_layernorm_fwd(const float* x, const float* gamma, const float* beta, long rows, int C, float eps, float* y,
                         float* mean, float* invstd, void* stream);
@@ -573,6 +593,13 @@ size_t buctd_mha_bwd_workspace(int B, int T);
 int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
                   const float* dout, const float* lse, float scale, float p_drop, uint64_t seed, float* dq, float* dk,
                   int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream);
+/* device-seed forms (transpose_h.py:192-197 in a captured training step) */
+int buctd_mha_fwd_train_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
+                              float scale, float p_drop, const uint64_t* seed, float* out, float* lse, void* stream);
+int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
+                        const float* out, const float* dout, const float* lse, float scale, float p_drop,
+                        const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------- sample pipeline --- */
 /* Person crop of the per-sample pipeline (dataset/JointsDataset.py:287-294): cv2.warpAffine(img_u8, M, (w, h),

@@ -147,6 +147,8 @@ SIGNATURES = {
     "buctd_conv3x3_bf16x6_group": (_I, [_I, C.POINTER(C3Conv), _P]),
     "buctd_conv3x3_bf16x6_group_eval": (_I, [_I, C.POINTER(C3ConvEval), _P]),
     "buctd_conv3x3_bf16x6_group_workgroups": (_I, [_I, C.POINTER(C3Conv)]),
+    "buctd_conv3x3_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    "buctd_conv3x3_wgrad_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "buctd_gconv_wgrad_x6_supported": (_I, [_I] * 6),
     "buctd_gconv_wgrad_x6_workspace": (_SZ, [_I] * 6),
     "buctd_gconv_wgrad_x6": (_I, [_I] * 6 + [_P, _P, _P, _I, _P, _SZ, _P]),

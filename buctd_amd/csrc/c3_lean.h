@@ -22,6 +22,7 @@
 #pragma once
 #include "c3_common.h"
 
+// (the mask values are part of the C interface: buctd_conv3x3_bf16x6_plan takes an option set as this mask)
 enum { C3M_IN_BN = 1, C3M_STATS = 2, C3M_RES = 4, C3M_BS_REBUILD = 8, C3M_BS_Y = 16 };
 
 // Tensors are addressed through buffer descriptors (32-bit byte offsets, hardware bounds check): a pad row carries the offset

@@ -619,7 +619,7 @@ __global__ __launch_bounds__(256) void conv3x3_prep3_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------- host ----
-struct C3Plan { int MF, NF, WM, WN, BM, BN, na; size_t lds; };
+struct C3Plan { int MF, NF, WM, WN, BM, BN, na; size_t lds; bool single; };
 
 // magic for unsigned division of n < 2^31 by d (2 <= d < 2^31): q = mulhi(n, mul) >> sh
 
@@ -674,7 +674,7 @@ static bool c3_plan(int np, int N, int H, int W, int Ci, int Co, C3Plan* pl) {
       if ((P + 447) / 448 <= 512) mf = 7;
     }
   }
-  pl->MF = mf; pl->NF = nf; pl->WM = wm; pl->WN = wn; pl->BM = wm * mf * 16; pl->BN = bn;
+  pl->MF = mf; pl->NF = nf; pl->WM = wm; pl->WN = wn; pl->BM = wm * mf * 16; pl->BN = bn; pl->single = single;
   pl->na = (pl->BM + 2 * c3_row_width(W) + 3 + 31) / 32;      // the staged rows + one spare row (c3_lean.h: C3Stager)
   size_t stage = (size_t)4 * (mf >= 2 ? 2 : 1) * 16 * (nf * 16 + 4) * 4 + 4 * 128 * 4;   // epilogue staging + row offsets
   if (np == 3 && stage < (size_t)C3_EPI_LDS) stage = C3_EPI_LDS;      // ... the bs reduction scratch and the accumulator exchange
@@ -709,10 +709,11 @@ static int c3_launch(const C3Args& a, const C3Plan& pl, hipStream_t st) {
   return BUCTD_OK;
 }
 
+// dry: no launch - only whether the tile shape has an instance here (buctd_conv3x3_bf16x6_plan)
 template <int NP>
-static int c3_dispatch(const C3Args& a, const C3Plan& pl, hipStream_t st) {
+static int c3_dispatch(const C3Args& a, const C3Plan& pl, hipStream_t st, bool dry = false) {
 #define C3_CASE(mf, nf, wm, wn) \
-  if (pl.MF == mf && pl.NF == nf && pl.WN == wn) return c3_launch<NP, mf, nf, wm, wn>(a, pl, st);
+  if (pl.MF == mf && pl.NF == nf && pl.WN == wn) return dry ? BUCTD_OK : c3_launch<NP, mf, nf, wm, wn>(a, pl, st);
 #define C3_MF(nf, wm, wn) C3_CASE(4, nf, wm, wn) C3_CASE(2, nf, wm, wn) C3_CASE(1, nf, wm, wn)
   if constexpr (NP == 3) { C3_CASE(8, 3, 4, 1) C3_CASE(7, 3, 4, 1) C3_CASE(8, 3, 2, 2) }
   C3_MF(1, 4, 1) C3_MF(2, 4, 1) C3_MF(3, 4, 1) C3_MF(3, 2, 2)
@@ -769,27 +770,38 @@ struct C3BwdStat { const float* z; const float* y; const float* mean; const floa
 // accumulator forms (bn_acc.h): the launch's own forward statistics, and the input BatchNorm's statistics decoded in the prologue
 struct C3Acc { long long* stats_acc; const buctd_bn_acc_in* in; };
 
-// builds the argument block and the tile plan of one convolution (no launch)
-static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* bias,
-                   const float* scale, const float* shift, const float* residual, int relu, float* y,
-                   float* stats_partials, int* stats_counts, const C3InBn* in_bn, const C3BwdStat* bst, const C3Acc* accs,
-                   C3Args& a, C3Plan& pl) {
-  BUCTD_CHECK_ARG(x && wprep && y, "buctd_conv3x3 (split bf16): null tensor pointer");
+// the part of the argument block that the shape alone decides, and the tile plan (also all that buctd_conv3x3_bf16x6_plan
+// needs: the launch and the query share it)
+static int c3_fill_shape(int np, int N, int H, int W, int Ci, int Co, C3Args& a, C3Plan& pl) {
   BUCTD_CHECK_ARG(c3_np_ok(np) && c3_plan(np, N, H, W, Ci, Co, &pl),
                   "buctd_conv3x3 (split bf16): unsupported shape N%d H%d W%d Ci%d Co%d", N, H, W, Ci, Co);
-  BUCTD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "buctd_conv3x3 (split bf16): scale and shift go together");
-  BUCTD_CHECK_ARG((stats_partials == nullptr) == (stats_counts == nullptr),
-                  "buctd_conv3x3 (split bf16): stats partials and counts go together");
-  a.x = x; a.wp = (const unsigned char*)wprep; a.out = y; a.bias = bias; a.scale = scale; a.shift = shift;
-  a.res = residual; a.stats = stats_partials; a.counts = stats_counts;
   a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co;
   a.SW = c3_row_width(W); a.IB = (H + 1) * a.SW;
   const long P = (long)N * a.IB + a.SW;
   BUCTD_CHECK_ARG(P < 2147483647L && (long)N * H * W * (Ci > Co ? Ci : Co) < 2147483647L,
                   "buctd_conv3x3 (split bf16): tensor too large");
   a.P = (int)P;
-  a.relu = relu; a.na = pl.na;
+  a.na = pl.na;
   a.omap = 0; a.oH = H; a.oW = W; a.ost = 1; a.oy0 = a.ox0 = 0;
+  a.col_major = (np == 3 && Co / pl.BN >= 2 && (size_t)c3_steps(Ci, 3) * Co * Geo<3>::BROW > ((size_t)3 << 20)) ? 1 : 0;
+  magic_u32((unsigned)a.IB, &a.ib_mul, &a.ib_sh);
+  magic_u32((unsigned)a.SW, &a.sw_mul, &a.sw_sh);
+  return BUCTD_OK;
+}
+
+// builds the argument block and the tile plan of one convolution (no launch)
+static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* bias,
+                   const float* scale, const float* shift, const float* residual, int relu, float* y,
+                   float* stats_partials, int* stats_counts, const C3InBn* in_bn, const C3BwdStat* bst, const C3Acc* accs,
+                   C3Args& a, C3Plan& pl) {
+  BUCTD_CHECK_ARG(x && wprep && y, "buctd_conv3x3 (split bf16): null tensor pointer");
+  if (const int rc = c3_fill_shape(np, N, H, W, Ci, Co, a, pl)) return rc;
+  BUCTD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "buctd_conv3x3 (split bf16): scale and shift go together");
+  BUCTD_CHECK_ARG((stats_partials == nullptr) == (stats_counts == nullptr),
+                  "buctd_conv3x3 (split bf16): stats partials and counts go together");
+  a.x = x; a.wp = (const unsigned char*)wprep; a.out = y; a.bias = bias; a.scale = scale; a.shift = shift;
+  a.res = residual; a.stats = stats_partials; a.counts = stats_counts;
+  a.relu = relu;
   a.in_mean = a.in_invstd = a.in_gamma = a.in_beta = nullptr;
   a.in_relu = 0;
   if (in_bn && in_bn->mean) {
@@ -821,10 +833,15 @@ static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, 
     a.bs_z = bst->z; a.bs_y = bst->y; a.bs_mean = bst->mean; a.bs_invstd = bst->invstd; a.bs_gamma = bst->gamma;
     a.bs_beta = bst->beta; a.bs_part = bst->part; a.bs_acc = bst->acc;
   }
-  a.col_major = (np == 3 && Co / pl.BN >= 2 && (size_t)c3_steps(Ci, 3) * Co * Geo<3>::BROW > ((size_t)3 << 20)) ? 1 : 0;
-  magic_u32((unsigned)a.IB, &a.ib_mul, &a.ib_sh);
-  magic_u32((unsigned)a.SW, &a.sw_mul, &a.sw_sh);
   return BUCTD_OK;
+}
+
+// the option sets that have a train-mode kernel (c3_lean.h): the mask itself, or -1
+static int c3_lean_mask(int m) {
+  switch (m) {
+    case C3M_STATS: case C3M_STATS | C3M_IN_BN: case C3M_BS_REBUILD: case C3M_RES | C3M_BS_Y: case C3M_RES: return m;
+    default: return -1;
+  }
 }
 
 // the train-mode option set of a launch (c3_lean.h), or -1: the general kernel
@@ -838,10 +855,7 @@ static int c3_lean_mode(const C3Args& a) {
   if (a.stats_acc) m |= C3M_STATS;
   if (a.res) m |= C3M_RES;
   if (a.bs_acc) m |= a.bs_y ? C3M_BS_Y : C3M_BS_REBUILD;
-  switch (m) {
-    case C3M_STATS: case C3M_STATS | C3M_IN_BN: case C3M_BS_REBUILD: case C3M_RES | C3M_BS_Y: case C3M_RES: return m;
-    default: return -1;
-  }
+  return c3_lean_mask(m);
 }
 
 // general: the launch runs conv3x3_x6_group_kernel (no train-mode option set) - its family 1 also holds the small 48-column
@@ -864,9 +878,13 @@ static int c3_group_variant(const C3Plan& pl, int* fam, bool general = false) {
   return -1;
 }
 
+// what a launch would run, for the no-launch queries: kernel 0 = conv3x3_x6_kernel (c3_dispatch), 1 = a group / train-mode
+// kernel with its family and the variant of the first member in launch order; wgs = its grid
+struct C3Dry { int kernel, fam, variant, wgs; };
+
 // n convolutions (argument blocks a[], tile plans pl[]) as ONE launch: the train-mode kernel of their common option set, else
 // the general group kernel (n > 1 only).  *done = false: the tile shapes have no common kernel family - nothing was launched.
-static int c3_group_launch(int n, const C3Args* a, const C3Plan* pl, hipStream_t stream, bool* done, int* dry_wgs = nullptr) {
+static int c3_group_launch(int n, const C3Args* a, const C3Plan* pl, hipStream_t stream, bool* done, C3Dry* dry = nullptr) {
   *done = false;
   int order[C3G_MAX];
   double cost[C3G_MAX];
@@ -911,7 +929,7 @@ static int c3_group_launch(int n, const C3Args* a, const C3Plan* pl, hipStream_t
   for (int i = n; i < C3G_MAX; ++i) h.tiles[i] = h.gx[i] = h.gy[i] = h.variant[i] = 0;
   if (lds > 160 * 1024) return BUCTD_OK;
   *done = true;
-  if (dry_wgs) { *dry_wgs = (int)(per_xcd * 8); return BUCTD_OK; }
+  if (dry) { *dry = C3Dry{1, fam, h.variant[0], (int)(per_xcd * 8)}; return BUCTD_OK; }
   if (lean >= 0) return c3_lean_launch(h, fam, lean, per_xcd * 8, lds, stream);
   static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
   void (*fn)(C3Group) = fam ? conv3x3_x6_group_kernel<1> : conv3x3_x6_group_kernel<0>;
@@ -920,6 +938,16 @@ static int c3_group_launch(int n, const C3Args* a, const C3Plan* pl, hipStream_t
   hipLaunchKernelGGL(fn, dim3(per_xcd * 8), dim3(256), lds, stream, h);
   BUCTD_CHECK_LAUNCH("buctd_conv3x3_bf16x6_group");
   return BUCTD_OK;
+}
+
+// one bf16x6 convolution: the specialised kernel of its train-mode option set if the tile shape has one, else the general
+// kernel.  dry: no launch, *dry says which of the two it would be (buctd_conv3x3_bf16x6_plan)
+static int c3_launch_one(const C3Args& a, const C3Plan& pl, hipStream_t stream, C3Dry* dry = nullptr) {
+  bool done = false;
+  const int rc = c3_group_launch(1, &a, &pl, stream, &done, dry);
+  if (rc || done) return rc;
+  if (dry) *dry = C3Dry{0, -1, -1, ceil_div(a.P, pl.BM) * (a.Co / pl.BN)};
+  return c3_dispatch<3>(a, pl, stream, dry != nullptr);
 }
 
 static int c3_run(int np, int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* bias,
@@ -931,12 +959,7 @@ static int c3_run(int np, int N, int H, int W, int Ci, int Co, const float* x, c
   const int rc = c3_fill(np, N, H, W, Ci, Co, x, wprep, bias, scale, shift, residual, relu, y, stats_partials, stats_counts,
                          in_bn, bst, accs, a, pl);
   if (rc) return rc;
-  if (np == 3 && c3_lean_mode(a) >= 0) {       // a train-mode option set: the specialised kernel, if the tile shape has one
-    bool done = false;
-    const int rc2 = c3_group_launch(1, &a, &pl, (hipStream_t)stream, &done);
-    if (rc2 || done) return rc2;
-  }
-  return np == 3 ? c3_dispatch<3>(a, pl, (hipStream_t)stream) : c3_dispatch<2>(a, pl, (hipStream_t)stream);
+  return np == 3 ? c3_launch_one(a, pl, (hipStream_t)stream) : c3_dispatch<2>(a, pl, (hipStream_t)stream);
 }
 
 // ---- "bf16x3" (NP = 2) entry points --------------------------------------------------------------------------
@@ -1050,12 +1073,8 @@ extern "C" int buctd_conv3x3_bf16x6_group(int n, const buctd_c3_conv* convs, voi
   bool done = false;
   const int rc = c3_group_launch(n, a, pl, (hipStream_t)stream, &done);
   if (rc || done) return rc;
-  for (int k = 0; k < n; ++k) {       // no common kernel: one launch per member (each may still take its train-mode kernel)
-    bool d1 = false;
-    int rc1 = c3_group_launch(1, a + k, pl + k, (hipStream_t)stream, &d1);
-    if (!rc1 && !d1) rc1 = c3_dispatch<3>(a[k], pl[k], (hipStream_t)stream);
-    if (rc1) return rc1;
-  }
+  for (int k = 0; k < n; ++k)         // no common kernel: one launch per member (each may still take its train-mode kernel)
+    if (const int rc1 = c3_launch_one(a[k], pl[k], (hipStream_t)stream)) return rc1;
   return BUCTD_OK;
 }
 
@@ -1087,8 +1106,34 @@ extern "C" int buctd_conv3x3_bf16x6_group_workgroups(int n, const buctd_c3_conv*
   C3Plan pl[C3G_MAX];
   if (const int rc0 = c3_group_fill(n, convs, a, pl)) return rc0;
   bool done = false;
-  int wgs = 0;
-  const int rc = c3_group_launch(n, a, pl, nullptr, &done, &wgs);
+  C3Dry dry{};
+  const int rc = c3_group_launch(n, a, pl, nullptr, &done, &dry);
   if (rc) return rc;
-  return done ? wgs : 0;
+  return done ? dry.wgs : 0;
+}
+
+/* Which tile plan and which kernel buctd_conv3x3_bf16x6* / _acc / _bnstat_acc would run for this shape with the train-mode
+ * option set `option_set` (a C3M_* mask of c3_lean.h, or -1: bias / eval scale / partial-sum statistics / plain).  No launch:
+ * the answer comes from the functions the launch itself goes through.  out[11] = MF, NF, WM, WN, single A buffer, col_major,
+ * kernel (0 = conv3x3_x6_kernel, 1 = the train-mode kernel), its family and variant (-1 for kernel 0), BM, BN. */
+extern "C" int buctd_conv3x3_bf16x6_plan(int N, int H, int W, int Ci, int Co, int option_set, int* out) {
+  BUCTD_CHECK_ARG(out && (option_set == -1 || c3_lean_mask(option_set) >= 0),
+                  "buctd_conv3x3_bf16x6_plan: option set %d is not one of the train-mode sets (or -1)", option_set);
+  static const float some = 0.f;       // stands for "this option is on": c3_lean_mode only looks at which pointers are set
+  const float* on = &some;
+  C3Args a{};
+  C3Plan pl;
+  if (const int rc = c3_fill_shape(3, N, H, W, Ci, Co, a, pl)) return rc;
+  if (option_set >= 0) {
+    if (option_set & C3M_IN_BN) { a.in_acc.acc = (const long long*)on; a.in_gamma = a.in_beta = on; }
+    if (option_set & C3M_STATS) a.stats_acc = (long long*)on;
+    if (option_set & C3M_RES) a.res = on;
+    if (option_set & (C3M_BS_REBUILD | C3M_BS_Y)) a.bs_acc = (long long*)on;
+    if (option_set & C3M_BS_Y) a.bs_y = on;
+  }
+  C3Dry dry{};
+  if (const int rc = c3_launch_one(a, pl, nullptr, &dry)) return rc;
+  const int v[11] = {pl.MF, pl.NF, pl.WM, pl.WN, pl.single ? 1 : 0, a.col_major, dry.kernel, dry.fam, dry.variant, pl.BM, pl.BN};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return BUCTD_OK;
 }

@@ -655,6 +655,15 @@ extern "C" int buctd_conv3x3_wgrad_bf16x3(int N, int H, int W, int Ci, int Co, c
                                           void* stream) {
   return wg3_run(2, N, H, W, Ci, Co, x, dy, dw, accumulate, workspace, workspace_bytes, stream);
 }
+/* The plan buctd_conv3x3_wgrad_bf16x6 / _bnin would run with (no launch): out[4] = CF (16-channel fragments per chunk: 48- or
+ * 32-channel chunk pairs), nsplit (position splits per chunk pair), q and rem (splits take q or q + 1 stages; rem take q + 1). */
+extern "C" int buctd_conv3x3_wgrad_bf16x6_plan(int N, int H, int W, int Ci, int Co, int* out) {
+  WG3Plan pl;
+  BUCTD_CHECK_ARG(out && wg3_plan(3, N, H, W, Ci, Co, &pl),
+                  "buctd_conv3x3_wgrad_bf16x6_plan: unsupported shape N%d H%d W%d Ci%d Co%d", N, H, W, Ci, Co);
+  out[0] = pl.CF; out[1] = pl.nsplit; out[2] = pl.q; out[3] = pl.rem;
+  return BUCTD_OK;
+}
 extern "C" int buctd_conv3x3_wgrad_bf16x6_supported(int N, int H, int W, int Ci, int Co) {
   WG3Plan pl;
   return wg3_plan(3, N, H, W, Ci, Co, &pl) ? 1 : 0;

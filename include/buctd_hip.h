@@ -153,6 +153,16 @@ int buctd_conv3x3_bf16x6_group_eval(int n, const buctd_c3_conv_eval* convs, void
 /* The number of workgroups buctd_conv3x3_bf16x6_group(n, convs) launches as ONE kernel (0: the members share no kernel and go
  * out one launch each; < 0: error).  No launch - for tools that find a launch in a kernel trace by its grid (bench.py). */
 int buctd_conv3x3_bf16x6_group_workgroups(int n, const buctd_c3_conv* convs);
+/* Which tile plan and which kernel a bf16x6 launch of this shape takes (host code only, no launch; computed by the functions
+ * the launch itself goes through, so the answer cannot drift from it).  option_set: the train-mode option set of the launch
+ * as the C3M_* mask of csrc/c3_lean.h - 2 STATS (_acc with stats_acc), 3 STATS | IN_BN (+ in_bn), 8 BS_REBUILD (_bnstat_acc,
+ * bn_y == NULL), 20 RES | BS_Y (_bnstat_acc with residual and bn_y), 4 RES (plain data gradient with residual) - or -1 for
+ * every other call (bias, eval scale / shift, ReLU, partial-sum statistics, nothing at all).
+ * out[11] = MF, NF, WM, WN (16-row / 16-column fragments per wave, waves along positions / columns), single A buffer (the
+ * 448- / 512-position tiles), column-major tile order, kernel (0 = conv3x3_x6_kernel, 1 = the train-mode kernel of the option
+ * set), its kernel family and variant index (-1, -1 for kernel 0), BM, BN (positions / columns of a workgroup tile).
+ * BUCTD_EINVAL: unsupported shape or option set.  For tests that must know which code path a shape exercises. */
+int buctd_conv3x3_bf16x6_plan(int N, int H, int W, int Ci, int Co, int option_set, int* out);
 int buctd_conv3x3_bf16x3_supported(int N, int H, int W, int Ci, int Co);
 int buctd_conv3x3_bf16x3_stats_groups(int N, int H, int W, int Ci, int Co, int* ngroups, int* rows_per_group);
 size_t buctd_conv3x3_bf16x3_prep_bytes(int Ci, int Co, int flip);
@@ -176,6 +186,9 @@ int buctd_conv3x3_bf16x3(int N, int H, int W, int Ci, int Co, const float* x, co
  * transpose-read fragments from position-major LDS tiles, split over positions through `workspace`):
  * dw (+)= sum_p dy[p] (x) x[p + tap].  dw: [Co][3][3][Ci].  Families as above. */
 int buctd_conv3x3_wgrad_bf16x6_supported(int N, int H, int W, int Ci, int Co);
+/* the plan of that launch (no launch): out[4] = CF (3: 48-channel chunk pairs, 2: 32-channel), nsplit (position splits per
+ * chunk pair), q, rem (a split takes q stages, the first rem of them q + 1).  BUCTD_EINVAL: unsupported shape. */
+int buctd_conv3x3_wgrad_bf16x6_plan(int N, int H, int W, int Ci, int Co, int* out);
 size_t buctd_conv3x3_wgrad_bf16x6_workspace(int N, int H, int W, int Ci, int Co);
 int buctd_conv3x3_wgrad_bf16x6(int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw,
                                int accumulate, void* workspace, size_t workspace_bytes, void* stream);

@@ -1,0 +1,582 @@
+"""Every case of tests/helpers/c3_cases.py x every option set of the 3x3 bf16x6 convolution against an fp64 CPU evaluation of
+the SAME operation (torch conv2d / autograd in double on the float inputs), per element.  The host-only closure test
+(test_conv3x3_plan_cover.py) proves that the cases reach every tile plan and every train-mode kernel variant.
+
+Metrics and bars (none of them taken from what the kernels give):
+  convolution outputs   |err| / (sum of the absolute values of the terms of the element: conv(|x|, |w|) + |bias| ...), the
+                        yardstick of test_bf16x6_split_is_exact_on_hard_operands, with its bar: <= 2e-6 and <= 3 x (the same
+                        ratio of the exact-fp32 kernel on the same inputs) + 2e-7;
+  forward statistics    the bars of test_gpu_bn_acc.py (mean 2e-6 max(1, |mu|), invstd 3e-7, running_var 1e-6 relative, applied
+                        output 2e-5 max(1, |y|)), fp64 statistics of the device's own z;
+  BatchNorm-backward    the sums s1 = sum m g, s2 = sum m g zhat (read back as dbeta / dgamma from the kernel that consumes the
+  sums, dz              accumulator) and dz against autograd of an fp64 BatchNorm + ReLU on the device's own g: <= max(5e-6,
+                        4 x the distance of the same evaluation in fp32 on the CPU) relative to the largest element - the rule
+                        of _check in test_gpu_blocks.py.
+Each convolution bar is asserted on the whole tensor and again on the last position tile, the last column tile (BM / BN of
+the plan query) and the border pixels, and the message names the worst element (n, h, w, c).
+
+Measured on an MI355X: worst figure per option set over all 36 cases, next to the baseline it was judged against (the
+exact-fp32 kernel's ratio for the convolution outputs, the fp32 CPU evaluation for the BatchNorm-backward quantities; the worst
+convolution ratios all come from the hard-operands case, random-normal cases stay below 2e-7):
+  option set    conv ratio / fp32 kernel   invstd (bar 3e-7)   s1 / fp32 CPU        s2 / fp32 CPU        dz / fp32 CPU
+  general       7.96e-07 / 6.11e-07        8.3e-08
+  STATS         7.96e-07 / 6.11e-07        1.2e-07
+  STATS|IN_BN   4.47e-07 / 3.84e-07        9.7e-08
+  RES           6.28e-07 / 6.80e-07
+  BS_REBUILD    6.06e-07 / 6.62e-07                            7.4e-08 / 1.0e-07    9.9e-08 / 9.3e-08    1.7e-07 / 1.1e-07
+  RES|BS_Y      6.28e-07 / 6.80e-07                            1.1e-07 / 9.1e-08    1.2e-07 / 1.1e-07    1.8e-07 / 1.3e-07
+  wgrad         3.78e-07 / 7.38e-07
+(every BatchNorm-backward figure is below the 5e-6 floor of its bar).  Wall time of the module: 45-52 s (255 tests; test_gpu_conv3x3_split.py:
+6 s on the same machine - the difference is the twelve model shapes at batch 32 and their fp64 references).
+
+The partial-sum form buctd_conv3x3_bf16x6_bnstat has no caller left in block.hip / ops.py (the block path uses the accumulator
+form only); it is not exercised here."""
+import ctypes as C
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests.helpers import c3_cases as T
+
+pytestmark = pytest.mark.gpu
+
+HARD = (2, 9, 7, 48, 48)          # the shape of the hard-operands test
+CONV_CASES = [(s, False) for s in T.CASES] + [(HARD, True)]
+WORST = {}
+
+
+def _id(c):
+    return T.case_id(c[0]) + ("-hard" if c[1] else "")
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def wcl(w):
+    return w.contiguous(memory_format=torch.channels_last)
+
+
+class _Bn:
+    """the attributes ops.BnAccInput reads from a BatchNorm module"""
+
+    def __init__(self, Cn, dev, seed=0, eps=1e-5, momentum=0.1):
+        g = torch.Generator().manual_seed(Cn + seed)
+        self.weight = (1.0 + 0.3 * torch.randn(Cn, generator=g)).to(dev)
+        self.bias = (0.2 * torch.randn(Cn, generator=g)).to(dev)
+        self.running_mean = torch.zeros(Cn, device=dev)
+        self.running_var = torch.ones(Cn, device=dev)
+        self.eps, self.momentum, self.track_running_stats = eps, momentum, True
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report():
+    yield
+    print("\nworst figures per option set (measured / baseline, case):")
+    for k in sorted(WORST):
+        v = WORST[k]
+        print(f"  {k:28s} {v[0]:.3e} / {v[1]:.3e}  at {v[2]}")
+
+
+def _note(key, val, base, where):
+    if key not in WORST or val > WORST[key][0]:
+        WORST[key] = (val, base, where)
+
+
+@pytest.fixture
+def x6(dev):
+    from buctd_amd import ops
+    old = ops.get_conv_math()
+    ops.set_conv_math("bf16x6")
+    ops.step_boundary(dev)
+    yield ops
+    ops.set_conv_math(old)
+
+
+def in_fp32(ops, fn):
+    ops.set_conv_math("fp32")
+    try:
+        return fn()
+    finally:
+        ops.set_conv_math("bf16x6")
+
+
+def plan(shape, option_set):
+    from buctd_amd import _C
+    out = (C.c_int * 11)()
+    assert _C.lib().buctd_conv3x3_bf16x6_plan(*shape, option_set, out) == 0, f"no plan for {shape}"
+    return dict(zip(("MF", "NF", "WM", "WN", "single", "col_major", "kernel", "family", "variant", "BM", "BN"), out))
+
+
+def hard_operands(shape, g, lo, hi, shift):
+    """all 24 mantissa bits set, exponents lo..hi (then scaled by 2^shift - exact), random sign"""
+    mant = (torch.randint(0, 2 ** 23, shape, generator=g) | 1).float() / 2 ** 23 + 1.0
+    v = mant * torch.exp2(torch.randint(lo, hi + 1, shape, generator=g).float() + shift)
+    return v * (torch.randint(0, 2, shape, generator=g).float() * 2 - 1)
+
+
+class Inputs:
+    """the float inputs of one case (NCHW on the CPU) and, on demand, the fp64 references built from them"""
+
+    def __init__(self, shape, hard):
+        N, H, W, Ci, Co = shape
+        self.shape, self.hard = shape, hard
+        g = torch.Generator().manual_seed(sum(shape) * 31 + Ci)
+        if hard:
+            # 2^-20..2^20 inside one reduction, moved down by 2^-14 so that the sums of squares of the outputs stay inside
+            # the range of the statistics accumulator (bn_acc.h: |sum| < 2^46 per workgroup)
+            self.x = hard_operands((N, Ci, H, W), g, -20, 20, -14)
+            self.w = hard_operands((Co, Ci, 3, 3), g, -8, 8, -6)
+            self.wb = hard_operands((Ci, Co, 3, 3), g, -8, 8, -6)
+            self.res = hard_operands((N, Co, H, W), g, -20, 20, -14)
+        else:
+            self.x = torch.randn(N, Ci, H, W, generator=g) + 0.5
+            self.w = torch.randn(Co, Ci, 3, 3, generator=g) / math.sqrt(9 * Ci)
+            self.wb = torch.randn(Ci, Co, 3, 3, generator=g) / math.sqrt(9 * Ci)     # forward Co -> Ci: its data gradient is Ci -> Co
+            self.res = torch.randn(N, Co, H, W, generator=g)
+        self.bias = torch.randn(Co, generator=g)
+        self.scale, self.shift = torch.rand(Co, generator=g) + 0.5, torch.randn(Co, generator=g)
+        self.zb = torch.randn(N, H, W, Co, generator=g) * 1.7 + 0.3                   # the z of the BatchNorm whose backward consumes dx
+        self.r2 = torch.randn(N, H, W, Co, generator=g)
+        self.memo = {}
+
+    def get(self, key, fn):
+        if key not in self.memo:
+            self.memo[key] = fn()
+        return self.memo[key]
+
+    def fwd(self):      # conv(x, w) and conv(|x|, |w|), NHWC double
+        return self.get("fwd", lambda: (nhwc(F.conv2d(self.x.double(), self.w.double(), None, 1, 1)),
+                                        nhwc(F.conv2d(self.x.double().abs(), self.w.double().abs(), None, 1, 1))))
+
+    def dgrad(self):    # the data gradient of the forward convolution wb (Co -> Ci) at dy = x
+        return self.get("dgrad", lambda: (nhwc(F.conv_transpose2d(self.x.double(), self.wb.double(), None, 1, 1)),
+                                          nhwc(F.conv_transpose2d(self.x.double().abs(), self.wb.double().abs(), None, 1, 1))))
+
+
+_last = {}
+
+
+def inputs(case):
+    if _last.get("case") != case:
+        _last.clear()
+        _last.update(case=case, inp=Inputs(*case))
+    return _last["inp"]
+
+
+def subsets(shape, pl):
+    """boolean masks [N, H, W, Co]-broadcastable: whole tensor, last position tile, last column tile, image borders"""
+    N, H, W, Ci, Co = shape
+    SW, IB = W + 1, (H + 1) * (W + 1)
+    n, y, x = torch.meshgrid(torch.arange(N), torch.arange(H), torch.arange(W), indexing="ij")
+    p = n * IB + (y + 1) * SW + (x + 1)                         # the padded flattened position of a pixel (c3_common.h)
+    last_tile = (p // pl["BM"] == int(p.max()) // pl["BM"])[..., None].expand(N, H, W, Co)
+    last_col = (torch.arange(Co) >= Co - pl["BN"]).expand(N, H, W, Co)
+    border = ((y == 0) | (y == H - 1) | (x == 0) | (x == W - 1))[..., None].expand(N, H, W, Co)
+    return {"whole tensor": None, "last position tile": last_tile, "last column tile": last_col, "border pixels": border}
+
+
+def check_conv(name, opt, case, got, got32, ref, mag):
+    """got / got32: the bf16x6 and the exact-fp32 kernel's output (NHWC, device); ref / mag: fp64 value and sum of |terms|"""
+    shape = case[0]
+    pl = plan(shape, T.OPTION_SETS[opt])
+    mag = mag.clamp_min(1e-300)
+    r = (got.double().cpu() - ref).abs() / mag
+    r32 = float(((got32.double().cpu() - ref).abs() / mag).max())
+    bar = min(2e-6, 3 * r32 + 2e-7)
+    worst = float(r.max())
+    at = tuple(int(v) for v in torch.unravel_index(r.argmax(), r.shape))
+    print(f"{opt} {name} {_id(case)}: error / sum|terms| bf16x6 {worst:.3e}, exact-fp32 kernel {r32:.3e} (bar {bar:.3e}); "
+          f"kernel {pl['kernel']} MF {pl['MF']} NF {pl['NF']} {pl['WM']}x{pl['WN']}")
+    _note(f"{opt}: conv", worst, r32, _id(case))
+    assert torch.isfinite(got).all(), f"{opt} {name} {shape}: non-finite output"
+    for where, m in subsets(shape, pl).items():
+        rr = r if m is None else torch.where(m, r, torch.zeros((), dtype=r.dtype))
+        w_ = float(rr.max())
+        a_ = tuple(int(v) for v in torch.unravel_index(rr.argmax(), rr.shape))
+        assert w_ <= bar, (f"{opt} {name} {shape} [{where}]: error / sum|terms| {w_:.3e} > {bar:.3e} at (n, h, w, c) = {a_} "
+                           f"(fp32 kernel {r32:.3e}; worst of the tensor {worst:.3e} at {at}; plan {pl})")
+
+
+def check_stats(name, opt, case, z, bnin, bn, y=None, res=None, relu=True):
+    """forward statistics decoded from an accumulator against fp64 statistics of the device's own z"""
+    Cn = z.shape[-1]
+    zd = z.double().cpu().reshape(-1, Cn)
+    rows = zd.shape[0]
+    mu, var = zd.mean(0), zd.var(0, unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + bn.eps)
+    e_mu = float(((bnin.mean.double().cpu() - mu).abs() / mu.abs().clamp_min(1.0)).max())
+    e_is = float(((bnin.invstd.double().cpu() - invstd).abs() / invstd).max())
+    rm = bn.momentum * mu
+    rv = (1 - bn.momentum) + bn.momentum * var * rows / (rows - 1)
+    e_rm = float(((bn.running_mean.double().cpu() - rm).abs() / rm.abs().clamp_min(1.0)).max())
+    e_rv = float(((bn.running_var.double().cpu() - rv).abs() / rv).max())
+    print(f"{opt} {name} {_id(case)}: mean {e_mu:.2e} (2e-6), invstd {e_is:.2e} (3e-7), running_mean {e_rm:.2e} (1e-6), "
+          f"running_var {e_rv:.2e} (1e-6)")
+    _note(f"{opt}: invstd", e_is, 3e-7, _id(case))
+    assert e_mu <= 2e-6 and e_is <= 3e-7 and e_rm <= 1e-6 and e_rv <= 1e-6, f"{opt} {name} {case[0]}"
+    if y is not None:
+        yr = (zd - mu) * invstd * bn.weight.double().cpu() + bn.bias.double().cpu()
+        if res is not None:
+            yr = yr + res.double().cpu().reshape(-1, Cn)
+        if relu:
+            yr = torch.relu(yr)
+        e = (y.double().cpu().reshape(-1, Cn) - yr).abs() / yr.abs().clamp_min(1.0)
+        assert float(e.max()) <= 2e-5, f"{opt} {name} {case[0]}: applied output off by {float(e.max()):.2e} at row, channel " \
+                                       f"{tuple(int(v) for v in torch.unravel_index(e.argmax(), e.shape))}"
+
+
+def bn_backward_reference(g, z, res, gamma, beta, m, dtype):
+    """autograd of BatchNorm (train mode) (+ residual) + ReLU with the ReLU mask m given: -> dz, dgamma (= s2), dbeta (= s1)"""
+    Cn = z.shape[-1]
+    zz = z.to(dtype).reshape(-1, Cn).requires_grad_(True)
+    ga, be = gamma.to(dtype).requires_grad_(True), beta.to(dtype).requires_grad_(True)
+    mu, var = zz.mean(0), zz.var(0, unbiased=False)
+    out = (zz - mu) / torch.sqrt(var + 1e-5) * ga + be
+    if res is not None:
+        out = out + res.to(dtype).reshape(-1, Cn)
+    (out * m.to(dtype).reshape(-1, Cn)).backward(g.to(dtype).reshape(-1, Cn))
+    return zz.grad.reshape(z.shape), ga.grad, be.grad
+
+
+def check_bn_backward(opt, case, g_dev, dz, dgamma, dbeta, z, res, gamma, beta, m):
+    g = g_dev.cpu()
+    ref = bn_backward_reference(g, z, res, gamma, beta, m, torch.float64)
+    cpu = bn_backward_reference(g, z, res, gamma, beta, m, torch.float32)
+    for name, got, r64, r32 in zip(("dz", "s2 = sum m g zhat (dgamma)", "s1 = sum m g (dbeta)"), (dz, dgamma, dbeta), ref, cpu):
+        top = float(r64.abs().max())
+        e = (got.double().cpu() - r64).abs() / top
+        e_cpu = float((r32.double() - r64).abs().max()) / top
+        bar = max(5e-6, 4 * e_cpu)
+        at = tuple(int(v) for v in torch.unravel_index(e.argmax(), e.shape))
+        print(f"{opt} {name} {_id(case)}: rel. error vs fp64 {float(e.max()):.3e}, fp32 on the CPU {e_cpu:.3e} (bar {bar:.3e})")
+        _note(f"{opt}: {name.split(' ')[0]}", float(e.max()), e_cpu, _id(case))
+        assert float(e.max()) <= bar, f"{opt} {name} {case[0]}: {float(e.max()):.3e} > {bar:.3e} at {at} (fp32 CPU {e_cpu:.3e})"
+
+
+def bn_params(inp, dev):
+    """the BatchNorm behind the data gradient: float batch statistics of zb (what its forward left), gamma, beta"""
+    Co = inp.shape[4]
+    zd = inp.zb.double().reshape(-1, Co)
+    mean = zd.mean(0).float()
+    invstd = (1.0 / torch.sqrt(zd.var(0, unbiased=False) + 1e-5)).float()
+    bn = _Bn(Co, dev, seed=3)
+    return mean, invstd, bn.weight.cpu(), bn.bias.cpu()
+
+
+def bnstat_acc(ops, shape, x, wb, residual, dx, bn_z, bn_y, mean, invstd, gamma, beta):
+    """buctd_conv3x3_bf16x6_bnstat_acc as block.hip calls it, then the consumer of the accumulator (buctd_bn_bwd_acc with
+    acc_ready = 1): -> dz, dgamma, dbeta"""
+    N, H, W, Ci, Co = shape
+    lib, ptr = ops.lib(), ops.ptr
+    dev = x.device
+    acc = ops.AccRef(Co, dev)
+    wp = ops._conv3x3_prepared(wb, 1)
+    ops.check(lib.buctd_conv3x3_bf16x6_bnstat_acc(N, H, W, Ci, Co, ptr(x), ptr(wp), ptr(residual), ptr(dx), ptr(bn_z), ptr(bn_y),
+                                                  ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), C.c_void_p(acc.ptr),
+                                                  ops.stream_ptr()), "conv3x3_bf16x6_bnstat_acc")
+    dz = torch.empty_like(bn_z)
+    dgamma, dbeta = torch.empty(Co, device=dev), torch.empty(Co, device=dev)
+    ops.check(lib.buctd_bn_bwd_acc(ptr(dx), ptr(bn_y), ptr(bn_z), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), 1, N * H * W, Co,
+                                   ptr(dz), None, ptr(dgamma), ptr(dbeta), 0, C.c_void_p(acc.ptr), 1, ops.stream_ptr()),
+              "bn_bwd_acc")
+    return dz, dgamma, dbeta
+
+
+def rebuilt_mask(ops, inp, mean, invstd, gamma, beta, dev):
+    """The ReLU mask (z - mean) (invstd gamma) + beta > 0 in fp64; where the value is within fp32 rounding of zero the sign is
+    undecided and the device's own forward (bn_apply, whose expression the kernel documents it rebuilds) decides."""
+    v = (inp.zb.double() - mean.double()) * (invstd.double() * gamma.double()) + beta.double()
+    band = v.abs() <= 4e-7 * ((inp.zb.double() - mean.double()).abs() * (invstd.double() * gamma.double()).abs() + beta.double().abs())
+    yd = ops.bn_apply(inp.zb.to(dev), mean.to(dev), invstd.to(dev), gamma.to(dev), beta.to(dev), None, True).cpu()
+    return torch.where(band, yd > 0, v > 0)
+
+
+def run_general(ops, dev, case):
+    inp = inputs(case)
+    N, H, W, Ci, Co = inp.shape
+    xd, wd, wbd = nhwc(inp.x).to(dev), wcl(inp.w).to(dev), wcl(inp.wb).to(dev)
+    resd = nhwc(inp.res).to(dev)
+    ref, mag = inp.fwd()
+    b, sc, sh = inp.bias.to(dev), inp.scale.to(dev), inp.shift.to(dev)
+    f = lambda: ops.conv_fwd(xd, wd, b, 1, 1)
+    check_conv("bias", "general", case, f(), in_fp32(ops, f), ref + inp.bias.double(), mag + inp.bias.double().abs())
+    f = lambda: ops.conv_fwd(xd, wd, None, 1, 1, scale=sc, shift=sh, residual=resd, relu=True)
+    rd = nhwc(inp.res).double()
+    check_conv("scale/shift/residual/relu", "general", case, f(), in_fp32(ops, f),
+               torch.relu(ref * inp.scale.double() + inp.shift.double() + rd),
+               mag * inp.scale.double().abs() + inp.shift.double().abs() + rd.abs())
+    z, part, info = ops.conv_fwd(xd, wd, None, 1, 1, stats=True)
+    z32 = inp.get("z32", lambda: in_fp32(ops, lambda: ops.conv_fwd(xd, wd, None, 1, 1)).cpu())
+    check_conv("partial-sum statistics: z", "general", case, z, z32, ref, mag)
+    assert int(info[2].sum()) == N * H * W, "valid-row counts must add up to N*H*W"
+    bn = _Bn(Co, dev)
+
+    class St:
+        pass
+    st = St()
+    st.mean, st.invstd = ops.bn_finalize(part, info, N * H * W, Co, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
+    check_stats("partial-sum statistics", "general", case, z, st, bn)
+    f = lambda: ops.conv_dgrad(xd, wbd, (N, H, W, Co), 1, 1)
+    dref, dmag = inp.dgrad()
+    dx32 = inp.get("dx32", lambda: in_fp32(ops, f).cpu())
+    check_conv("data gradient", "general", case, f(), dx32, dref, dmag)
+
+
+def run_stats(ops, dev, case):
+    inp = inputs(case)
+    N, H, W, Ci, Co = inp.shape
+    xd, wd = nhwc(inp.x).to(dev), wcl(inp.w).to(dev)
+    ref, mag = inp.fwd()
+    z, acc, info = ops.conv_fwd(xd, wd, None, 1, 1, stats="acc")
+    assert info[0] == "acc"
+    z32 = inp.get("z32", lambda: in_fp32(ops, lambda: ops.conv_fwd(xd, wd, None, 1, 1)).cpu())
+    check_conv("z", "STATS", case, z, z32, ref, mag)
+    bn = _Bn(Co, dev)
+    bnin = ops.BnAccInput(acc, N * H * W, bn, True)
+    resd = nhwc(inp.res).to(dev)
+    y = ops.bn_apply_acc(z, bnin, resd, True)
+    check_stats("statistics", "STATS", case, z, bnin, bn, y, resd)
+
+
+def run_stats_in_bn(ops, dev, case):
+    inp = inputs(case)
+    N, H, W, Ci, Co = inp.shape
+    g = torch.Generator().manual_seed(Ci + 11)
+    w0 = (hard_operands((Ci, Ci, 3, 3), g, -8, 8, -6) if inp.hard else torch.randn(Ci, Ci, 3, 3, generator=g) / math.sqrt(9 * Ci))
+    # the producer: a convolution with its own statistics accumulator; its raw output z1 is this launch's input
+    z1, acc1, info1 = ops.conv_fwd(nhwc(inp.x).to(dev), wcl(w0).to(dev), None, 1, 1, stats="acc")
+    assert info1[0] == "acc"
+    bn1 = _Bn(Ci, dev, seed=1)
+    bnin1 = ops.BnAccInput(acc1, N * H * W, bn1, True, relu=True)
+    wd = wcl(inp.w).to(dev)
+    z2, acc2, info2 = ops.conv_fwd(z1, wd, None, 1, 1, stats="acc", in_bn=bnin1)
+    assert info2[0] == "acc"
+    # fp64: conv(relu(bn_train(z1))) from the same z1
+    zd = z1.double().cpu()
+    z2d = zd.reshape(-1, Ci)
+    mu, var = z2d.mean(0), z2d.var(0, unbiased=False)
+    a = (zd - mu) / torch.sqrt(var + bn1.eps) * bn1.weight.double().cpu()
+    beta = bn1.bias.double().cpu()
+    y1 = torch.relu(a + beta)
+    terms = torch.where(y1 > 0, a.abs() + beta.abs(), torch.zeros((), dtype=torch.float64))
+    w64 = inp.w.double()
+    ref = nhwc(F.conv2d(nchw(y1), w64, None, 1, 1))
+    mag = nhwc(F.conv2d(nchw(terms), w64.abs(), None, 1, 1))
+    y1f = y1.float().to(dev)
+    z32 = in_fp32(ops, lambda: ops.conv_fwd(y1f, wd, None, 1, 1))
+    check_conv("z of conv(relu(bn(z1)))", "STATS|IN_BN", case, z2, z32, ref, mag)
+    check_stats("the producer's statistics (mean_out, invstd_out, running)", "STATS|IN_BN", case, z1, bnin1, bn1)
+    bn2 = _Bn(Co, dev, seed=2)
+    bnin2 = ops.BnAccInput(acc2, N * H * W, bn2, True)
+    y = ops.bn_apply_acc(z2, bnin2, None, True)
+    check_stats("its own statistics", "STATS|IN_BN", case, z2, bnin2, bn2, y)
+
+
+def run_res(ops, dev, case):
+    inp = inputs(case)
+    N, H, W, Ci, Co = inp.shape
+    xd, wbd, resd = nhwc(inp.x).to(dev), wcl(inp.wb).to(dev), nhwc(inp.res).to(dev)
+    f = lambda: ops.conv_dgrad(xd, wbd, (N, H, W, Co), 1, 1, residual=resd)
+    dref, dmag = inp.dgrad()
+    rd = nhwc(inp.res).double()
+    check_conv("data gradient + skip gradient", "RES", case, f(), in_fp32(ops, f), dref + rd, dmag + rd.abs())
+
+
+def run_bs(ops, dev, case, opt):
+    inp = inputs(case)
+    N, H, W, Ci, Co = inp.shape
+    with_y = opt == "RES|BS_Y"
+    xd, wbd = nhwc(inp.x).to(dev), wcl(inp.wb).to(dev)
+    mean, invstd, gamma, beta = bn_params(inp, dev)
+    dref, dmag = inp.dgrad()
+    dx32 = inp.get("dx32", lambda: in_fp32(ops, lambda: ops.conv_dgrad(xd, wbd, (N, H, W, Co), 1, 1)).cpu())
+    if with_y:
+        # the forward output of that BatchNorm (with its skip connection) decides the mask; the skip gradient joins dx
+        yb = torch.relu(((inp.zb.double() - mean.double()) * (invstd.double() * gamma.double()) + beta.double()
+                         + inp.r2.double())).float()
+        m, res_bn = yb > 0, inp.r2
+        rd = nhwc(inp.res)
+        dref, dmag, dx32 = dref + rd.double(), dmag + rd.double().abs(), dx32 + rd      # (fp32: one exact-to-half-ulp add)
+        resd, ybd, betad = rd.to(dev), yb.to(dev), None
+    else:
+        m, res_bn = rebuilt_mask(ops, inp, mean, invstd, gamma, beta, dev), None
+        resd, ybd, betad = None, None, beta.to(dev)
+    dx = torch.empty((N, H, W, Co), device=dev)
+    dz, dgamma, dbeta = bnstat_acc(ops, inp.shape, xd, wbd, resd, dx, inp.zb.to(dev), ybd, mean.to(dev), invstd.to(dev),
+                                   gamma.to(dev), betad)
+    check_conv("dx", opt, case, dx, dx32, dref, dmag)
+    check_bn_backward(opt, case, dx, dz, dgamma, dbeta, inp.zb, res_bn, gamma, beta, m)
+
+
+RUN = {"general": run_general, "STATS": run_stats, "STATS|IN_BN": run_stats_in_bn, "RES": run_res,
+       "BS_REBUILD": lambda ops, dev, case: run_bs(ops, dev, case, "BS_REBUILD"),
+       "RES|BS_Y": lambda ops, dev, case: run_bs(ops, dev, case, "RES|BS_Y")}
+
+
+@pytest.mark.parametrize("opt", list(T.OPTION_SETS))
+@pytest.mark.parametrize("case", CONV_CASES, ids=_id)
+def test_case_x_option_set_against_fp64(x6, dev, case, opt):
+    RUN[opt](x6, dev, case)
+
+
+# ---- weight gradient -----------------------------------------------------------------------------------------------------
+def check_wgrad(name, case, got, got32, ref, mag):
+    mag = mag.clamp_min(1e-300)
+    r = (got.double().cpu() - ref).abs() / mag
+    r32 = float(((got32.double().cpu() - ref).abs() / mag).max())
+    bar = min(2e-6, 3 * r32 + 2e-7)
+    at = tuple(int(v) for v in torch.unravel_index(r.argmax(), r.shape))
+    print(f"wgrad {name} {_id(case)}: error / sum|terms| bf16x6 {float(r.max()):.3e}, exact-fp32 kernel {r32:.3e} (bar {bar:.3e})")
+    _note("wgrad", float(r.max()), r32, _id(case))
+    assert torch.isfinite(got).all() and float(r.max()) <= bar, \
+        f"wgrad {name} {case[0]}: {float(r.max()):.3e} > {bar:.3e} at (co, ci, r, s) = {at} (fp32 kernel {r32:.3e})"
+
+
+def wgrad_ref(x, dy, shape):
+    """x, dy: NCHW double"""
+    N, H, W, Ci, Co = shape
+    return torch.nn.grad.conv2d_weight(x, (Co, Ci, 3, 3), dy, stride=1, padding=1)
+
+
+@pytest.mark.parametrize("case", [(s, False) for s in T.WGRAD_CASES] + [(HARD, True)], ids=_id)
+def test_weight_gradient_against_fp64(x6, dev, case):
+    ops = x6
+    shape, hard = case
+    N, H, W, Ci, Co = shape
+    from buctd_amd import _C
+    wpl = (C.c_int * 4)()
+    assert _C.lib().buctd_conv3x3_wgrad_bf16x6_plan(*shape, wpl) == 0
+    g = torch.Generator().manual_seed(sum(shape) * 17 + Co)
+    if hard:
+        # (the products of a weight gradient are summed over all positions: 2^-10..2^10 keeps them inside fp32's exponent range)
+        x, dy = hard_operands((N, Ci, H, W), g, -10, 10, 0), hard_operands((N, Co, H, W), g, -10, 10, 0)
+    else:
+        x, dy = torch.randn(N, Ci, H, W, generator=g) + 0.5, torch.randn(N, Co, H, W, generator=g)
+    w_like = wcl(torch.empty(Co, Ci, 3, 3)).to(dev)
+    xd, dyd = nhwc(x).to(dev), nhwc(dy).to(dev)
+    ref, mag = wgrad_ref(x.double(), dy.double(), shape), wgrad_ref(x.double().abs(), dy.double().abs(), shape)
+    need = ops.lib().buctd_conv3x3_wgrad_bf16x6_workspace(*shape)
+    ops.workspace(need, dev).fill_(0xFF)
+    f = lambda: ops.conv_wgrad(xd, dyd, w_like, 1, 1)
+    dw = f()
+    dw32 = in_fp32(ops, f)
+    check_wgrad("plain", case, dw, dw32, ref, mag)
+    assert torch.equal(dw, f()), "the weight gradient is not bit-reproducible"
+    # accumulate into a non-zero gradient
+    out0 = wcl(torch.randn(Co, Ci, 3, 3, generator=g))
+    out = out0.to(dev)
+    ops.conv_wgrad(xd, dyd, w_like, 1, 1, out=out, accumulate=1)
+    check_wgrad("accumulate", case, out, dw32 + out0.to(dev), ref + out0.double(), mag + out0.double().abs())
+    # the X operand normalised on the fly: x is a raw z, the kernel uses relu((z - mean) (invstd gamma) + beta)
+    zd = x.double()
+    mean = zd.mean((0, 2, 3)).float()
+    invstd = (1.0 / torch.sqrt(zd.var((0, 2, 3), unbiased=False) + 1e-5)).float()
+    bn = _Bn(Ci, dev, seed=4)
+    x_bn = (mean.to(dev), invstd.to(dev), bn.weight, bn.bias, True)
+    if Ci % (wpl[0] * 16) != 0:
+        with pytest.raises(_C.BuctdHipError):        # documented: the fused input BatchNorm needs whole channel chunks
+            ops.conv_wgrad(xd, dyd, w_like, 1, 1, x_bn=x_bn)
+        return
+    v = lambda t: t.double().cpu().view(1, -1, 1, 1)
+    a = (zd - v(mean)) * (v(invstd) * v(bn.weight))
+    y1 = torch.relu(a + v(bn.bias))
+    terms = torch.where(y1 > 0, a.abs() + v(bn.bias).abs(), torch.zeros((), dtype=torch.float64))
+    y1f = nhwc(y1.float()).to(dev)
+    dwb = ops.conv_wgrad(xd, dyd, w_like, 1, 1, x_bn=x_bn)
+    dwb32 = in_fp32(ops, lambda: ops.conv_wgrad(y1f, dyd, w_like, 1, 1))
+    check_wgrad("x_bn", case, dwb, dwb32, wgrad_ref(y1, dy.double(), shape), wgrad_ref(terms, dy.double().abs(), shape))
+    assert torch.equal(dwb, ops.conv_wgrad(xd, dyd, w_like, 1, 1, x_bn=x_bn))
+
+
+# ---- guard bands -----------------------------------------------------------------------------------------------------------
+SENTINEL = -12345.678
+
+
+def banded(t, dev, shape, fill=float("nan")):
+    """a copy of t (device) in the middle of a larger allocation filled with `fill`: >= 2 * SW + 3 rows of it on either side"""
+    W, Cn = shape[2], t.shape[-1]
+    pad = (2 * (W + 1) + 3 + 5) * Cn
+    big = torch.full((2 * pad + t.numel(),), fill, dtype=torch.float32, device=dev)
+    view = big[pad:pad + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view, big, pad
+
+
+def untouched(big, pad, n):
+    return bool((big[:pad] == SENTINEL).all()) and bool((big[pad + n:] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("opt", [o for o in T.OPTION_SETS if o != "general"])
+@pytest.mark.parametrize("shape", T.GUARD_CASES, ids=T.case_id)
+def test_inputs_between_nan_bands(x6, dev, shape, opt):
+    """A descriptor range or a row bound that reaches past its tensor reads NaN and shows up in the result; a store past the
+    output lands in the sentinel.  Ordinary in-bounds allocations only."""
+    ops = x6
+    N, H, W, Ci, Co = shape
+    inp = Inputs(shape, False)
+    xd, resd = nhwc(inp.x).to(dev), nhwc(inp.res).to(dev)
+    zbd, r2 = inp.zb.to(dev), inp.r2
+    mean, invstd, gamma, beta = (t.to(dev) for t in bn_params(inp, dev))
+
+    def run(band):
+        ops.step_boundary(dev)
+        wrap = (lambda t: banded(t, dev, shape)[0]) if band else (lambda t: t)
+        if opt == "STATS":
+            z, acc, _ = ops.conv_fwd(wrap(xd), wcl(inp.w).to(dev), None, 1, 1, stats="acc")
+            bnin = ops.BnAccInput(acc, N * H * W, _Bn(Co, dev), True)
+            return z, ops.bn_apply_acc(z, bnin, None, True), bnin.mean.clone()
+        if opt == "STATS|IN_BN":
+            g = torch.Generator().manual_seed(5)
+            w0 = wcl(torch.randn(Ci, Ci, 3, 3, generator=g) / math.sqrt(9 * Ci)).to(dev)
+            z1, acc1, _ = ops.conv_fwd(xd, w0, None, 1, 1, stats="acc")
+            bnin1 = ops.BnAccInput(acc1, N * H * W, _Bn(Ci, dev, seed=1), True, relu=True)
+            z2, acc2, _ = ops.conv_fwd(wrap(z1), wcl(inp.w).to(dev), None, 1, 1, stats="acc", in_bn=bnin1)
+            bnin2 = ops.BnAccInput(acc2, N * H * W, _Bn(Co, dev, seed=2), True)
+            return z2, ops.bn_apply_acc(z2, bnin2, None, True), bnin1.invstd.clone()
+        wbd = wcl(inp.wb).to(dev)
+        if opt == "RES":
+            return (ops.conv_dgrad(wrap(xd), wbd, (N, H, W, Co), 1, 1, residual=wrap(resd)),)
+        with_y = opt == "RES|BS_Y"
+        yb = torch.relu(ops.bn_apply(zbd, mean, invstd, gamma, beta, None, False) + r2.to(dev)) if with_y else None
+        dx, big, pad = banded(torch.zeros((N, H, W, Co), device=dev), dev, shape, SENTINEL) if band else \
+            (torch.empty((N, H, W, Co), device=dev), None, 0)
+        out = bnstat_acc(ops, shape, wrap(xd), wbd, wrap(resd) if with_y else None, dx, wrap(zbd), wrap(yb) if with_y else None,
+                         mean, invstd, gamma, None if with_y else beta)
+        if band:
+            assert untouched(big, pad, dx.numel()), f"{opt} {shape}: the launch wrote outside dx"
+        return (dx.clone(),) + out
+
+    plain, guarded = run(False), run(True)
+    for i, (a, b) in enumerate(zip(plain, guarded)):
+        assert torch.isfinite(b).all(), f"{opt} {shape}: result {i} picked up a NaN from beyond an input tensor"
+        assert torch.equal(a, b), f"{opt} {shape}: result {i} changes with what lies next to the inputs"
+
+
+@pytest.mark.parametrize("form", ["plain", "x_bn"])
+@pytest.mark.parametrize("shape", T.GUARD_WGRAD_CASES, ids=T.case_id)
+def test_weight_gradient_between_nan_bands(x6, dev, shape, form):
+    ops = x6
+    N, H, W, Ci, Co = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    xd = (torch.randn(N, H, W, Ci, generator=g) + 0.5).to(dev)
+    dyd = torch.randn(N, H, W, Co, generator=g).to(dev)
+    bn = _Bn(Ci, dev, seed=4)
+    x_bn = (torch.full((Ci,), 0.5, device=dev), torch.full((Ci,), 1.1, device=dev), bn.weight, bn.bias, True) if form == "x_bn" else None
+    w_like = wcl(torch.empty(Co, Ci, 3, 3)).to(dev)
+    need = ops.lib().buctd_conv3x3_wgrad_bf16x6_workspace(*shape)
+    ops.workspace(need, dev).fill_(0xFF)
+    plain = ops.conv_wgrad(xd, dyd, w_like, 1, 1, x_bn=x_bn)
+    ops.workspace(need, dev).fill_(0xFF)
+    out, big, pad = banded(wcl(torch.zeros(Co, Ci, 3, 3)).to(dev).permute(0, 2, 3, 1), dev, shape, SENTINEL)
+    out = out.permute(0, 3, 1, 2)          # logical [Co][Ci][3][3] over the physical [Co][3][3][Ci] inside the sentinel
+    got = ops.conv_wgrad(banded(xd, dev, shape)[0], banded(dyd, dev, shape)[0], w_like, 1, 1, out=out, accumulate=0, x_bn=x_bn)
+    assert untouched(big, pad, out.numel()), f"wgrad {shape}: the launch wrote outside dw"
+    assert torch.isfinite(got).all(), f"wgrad {shape}: picked up a NaN from beyond an operand"
+    assert torch.equal(got, plain), f"wgrad {shape}: the result changes with what lies next to the operands"

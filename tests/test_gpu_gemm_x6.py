@@ -7,11 +7,6 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
 def rel_err(got, ref):
     return (got.double().cpu() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
 

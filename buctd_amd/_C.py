@@ -76,6 +76,14 @@ class Wg3Conv(C.Structure):            # mirrors buctd_wg3_conv
                 [("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)])
 
 
+class MhaArgs(C.Structure):            # mirrors buctd_mha_args
+    _fields_ = ([(n, C.c_int) for n in ("B", "T", "h", "dh")] +
+                [(n, C.c_void_p) for n in ("q", "k", "v")] + [(n, C.c_int) for n in ("ldq", "ldk", "ldv")] +
+                [("out", C.c_void_p), ("ldo", C.c_int), ("lse", C.c_void_p), ("scale", C.c_float), ("p_drop", C.c_float),
+                 ("dout", C.c_void_p), ("lddo", C.c_int)] +
+                [(n, C.c_void_p) for n in ("dq", "dk", "dv")] + [(n, C.c_int) for n in ("lddq", "lddk", "lddv")])
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -225,6 +233,15 @@ SIGNATURES = {
     "buctd_mha_bwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _U64, _P, _P, _I, _P, _I, _P, _SZ, _P]),
     "buctd_mha_fwd_train_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P]),
     "buctd_mha_bwd_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
+    "buctd_mha_heads_fwd_supported": (_I, [_I, _I, _I]),
+    "buctd_mha_heads_fwd": (_I, [C.POINTER(MhaArgs), _P]),
+    "buctd_mha_heads_fwd_bf16x6": (_I, [C.POINTER(MhaArgs), _P]),
+    "buctd_mha_heads_train_supported": (_I, [_I, _I, _I]),
+    "buctd_mha_heads_fwd_train": (_I, [C.POINTER(MhaArgs), _U64, _P]),
+    "buctd_mha_heads_bwd_workspace": (_SZ, [_I, _I, _I]),
+    "buctd_mha_heads_bwd": (_I, [C.POINTER(MhaArgs), _U64, _P, _SZ, _P]),
+    "buctd_mha_heads_fwd_train_dseed": (_I, [C.POINTER(MhaArgs), _P, _P]),
+    "buctd_mha_heads_bwd_dseed": (_I, [C.POINTER(MhaArgs), _P, _P, _SZ, _P]),
     "buctd_nms_workspace": (_SZ, [_I]),
     "buctd_nms": (_I, [_P, _P, _P, _I, _I, _F, _P, _SZ, _P]),
     "buctd_cpu_nms": (_I, [_P, _I, _P, _F, _P, _P]),

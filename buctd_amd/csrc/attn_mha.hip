@@ -20,10 +20,23 @@
 #define MHA_BK 64
 #define MHA_VPM 2      // soft-max VALU instructions slotted behind each MFMA of the next tile's logits (mha_fwd_x6q_kernel)
 
-template <int DF>   // d / 16
-__global__ __launch_bounds__(512, 1) void mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                         const float* __restrict__ v, int T, int ldqk, int ldv,
-                                                         float scale, float* __restrict__ out, float* __restrict__ lse) {
+// General calling form (all kernels of this file that take MhaFwdArgs): head blockIdx.z of gridDim.z reads columns
+// [head * D, (head + 1) * D) of q, k, v - separate tensors, each with its own row stride - and writes the same columns of
+// out; lse is [B][h][T].  The packed one-head projection is the special case k = q + D, ldk = ldq.
+// TAIL: T is a multiple of 64 but not of 128 - the last workgroup owns 64 real query rows; its wavefronts 4-7 (whole
+// wavefronts, 16 rows each) read row 0 instead of rows past T and store nothing.  Key blocks are 64 rows: always whole.
+struct MhaFwdArgs {
+  const float* q; const float* k; const float* v;
+  float* out; float* lse;
+  int T, ldq, ldk, ldv, ldo;
+  float scale;
+};
+
+template <int DF, bool TAIL>   // d / 16
+__global__ __launch_bounds__(512, 1) void mha_fwd_kernel(MhaFwdArgs arg) {
+  const int T = arg.T, ldq = arg.ldq, ldk = arg.ldk, ldv = arg.ldv;
+  const float scale = arg.scale;
+  float* __restrict__ lse = arg.lse;
   constexpr int D = DF * 16, LDK = D + 8, LDV = MHA_BK + 8, LDP = MHA_BK + 8;
   constexpr int C4 = D / 4;                                  // float4 per token row
   constexpr int PL = (MHA_BK * C4 + 511) / 512;              // float4 per thread for one K (or V) block
@@ -33,17 +46,19 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_kernel(const float* __restrict
   float* Ps = Vt + D * LDV;                                  // [8 waves][16][LDP]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int i16 = lane & 15, g = lane >> 4;
-  const int b = blockIdx.y, q0 = blockIdx.x * MHA_BQ + wave * 16;
-  const float* qb = q + ((long)b * T) * ldqk;
-  const float* kb = k + ((long)b * T) * ldqk;
-  const float* vb = v + ((long)b * T) * ldv;
+  const int b = blockIdx.y, head = blockIdx.z, q0 = blockIdx.x * MHA_BQ + wave * 16;
+  const bool live = !TAIL || q0 < T;
+  const int qr = live ? q0 : 0;
+  const float* qb = arg.q + ((long)b * T) * ldq + head * D;
+  const float* kb = arg.k + ((long)b * T) * ldk + head * D;
+  const float* vb = arg.v + ((long)b * T) * ldv + head * D;
   float* Pw = Ps + wave * 16 * LDP;
 
   // Q fragment: lane (i16, g) holds Q[q0 + i16][16 m + 4 g + e], m < DF, e < 4  (pre-scaled)
   f32x4 qf[DF];
 #pragma unroll
   for (int m = 0; m < DF; ++m) {
-    qf[m] = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldqk + 16 * m + 4 * g);
+    qf[m] = *reinterpret_cast<const f32x4*>(qb + (long)(qr + i16) * ldq + 16 * m + 4 * g);
 #pragma unroll
     for (int e = 0; e < 4; ++e) qf[m][e] *= scale;
   }
@@ -61,7 +76,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_kernel(const float* __restrict
       const int id = t + 512 * p;
       const int row = id / C4, c4 = (id - row * C4) * 4;
       if (row < MHA_BK) {
-        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldqk + c4);
+        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldk + c4);
         vreg[p] = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + row) * ldv + c4);
       }
     }
@@ -142,13 +157,14 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_kernel(const float* __restrict
     }
   }
   // O / l : lane holds rows g*4 + r, column 16 n + i16
+  if (!live) return;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float inv = 1.f / lrow[r];
-    float* op = out + ((long)b * T + q0 + g * 4 + r) * (long)D;
+    float* op = arg.out + ((long)b * T + q0 + g * 4 + r) * (long)arg.ldo + head * D;
 #pragma unroll
     for (int n = 0; n < DF; ++n) op[16 * n + i16] = o[n][r] * inv;
-    if (lse && i16 == 0) lse[(long)b * T + q0 + g * 4 + r] = mrow[r] + __logf(lrow[r]);
+    if (lse && i16 == 0) lse[((long)b * gridDim.z + head) * T + q0 + g * 4 + r] = mrow[r] + __logf(lrow[r]);
   }
 }
 
@@ -195,11 +211,11 @@ __device__ __forceinline__ void mha_mma6(f32x4& acc, const mbf16x8 (&a)[3], cons
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
-template <int DF>
-__global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                            const float* __restrict__ v, int T, int ldqk, int ldv,
-                                                            float scale, float* __restrict__ out,
-                                                            float* __restrict__ lse) {
+template <int DF, bool TAIL>
+__global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
+  const int T = arg.T, ldq = arg.ldq, ldk = arg.ldk, ldv = arg.ldv;
+  const float scale = arg.scale;
+  float* __restrict__ lse = arg.lse;
   constexpr int D = DF * 16, LO = D * 2, RS = D * 6 + (((D * 6) % 64 == 32) ? 0 : 32), NK = (D + 31) / 32;
   constexpr int C4 = D / 4, PL = (MHA_BK * C4 + 511) / 512;
   extern __shared__ __attribute__((aligned(16))) unsigned char smx[];
@@ -207,10 +223,12 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(const float* __restr
   unsigned char* vt = smx + MHA_BK * RS;      // [64 keys][RS]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int i16 = lane & 15, g = lane >> 4;
-  const int b = blockIdx.y, q0 = blockIdx.x * MHA_BQ + wave * 16;
-  const float* qb = q + ((long)b * T) * ldqk;
-  const float* kb = k + ((long)b * T) * ldqk;
-  const float* vb = v + ((long)b * T) * ldv;
+  const int b = blockIdx.y, head = blockIdx.z, q0 = blockIdx.x * MHA_BQ + wave * 16;
+  const bool live = !TAIL || q0 < T;
+  const int qr = live ? q0 : 0;
+  const float* qb = arg.q + ((long)b * T) * ldq + head * D;
+  const float* kb = arg.k + ((long)b * T) * ldk + head * D;
+  const float* vb = arg.v + ((long)b * T) * ldv + head * D;
 
   // B operand of S^T: lane (query i16, group g) holds Q[q0 + i16][32 kk + 8 g .. +8] (zeros past d), pre-scaled
   mbf16x8 qq[NK][3];
@@ -220,8 +238,8 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(const float* __restr
     const int c0 = 32 * kk + 8 * g;
     float x[8];
     if (c0 < D) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldqk + c0);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldqk + c0 + 4);
+      const f32x4 a = *reinterpret_cast<const f32x4*>(qb + (long)(qr + i16) * ldq + c0);
+      const f32x4 c = *reinterpret_cast<const f32x4*>(qb + (long)(qr + i16) * ldq + c0 + 4);
       x[0] = a.x * s2; x[1] = a.y * s2; x[2] = a.z * s2; x[3] = a.w * s2;
       x[4] = c.x * s2; x[5] = c.y * s2; x[6] = c.z * s2; x[7] = c.w * s2;
     } else {
@@ -249,7 +267,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(const float* __restr
       const int id = t + 512 * p;
       const int row = id / C4, c4 = (id - row * C4) * 4;
       if (row < MHA_BK) {
-        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldqk + c4);
+        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldk + c4);
         vreg[p] = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + row) * ldv + c4);
       }
     }
@@ -353,11 +371,13 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(const float* __restr
   lrun += __shfl_xor(lrun, 16, 64);
   lrun += __shfl_xor(lrun, 32, 64);
   const float linv = 1.f / lrun;
-  if (lse && g == 0) lse[(long)b * T + q0 + i16] = (mrun + __builtin_amdgcn_logf(lrun)) * 0.69314718055994530942f;
+  if (!live) return;
+  if (lse && g == 0)
+    lse[((long)b * gridDim.z + head) * T + q0 + i16] = (mrun + __builtin_amdgcn_logf(lrun)) * 0.69314718055994530942f;
 #pragma unroll
   for (int rg = 0; rg < 4; ++rg) {
     const float fl = __shfl(linv, g * 4 + rg, 64);
-    float* op = out + ((long)b * T + q0 + g * 4 + rg) * (long)D;
+    float* op = arg.out + ((long)b * T + q0 + g * 4 + rg) * (long)arg.ldo + head * D;
 #pragma unroll
     for (int n = 0; n < DF; ++n) op[16 * n + i16] = o[n][rg] * fl;
   }
@@ -845,43 +865,73 @@ extern "C" int buctd_mha_fwd_supported(int T, int d) {
   return (T > 0 && T % MHA_BQ == 0 && d >= 16 && d <= 128 && d % 16 == 0) ? 1 : 0;
 }
 
-template <int DF>
-static int mha_launch(int B, int T, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                      float* out, float* lse, int x6, hipStream_t st) {
+extern "C" int buctd_mha_heads_fwd_supported(int T, int h, int dh) {
+  return (T > 0 && T % MHA_BK == 0 && h >= 1 && h <= 65535 && dh >= 16 && dh <= 128 && dh % 16 == 0) ? 1 : 0;
+}
+
+template <int DF, bool TAIL>
+static int mha_launch(int B, int h, const MhaFwdArgs& a, int x6, hipStream_t st) {
   static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
-  void (*fn)(const float*, const float*, const float*, int, int, int, float, float*, float*) =
-      x6 ? mha_fwd_x6_kernel<DF> : mha_fwd_kernel<DF>;
+  void (*fn)(MhaFwdArgs) = x6 ? mha_fwd_x6_kernel<DF, TAIL> : mha_fwd_kernel<DF, TAIL>;
   const size_t lds = x6 ? mha_x6_lds(DF * 16) : mha_lds(DF * 16);
   if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, attr_done[x6 ? 1 : 0], "buctd_mha_fwd")) return rc;
-  hipLaunchKernelGGL(fn, dim3(T / MHA_BQ, B), dim3(512), lds, st, q, k, v, T, ldqk, ldv, scale, out, lse);
+  hipLaunchKernelGGL(fn, dim3((a.T + MHA_BQ - 1) / MHA_BQ, B, h), dim3(512), lds, st, a);
   BUCTD_CHECK_LAUNCH("buctd_mha_fwd");
   return BUCTD_OK;
 }
 
-static int mha_run(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                   float* out, float* lse, int x6, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && B > 0, "buctd_mha_fwd: null pointer");
-  BUCTD_CHECK_ARG(buctd_mha_fwd_supported(T, d), "buctd_mha_fwd: unsupported shape T%d d%d (T %% 128 == 0, d %% 16 == 0, d <= 128)",
-                  T, d);
-  BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && ldqk % 4 == 0 && ldv % 4 == 0, "buctd_mha_fwd: row strides must be >= d and 16-byte aligned");
+// the general launcher: the one-head entry points below are its h = 1, ldk = ldq, ldo = d case
+static int mha_run(const buctd_mha_args& g, int x6, void* stream) {
+  BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.B > 0 && g.B <= 65535, "buctd_mha_fwd: null pointer or bad batch");
+  BUCTD_CHECK_ARG(buctd_mha_heads_fwd_supported(g.T, g.h, g.dh),
+                  "buctd_mha_fwd: unsupported shape T%d h%d dh%d (T %% 64 == 0, dh %% 16 == 0, dh <= 128)", g.T, g.h, g.dh);
+  const int hd = g.h * g.dh;
+  BUCTD_CHECK_ARG(g.ldq >= hd && g.ldk >= hd && g.ldv >= hd && g.ldo >= hd && g.ldq % 4 == 0 && g.ldk % 4 == 0 && g.ldv % 4 == 0,
+                  "buctd_mha_fwd: row strides must be >= h * dh and 16-byte aligned");
+  MhaFwdArgs a;
+  a.q = g.q; a.k = g.k; a.v = g.v; a.out = g.out; a.lse = g.lse;
+  a.T = g.T; a.ldq = g.ldq; a.ldk = g.ldk; a.ldv = g.ldv; a.ldo = g.ldo;
+  a.scale = g.scale;
   hipStream_t st = (hipStream_t)stream;
-  switch (d / 16) {
-#define MHA_CASE(n) case n: return mha_launch<n>(B, T, q, k, v, ldqk, ldv, scale, out, lse, x6, st);
+  const bool tail = g.T % MHA_BQ != 0;
+  switch (g.dh / 16) {
+#define MHA_CASE(n) case n: return tail ? mha_launch<n, true>(g.B, g.h, a, x6, st) : mha_launch<n, false>(g.B, g.h, a, x6, st);
     MHA_CASE(1) MHA_CASE(2) MHA_CASE(3) MHA_CASE(4) MHA_CASE(5) MHA_CASE(6) MHA_CASE(7) MHA_CASE(8)
 #undef MHA_CASE
   }
-  buctd_set_error("buctd_mha_fwd: no kernel for d=%d", d);
+  buctd_set_error("buctd_mha_fwd: no kernel for dh=%d", g.dh);
   return BUCTD_EINVAL;
+}
+
+static int mha_run1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
+                    float* out, float* lse, int x6, void* stream) {
+  BUCTD_CHECK_ARG(buctd_mha_fwd_supported(T, d), "buctd_mha_fwd: unsupported shape T%d d%d (T %% 128 == 0, d %% 16 == 0, d <= 128)",
+                  T, d);
+  buctd_mha_args g = {};
+  g.B = B; g.T = T; g.h = 1; g.dh = d;
+  g.q = q; g.k = k; g.v = v; g.ldq = ldqk; g.ldk = ldqk; g.ldv = ldv;
+  g.out = out; g.ldo = d; g.lse = lse; g.scale = scale;
+  return mha_run(g, x6, stream);
 }
 
 extern "C" int buctd_mha_fwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
                              float scale, float* out, float* lse, void* stream) {
-  return mha_run(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 0, stream);
+  return mha_run1(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 0, stream);
 }
 
 extern "C" int buctd_mha_fwd_bf16x6(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
                                     int ldv, float scale, float* out, float* lse, void* stream) {
-  return mha_run(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 1, stream);
+  return mha_run1(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 1, stream);
+}
+
+extern "C" int buctd_mha_heads_fwd(const buctd_mha_args* a, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd: null descriptor");
+  return mha_run(*a, 0, stream);
+}
+
+extern "C" int buctd_mha_heads_fwd_bf16x6(const buctd_mha_args* a, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd_bf16x6: null descriptor");
+  return mha_run(*a, 1, stream);
 }
 
 static int mha_x6_rs(int d) { return d * 6 + (((d * 6) % 64 == 32) ? 0 : 32); }

@@ -29,12 +29,23 @@
 // ---------------------------------------------------------------------------------------------------------- forward ----
 // mha_fwd_kernel of attn_mha.hip plus attention dropout on the probabilities that enter P V (the soft-max normaliser uses
 // the undropped ones) and the log-sum-exp row statistic for the backward.
-template <int DF, bool DSEED>
-__global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                               const float* __restrict__ v, int T, int ldqk, int ldv,
-                                                               float scale, float p_drop, SeedArg<DSEED> seed_arg,
-                                                               float* __restrict__ out, float* __restrict__ lse) {
+// General calling form (forward and backward): head blockIdx.z of H = gridDim.z works on columns [head D, (head + 1) D) of
+// q, k, v, out, dout, dq, dk, dv - separate tensors, each with its own row stride; lse and the row dots are [B][H][T]; the
+// dropout counter is the one of a materialised [B][H][T][T] tensor, ((b H + head) T + q) T + key.
+// TAIL: T is a multiple of 64 but not of 128 - wavefronts 4-7 of the last workgroup own no real rows: they read row 0
+// instead and store nothing.  The streamed blocks are 64 rows, always whole.
+struct MhaTrainFwdArgs {
+  const float* q; const float* k; const float* v;
+  float* out; float* lse;
+  int T, ldq, ldk, ldv, ldo;
+  float scale, p_drop;
+};
+
+template <int DF, bool DSEED, bool TAIL>
+__global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(MhaTrainFwdArgs arg, SeedArg<DSEED> seed_arg) {
   const uint64_t seed = load_seed(seed_arg);
+  const int T = arg.T, ldq = arg.ldq, ldk = arg.ldk, ldv = arg.ldv;
+  const float scale = arg.scale, p_drop = arg.p_drop;
   constexpr int D = DF * 16, LDK = D + 8, LDV = MT_BS + 8, LDP = MT_BS + 8;
   constexpr int C4 = D / 4;
   constexpr int PL = (MT_BS * C4 + 511) / 512;
@@ -44,17 +55,20 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __re
   float* Ps = Vt + D * LDV;                                  // [8 waves][16][LDP]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int i16 = lane & 15, g = lane >> 4;
-  const int b = blockIdx.y, q0 = blockIdx.x * MT_BO + wave * 16;
-  const float* qb = q + ((long)b * T) * ldqk;
-  const float* kb = k + ((long)b * T) * ldqk;
-  const float* vb = v + ((long)b * T) * ldv;
+  const int b = blockIdx.y, head = blockIdx.z, q0 = blockIdx.x * MT_BO + wave * 16;
+  const bool live = !TAIL || q0 < T;
+  const int qr = live ? q0 : 0;
+  const long bh = (long)b * gridDim.z + head;
+  const float* qb = arg.q + ((long)b * T) * ldq + head * D;
+  const float* kb = arg.k + ((long)b * T) * ldk + head * D;
+  const float* vb = arg.v + ((long)b * T) * ldv + head * D;
   float* Pw = Ps + wave * 16 * LDP;
   const float inv_keep = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
 
   f32x4 qf[DF];
 #pragma unroll
   for (int m = 0; m < DF; ++m) {
-    qf[m] = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldqk + 16 * m + 4 * g);
+    qf[m] = *reinterpret_cast<const f32x4*>(qb + (long)(qr + i16) * ldq + 16 * m + 4 * g);
 #pragma unroll
     for (int e = 0; e < 4; ++e) qf[m][e] *= scale;
   }
@@ -72,7 +86,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __re
       const int id = t + 512 * p;
       const int row = id / C4, c4 = (id - row * C4) * 4;
       if (row < MT_BS) {
-        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldqk + c4);
+        kreg[p] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + row) * ldk + c4);
         vreg[p] = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + row) * ldv + c4);
       }
     }
@@ -136,7 +150,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __re
       for (int r = 0; r < 4; ++r) {
         float pv = s[nb][r];
         if (p_drop > 0.f) {
-          const uint64_t idx = ((uint64_t)b * T + (uint64_t)(q0 + g * 4 + r)) * (uint64_t)T + (uint64_t)(k0 + nb * 16 + i16);
+          const uint64_t idx = ((uint64_t)bh * T + (uint64_t)(q0 + g * 4 + r)) * (uint64_t)T + (uint64_t)(k0 + nb * 16 + i16);
           pv *= keep_scale(seed, idx, p_drop, inv_keep);
         }
         Pw[(g * 4 + r) * LDP + nb * 16 + i16] = pv;
@@ -156,35 +170,39 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_train_kernel(const float* __re
       }
     }
   }
+  if (!live) return;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float inv = 1.f / lrow[r];
-    float* op = out + ((long)b * T + q0 + g * 4 + r) * (long)D;
+    float* op = arg.out + ((long)b * T + q0 + g * 4 + r) * (long)arg.ldo + head * D;
 #pragma unroll
     for (int n = 0; n < DF; ++n) op[16 * n + i16] = o[n][r] * inv;
-    if (i16 == 0) lse[(long)b * T + q0 + g * 4 + r] = mrow[r] + __logf(lrow[r]);
+    if (i16 == 0) arg.lse[bh * T + q0 + g * 4 + r] = mrow[r] + __logf(lrow[r]);
   }
 }
 
 // --------------------------------------------------------------------------------------------------------- backward ----
-// D[row] = dO[row] . O[row]  (one wavefront per row of d <= 128 floats)
-__global__ __launch_bounds__(256) void mha_rowdot_kernel(const float* __restrict__ a, const float* __restrict__ bmat, long rows,
-                                                         int d, float* __restrict__ out) {
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+// D[b][head][t] = dO[b][t][head cols] . O[b][t][head cols]  (one wavefront per row of d <= 128 floats)
+__global__ __launch_bounds__(256) void mha_rowdot_kernel(const float* __restrict__ a, int lda, const float* __restrict__ bmat,
+                                                         int ldb, long items, int T, int h, int d, float* __restrict__ out) {
+  const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);     // (b h + head) T + t
+  if (item >= items) return;
+  const long bhd = item / T;
+  const long row = (bhd / h) * T + (item - bhd * T);
+  const int c0 = (int)(bhd % h) * d;
   const int lane = threadIdx.x & 63;
   float s = 0.f;
-  for (int c = lane; c < d; c += 64) s += a[row * d + c] * bmat[row * d + c];
+  for (int c = lane; c < d; c += 64) s += a[row * lda + c0 + c] * bmat[row * ldb + c0 + c];
   s = wave_sum(s);
-  if (lane == 0) out[row] = s;
+  if (lane == 0) out[item] = s;
 }
 
 struct MhaBwdArgs {
-  const float* q; const float* k; const float* v;     // [B][T] rows, strides ldqk (q, k) / ldv
-  const float* dout;                                   // [B][T][d]
-  const float* lse; const float* dvec;                 // [B][T]
-  float* dq; float* dk; float* dv;                     // strides lddqk (dq, dk) / lddv
-  int T, ldqk, ldv, lddqk, lddv;
+  const float* q; const float* k; const float* v;     // [B][T] rows, strides ldq / ldk / ldv
+  const float* dout;                                   // [B][T] rows, stride lddo
+  const float* lse; const float* dvec;                 // [B][H][T]
+  float* dq; float* dk; float* dv;                     // strides lddq / lddk / lddv
+  int T, ldq, ldk, ldv, lddo, lddq, lddk, lddv;
   float scale, p_drop;
   uint64_t seed;
 };
@@ -197,7 +215,7 @@ __device__ __forceinline__ MhaBwdArgs with_seed(const DevSeeded<MhaBwdArgs>& d) 
   return a;
 }
 
-template <int DF, bool DKV, bool DSEED>
+template <int DF, bool DKV, bool DSEED, bool TAIL>
 __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, DSEED> args) {
   const MhaBwdArgs& p = with_seed(args);
   constexpr int D = DF * 16, LDK = D + 8;
@@ -209,21 +227,25 @@ __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, 
   float* St = Y2s + MT_BS * LDK;         // [64][2]     dKV: (lse, D) of the streamed queries
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int i16 = lane & 15, g = lane >> 4;
-  const int b = blockIdx.y, T = p.T;
+  const int b = blockIdx.y, head = blockIdx.z, T = p.T;
   const int own0 = blockIdx.x * MT_BO + wave * 16;
-  const long brow = (long)b * T;
+  const bool live = !TAIL || own0 < T;
+  const int ownr = live ? own0 : 0;
+  const long brow = (long)b * T;                       // first row of the image in q, k, v, dout, dq, dk, dv
+  const long srow0 = ((long)b * gridDim.z + head) * T; // first row of (image, head) in lse / dvec and in the mask counter
+  const int hc = head * D;
   const float inv_keep = p.p_drop > 0.f ? 1.f / (1.f - p.p_drop) : 1.f;
   // stream sources
-  const float* y1 = DKV ? p.q : p.k;
-  const float* y2 = DKV ? p.dout : p.v;
-  const int ldy1 = p.ldqk, ldy2 = DKV ? D : p.ldv;
+  const float* y1 = (DKV ? p.q : p.k) + hc;
+  const float* y2 = (DKV ? p.dout : p.v) + hc;
+  const int ldy1 = DKV ? p.ldq : p.ldk, ldy2 = DKV ? p.lddo : p.ldv;
   const float y1scale = DKV ? p.scale : 1.f;
 
   // own operands in registers: lane (i16, g) holds X[own0 + i16][16 m + 4 g + e]
   f32x4 x1[DF], x2[DF];
   {
-    const float* s1 = (DKV ? p.k : p.q) + (brow + own0 + i16) * (long)p.ldqk;
-    const float* s2 = DKV ? p.v + (brow + own0 + i16) * (long)p.ldv : p.dout + (brow + own0 + i16) * (long)D;
+    const float* s1 = (DKV ? p.k : p.q) + (brow + ownr + i16) * (long)(DKV ? p.ldk : p.ldq) + hc;
+    const float* s2 = (DKV ? p.v : p.dout) + (brow + ownr + i16) * (long)(DKV ? p.ldv : p.lddo) + hc;
 #pragma unroll
     for (int m = 0; m < DF; ++m) {
       x1[m] = *reinterpret_cast<const f32x4*>(s1 + 16 * m + 4 * g);
@@ -237,8 +259,8 @@ __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, 
   // role dQ: the row statistics belong to the own column i16
   float lse_own = 0.f, d_own = 0.f;
   if (!DKV) {
-    lse_own = p.lse[brow + own0 + i16];
-    d_own = p.dvec[brow + own0 + i16];
+    lse_own = p.lse[srow0 + ownr + i16];
+    d_own = p.dvec[srow0 + ownr + i16];
   }
   f32x4 acc1[DF], acc2[DKV ? DF : 1];     // dQ: acc1 = dQ;  dKV: acc1 = dV, acc2 = dK
 #pragma unroll
@@ -258,7 +280,7 @@ __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, 
         r2[q] = *reinterpret_cast<const f32x4*>(y2 + (brow + s0 + row) * (long)ldy2 + c4);
       }
     }
-    if (DKV && t < 2 * MT_BS) rst = (t & 1) ? p.dvec[brow + s0 + (t >> 1)] : p.lse[brow + s0 + (t >> 1)];
+    if (DKV && t < 2 * MT_BS) rst = (t & 1) ? p.dvec[srow0 + s0 + (t >> 1)] : p.lse[srow0 + s0 + (t >> 1)];
   };
   auto store_y = [&]() {
 #pragma unroll
@@ -311,7 +333,7 @@ __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, 
         const float dq_ = DKV ? St[(tb * 16 + 4 * g + r) * 2 + 1] : d_own;
         const float pr = __expf(t1[r] - lq);
         float z = 1.f;
-        if (p.p_drop > 0.f) z = keep_scale(p.seed, ((uint64_t)brow + (uint64_t)qi) * (uint64_t)T + (uint64_t)ki, p.p_drop, inv_keep);
+        if (p.p_drop > 0.f) z = keep_scale(p.seed, ((uint64_t)srow0 + (uint64_t)qi) * (uint64_t)T + (uint64_t)ki, p.p_drop, inv_keep);
         e_pd[r] = pr * z;
         e_ds[r] = pr * (z * t2[r] - dq_);
       }
@@ -333,18 +355,19 @@ __global__ __launch_bounds__(512, 1) void mha_bwd_kernel(SeededArgs<MhaBwdArgs, 
     }
   }
   // accumulators: lane holds own rows own0 + 4g + r, column 16 n + i16
+  if (!live) return;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const long row = brow + own0 + 4 * g + r;
     if (DKV) {
 #pragma unroll
       for (int n = 0; n < DF; ++n) {
-        p.dv[row * p.lddv + 16 * n + i16] = acc1[n][r];
-        p.dk[row * p.lddqk + 16 * n + i16] = acc2[n][r];
+        p.dv[row * p.lddv + hc + 16 * n + i16] = acc1[n][r];
+        p.dk[row * p.lddk + hc + 16 * n + i16] = acc2[n][r];
       }
     } else {
 #pragma unroll
-      for (int n = 0; n < DF; ++n) p.dq[row * p.lddqk + 16 * n + i16] = acc1[n][r] * p.scale;
+      for (int n = 0; n < DF; ++n) p.dq[row * p.lddq + hc + 16 * n + i16] = acc1[n][r] * p.scale;
     }
   }
 }
@@ -359,47 +382,63 @@ extern "C" int buctd_mha_train_supported(int T, int d) {
   return (T > 0 && T % MT_BO == 0 && d >= 16 && d <= 128 && d % 16 == 0) ? 1 : 0;
 }
 
+extern "C" int buctd_mha_heads_train_supported(int T, int h, int dh) {
+  return (T > 0 && T % MT_BS == 0 && h >= 1 && h <= 65535 && dh >= 16 && dh <= 128 && dh % 16 == 0) ? 1 : 0;
+}
+
 template <typename F>
 static int mt_attr(F fn, unsigned char (&done)[BUCTD_MAX_DEVICES], const char* who) {
   return buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, done, who);
 }
 
-template <int DF, bool DSEED>
-static int mt_fwd_launch(int B, int T, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                         float p_drop, SeedArg<DSEED> seed, float* out, float* lse, hipStream_t st) {
+static dim3 mt_grid(int B, int h, int T) { return dim3((T + MT_BO - 1) / MT_BO, B, h); }
+
+template <int DF, bool DSEED, bool TAIL>
+static int mt_fwd_launch(int B, int h, const MhaTrainFwdArgs& a, SeedArg<DSEED> seed, hipStream_t st) {
   static unsigned char done[BUCTD_MAX_DEVICES] = {0};
-  const int rc = mt_attr(mha_fwd_train_kernel<DF, DSEED>, done, "buctd_mha_fwd_train");
+  const int rc = mt_attr(mha_fwd_train_kernel<DF, DSEED, TAIL>, done, "buctd_mha_fwd_train");
   if (rc) return rc;
-  hipLaunchKernelGGL((mha_fwd_train_kernel<DF, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_fwd_lds(DF * 16), st, q, k, v, T,
-                     ldqk, ldv, scale, p_drop, seed, out, lse);
+  hipLaunchKernelGGL((mha_fwd_train_kernel<DF, DSEED, TAIL>), mt_grid(B, h, a.T), dim3(512), mt_fwd_lds(DF * 16), st, a, seed);
   BUCTD_CHECK_LAUNCH("buctd_mha_fwd_train");
   return BUCTD_OK;
 }
 
-template <int DF, bool DSEED>
-static int mt_bwd_launch(int B, int T, const SeededArgs<MhaBwdArgs, DSEED>& a, hipStream_t st) {
+template <int DF, bool DSEED, bool TAIL>
+static int mt_bwd_launch(int B, int h, int T, const SeededArgs<MhaBwdArgs, DSEED>& a, hipStream_t st) {
   static unsigned char done[2][BUCTD_MAX_DEVICES] = {{0}};
-  int rc = mt_attr(mha_bwd_kernel<DF, false, DSEED>, done[0], "buctd_mha_bwd");
+  int rc = mt_attr(mha_bwd_kernel<DF, false, DSEED, TAIL>, done[0], "buctd_mha_bwd");
   if (rc) return rc;
-  rc = mt_attr(mha_bwd_kernel<DF, true, DSEED>, done[1], "buctd_mha_bwd");
+  rc = mt_attr(mha_bwd_kernel<DF, true, DSEED, TAIL>, done[1], "buctd_mha_bwd");
   if (rc) return rc;
-  hipLaunchKernelGGL((mha_bwd_kernel<DF, true, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
+  hipLaunchKernelGGL((mha_bwd_kernel<DF, true, DSEED, TAIL>), mt_grid(B, h, T), dim3(512), mt_bwd_lds(DF * 16), st, a);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dK, dV)");
-  hipLaunchKernelGGL((mha_bwd_kernel<DF, false, DSEED>), dim3(T / MT_BO, B), dim3(512), mt_bwd_lds(DF * 16), st, a);
+  hipLaunchKernelGGL((mha_bwd_kernel<DF, false, DSEED, TAIL>), mt_grid(B, h, T), dim3(512), mt_bwd_lds(DF * 16), st, a);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dQ)");
   return BUCTD_OK;
 }
 
+static bool mt_strides_ok(const buctd_mha_args& g) {
+  const int hd = g.h * g.dh;
+  return g.ldq >= hd && g.ldk >= hd && g.ldv >= hd && g.ldo >= hd && g.ldq % 4 == 0 && g.ldk % 4 == 0 && g.ldv % 4 == 0;
+}
+
+// the general launchers: the one-head entry points below are their h = 1, ldk = ldq, ldo = lddo = d case
 template <bool DSEED>
-static int mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                         float p_drop, SeedArg<DSEED> seed, float* out, float* lse, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && lse && B > 0 && seed_ok(seed), "buctd_mha_fwd_train: null pointer");
-  BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "buctd_mha_fwd_train: unsupported shape T%d d%d", T, d);
-  BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && ldqk % 4 == 0 && ldv % 4 == 0 && p_drop >= 0.f && p_drop < 1.f,
-                  "buctd_mha_fwd_train: bad strides or dropout probability");
+static int mha_fwd_train(const buctd_mha_args& g, SeedArg<DSEED> seed, void* stream) {
+  BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.lse && g.B > 0 && g.B <= 65535 && seed_ok(seed),
+                  "buctd_mha_fwd_train: null pointer or bad batch");
+  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_fwd_train: unsupported shape T%d h%d dh%d", g.T,
+                  g.h, g.dh);
+  BUCTD_CHECK_ARG(mt_strides_ok(g) && g.p_drop >= 0.f && g.p_drop < 1.f, "buctd_mha_fwd_train: bad strides or dropout probability");
+  MhaTrainFwdArgs a;
+  a.q = g.q; a.k = g.k; a.v = g.v; a.out = g.out; a.lse = g.lse;
+  a.T = g.T; a.ldq = g.ldq; a.ldk = g.ldk; a.ldv = g.ldv; a.ldo = g.ldo;
+  a.scale = g.scale; a.p_drop = g.p_drop;
   hipStream_t st = (hipStream_t)stream;
-  switch (d / 16) {
-#define MT_CASE(n) case n: return mt_fwd_launch<n, DSEED>(B, T, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, st);
+  const bool tail = g.T % MT_BO != 0;
+  switch (g.dh / 16) {
+#define MT_CASE(n) \
+  case n: return tail ? mt_fwd_launch<n, DSEED, true>(g.B, g.h, a, seed, st) : mt_fwd_launch<n, DSEED, false>(g.B, g.h, a, seed, st);
     MT_CASE(1) MT_CASE(2) MT_CASE(3) MT_CASE(4) MT_CASE(5) MT_CASE(6) MT_CASE(7) MT_CASE(8)
 #undef MT_CASE
   }
@@ -407,39 +446,75 @@ static int mha_fwd_train(int B, int T, int d, const float* q, const float* k, co
 }
 
 template <bool DSEED>
-static int mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
-                   const float* dout, const float* lse, float scale, float p_drop, SeedArg<DSEED> seed, float* dq, float* dk,
-                   int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && B > 0 && seed_ok(seed), "buctd_mha_bwd: null pointer");
-  BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "buctd_mha_bwd: unsupported shape T%d d%d", T, d);
-  BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && lddqk >= d && lddv >= d && ldqk % 4 == 0 && ldv % 4 == 0,
+static int mha_bwd(const buctd_mha_args& g, SeedArg<DSEED> seed, void* workspace, size_t workspace_bytes, void* stream) {
+  BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.dout && g.lse && g.dq && g.dk && g.dv && g.B > 0 && g.B <= 65535 && seed_ok(seed),
+                  "buctd_mha_bwd: null pointer or bad batch");
+  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_bwd: unsupported shape T%d h%d dh%d", g.T, g.h, g.dh);
+  const int hd = g.h * g.dh;
+  BUCTD_CHECK_ARG(mt_strides_ok(g) && g.lddo >= hd && g.lddo % 4 == 0 && g.lddq >= hd && g.lddk >= hd && g.lddv >= hd,
                   "buctd_mha_bwd: bad strides");
-  if (!workspace || workspace_bytes < buctd_mha_bwd_workspace(B, T)) {
-    buctd_set_error("buctd_mha_bwd: workspace %zu bytes < required %zu", workspace_bytes, buctd_mha_bwd_workspace(B, T));
+  const size_t need = buctd_mha_heads_bwd_workspace(g.B, g.h, g.T);
+  if (!workspace || workspace_bytes < need) {
+    buctd_set_error("buctd_mha_bwd: workspace %zu bytes < required %zu", workspace_bytes, need);
     return BUCTD_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  const long rows = (long)B * T;
-  hipLaunchKernelGGL(mha_rowdot_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, dout, out, rows, d, (float*)workspace);
+  const long items = (long)g.B * g.h * g.T;
+  hipLaunchKernelGGL(mha_rowdot_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, g.dout, g.lddo, g.out, g.ldo, items,
+                     g.T, g.h, g.dh, (float*)workspace);
   BUCTD_CHECK_LAUNCH("buctd_mha_bwd (row dots)");
   SeededArgs<MhaBwdArgs, DSEED> args;
   MhaBwdArgs& a = kernel_args(args);
-  a.q = q; a.k = k; a.v = v; a.dout = dout; a.lse = lse; a.dvec = (const float*)workspace;
-  a.dq = dq; a.dk = dk; a.dv = dv;
-  a.T = T; a.ldqk = ldqk; a.ldv = ldv; a.lddqk = lddqk; a.lddv = lddv;
-  a.scale = scale; a.p_drop = p_drop;
+  a.q = g.q; a.k = g.k; a.v = g.v; a.dout = g.dout; a.lse = g.lse; a.dvec = (const float*)workspace;
+  a.dq = g.dq; a.dk = g.dk; a.dv = g.dv;
+  a.T = g.T; a.ldq = g.ldq; a.ldk = g.ldk; a.ldv = g.ldv; a.lddo = g.lddo;
+  a.lddq = g.lddq; a.lddk = g.lddk; a.lddv = g.lddv;
+  a.scale = g.scale; a.p_drop = g.p_drop;
   if constexpr (DSEED) {
     a.seed = 0;
     args.seedp = seed;
   } else {
     a.seed = seed;
   }
-  switch (d / 16) {
-#define MT_CASE(n) case n: return mt_bwd_launch<n, DSEED>(B, T, args, st);
+  const bool tail = g.T % MT_BO != 0;
+  switch (g.dh / 16) {
+#define MT_CASE(n) \
+  case n: return tail ? mt_bwd_launch<n, DSEED, true>(g.B, g.h, g.T, args, st) : mt_bwd_launch<n, DSEED, false>(g.B, g.h, g.T, args, st);
     MT_CASE(1) MT_CASE(2) MT_CASE(3) MT_CASE(4) MT_CASE(5) MT_CASE(6) MT_CASE(7) MT_CASE(8)
 #undef MT_CASE
   }
   return BUCTD_EINVAL;
+}
+
+static int mt_one_head(buctd_mha_args& g, const char* who, int B, int T, int d, const float* q, const float* k, const float* v,
+                       int ldqk, int ldv, float scale, float p_drop, float* out, float* lse) {
+  BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "%s: unsupported shape T%d d%d", who, T, d);
+  g = buctd_mha_args{};
+  g.B = B; g.T = T; g.h = 1; g.dh = d;
+  g.q = q; g.k = k; g.v = v; g.ldq = ldqk; g.ldk = ldqk; g.ldv = ldv;
+  g.out = out; g.ldo = d; g.lse = lse; g.scale = scale; g.p_drop = p_drop;
+  return BUCTD_OK;
+}
+
+template <bool DSEED>
+static int mha_fwd_train1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
+                          float p_drop, SeedArg<DSEED> seed, float* out, float* lse, void* stream) {
+  buctd_mha_args g;
+  if (const int rc = mt_one_head(g, "buctd_mha_fwd_train", B, T, d, q, k, v, ldqk, ldv, scale, p_drop, out, lse)) return rc;
+  return mha_fwd_train<DSEED>(g, seed, stream);
+}
+
+template <bool DSEED>
+static int mha_bwd1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
+                    const float* dout, const float* lse, float scale, float p_drop, SeedArg<DSEED> seed, float* dq, float* dk,
+                    int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream) {
+  buctd_mha_args g;
+  if (const int rc = mt_one_head(g, "buctd_mha_bwd", B, T, d, q, k, v, ldqk, ldv, scale, p_drop, const_cast<float*>(out),
+                                 const_cast<float*>(lse)))
+    return rc;
+  g.dout = dout; g.lddo = d;
+  g.dq = dq; g.dk = dk; g.dv = dv; g.lddq = lddqk; g.lddk = lddqk; g.lddv = lddv;
+  return mha_bwd<DSEED>(g, seed, workspace, workspace_bytes, stream);
 }
 
 /* softmax(scale q k^T) -> dropout(p_drop, seed) -> . v for one head, fused (no T x T tensor), train mode: also writes the
@@ -447,28 +522,48 @@ static int mha_bwd(int B, int T, int d, const float* q, const float* k, const fl
  * Reference: nn.MultiheadAttention in transpose_h.py:192-197 (forward of the training step). */
 extern "C" int buctd_mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
                                    float scale, float p_drop, uint64_t seed, float* out, float* lse, void* stream) {
-  return mha_fwd_train<false>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
+  return mha_fwd_train1<false>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
 }
 extern "C" int buctd_mha_fwd_train_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
                                          int ldv, float scale, float p_drop, const uint64_t* seed, float* out, float* lse,
                                          void* stream) {
-  return mha_fwd_train<true>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
+  return mha_fwd_train1<true>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
 }
 
 /* backward of buctd_mha_fwd_train: dq, dk (rows of stride lddqk), dv (stride lddv) from q, k, v, the forward's out and lse,
  * and dout [B][T][d].  workspace: B * T floats (the row dots dout . out). */
 extern "C" size_t buctd_mha_bwd_workspace(int B, int T) { return (size_t)B * T * sizeof(float); }
+extern "C" size_t buctd_mha_heads_bwd_workspace(int B, int h, int T) { return (size_t)B * h * T * sizeof(float); }
 extern "C" int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
                              const float* out, const float* dout, const float* lse, float scale, float p_drop, uint64_t seed,
                              float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  return mha_bwd<false>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
-                        workspace_bytes, stream);
+  return mha_bwd1<false>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
+                         workspace_bytes, stream);
 }
 extern "C" int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
                                    const float* out, const float* dout, const float* lse, float scale, float p_drop,
                                    const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  return mha_bwd<true>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
-                       workspace_bytes, stream);
+  return mha_bwd1<true>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
+                        workspace_bytes, stream);
+}
+
+/* the general form (include/buctd_hip.h: buctd_mha_args) */
+extern "C" int buctd_mha_heads_fwd_train(const buctd_mha_args* a, uint64_t seed, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd_train: null descriptor");
+  return mha_fwd_train<false>(*a, seed, stream);
+}
+extern "C" int buctd_mha_heads_fwd_train_dseed(const buctd_mha_args* a, const uint64_t* seed, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd_train_dseed: null descriptor");
+  return mha_fwd_train<true>(*a, seed, stream);
+}
+extern "C" int buctd_mha_heads_bwd(const buctd_mha_args* a, uint64_t seed, void* workspace, size_t workspace_bytes, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_bwd: null descriptor");
+  return mha_bwd<false>(*a, seed, workspace, workspace_bytes, stream);
+}
+extern "C" int buctd_mha_heads_bwd_dseed(const buctd_mha_args* a, const uint64_t* seed, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_bwd_dseed: null descriptor");
+  return mha_bwd<true>(*a, seed, workspace, workspace_bytes, stream);
 }

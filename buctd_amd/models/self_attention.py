@@ -28,7 +28,7 @@ class ScaledDotProductAttention(nn.Module):
         self.fc_o = nn.Linear(h * d_v, d_model)
         self.dropout = torch.nn.Dropout(dropout)  # holds p; the mask is generated inside the softmax kernel
         self.d_model, self.d_k, self.d_v, self.h = d_model, d_k, d_v, h
-        self.fused = True  # take the fused narrow-contraction kernels whenever the shape allows (tests toggle this)
+        self.fused = True  # take the fused kernels (narrow-contraction or general) whenever the shape allows (tests toggle this)
         _init_linear(self)
 
     def forward(self, queries, keys, values, attention_mask=None, attention_weights=None):
@@ -43,6 +43,17 @@ class ScaledDotProductAttention(nn.Module):
                                              self.training)
             return self.fc_o(out)
         q = self.fc_q(queries)
+        if self.fused and self.d_k == self.d_v and keys.shape[1] == queries.shape[1] \
+                and ops.mha_train_ok(queries.shape[1], self.h * self.d_k, self.h):
+            # several heads, a wide condition, q / k / v projections of one feature map (SelfDAModule): the general fused
+            # kernels of the TransPose encoder on separate q, k, v - no T x T matrix either
+            p_eff = float(self.dropout.p) if self.training else 0.0
+            needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+            if p_eff == 0.0 and not needs_grad and ops.mha_fused_ok(queries.shape[1], self.h * self.d_k, self.h):
+                out = ops.mha_fwd(q, v, h=self.h, k=k)
+            else:
+                out = ops.FusedMHA.apply(q, v, float(self.dropout.p), self.training, self.h, k)
+            return self.fc_o(out)
         out = ops.PositionAttention.apply(q, k, v, self.h, float(self.dropout.p), self.training)
         return self.fc_o(out)
 

@@ -35,13 +35,13 @@ class MultiheadAttention(nn.Module):
         needs_grad = torch.is_grad_enabled() and (qk.requires_grad or v.requires_grad)
         if p_eff == 0.0 and not needs_grad and ops.mha_fused_ok(qk.shape[1], self.embed_dim, self.num_heads):
             # inference (BASELINE config C5): flash-style fused attention, no T x T matrix in HBM
-            out = ops.mha_fwd(qk, v)
+            out = ops.mha_fwd(qk, v) if self.num_heads == 1 else ops.mha_fwd(qk, v, h=self.num_heads)
         elif ops.mha_train_ok(qk.shape[1], self.embed_dim, self.num_heads):
             # training: fused in both directions - forward with in-kernel attention dropout, flash-style backward
-            out = ops.FusedMHA.apply(qk, v, float(self.dropout), self.training)
+            out = ops.FusedMHA.apply(qk, v, float(self.dropout), self.training, self.num_heads)
         else:
-            # shapes the fused kernels do not take (T not a multiple of 128, several heads): materialised soft-max with
-            # the same counter-hash dropout
+            # shapes the fused kernels do not take (T not a multiple of 64, head width not a multiple of 16):
+            # materialised soft-max with the same counter-hash dropout
             out = ops.PositionAttention.apply(qk, None, v, self.num_heads, float(self.dropout), self.training)
         return self.out_proj(out)
 

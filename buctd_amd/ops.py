@@ -2455,18 +2455,70 @@ class PositionAttention(torch.autograd.Function):
         return dq, (None if packed else dkk), dvv, None, None, None
 
 
+def _head_width(d, h):
+    d, h = int(d), int(h)
+    return d // h if h >= 1 and d % h == 0 else 0
+
+
 def mha_fused_ok(T, d, h=1):
-    """True when the fused flash-style self-attention forward (attn_mha.hip) covers this shape."""
-    return h == 1 and lib().buctd_mha_fwd_supported(int(T), int(d)) == 1
+    """True when the fused flash-style self-attention forward (attn_mha.hip) covers T tokens of total width d in h heads."""
+    return _memo(("mhafw", int(T), int(d), int(h)),
+                 lambda: lib().buctd_mha_heads_fwd_supported(int(T), int(h), _head_width(d, h)) == 1)
 
 
-def mha_fwd(qk, v, scale=None):
-    """softmax(scale * q k^T) v for one head without the T x T matrix.  qk [B, T, 2d] = q | k side by side (the packed
-    nn.MultiheadAttention input projection), v [B, T, d] -> [B, T, d].  Inference / no-dropout path."""
+def _mha_rows(t, T, name):
+    """-> (tensor, row stride) of a [B, T, >= h*dh] operand of the general attention form: unit stride along the
+    channels, rows ld floats apart, images T * ld apart (a contiguous tensor or a channel slice of one); anything else
+    is copied"""
+    if t.dtype != torch.float32:
+        raise _C.BuctdHipError(f"{name}: fp32 expected, got {t.dtype}")
+    ld = t.stride(1)
+    if t.stride(2) != 1 or t.stride(0) != T * ld or ld % 4 or t.data_ptr() % 16 or ld < t.shape[2]:
+        t = t.contiguous()
+        ld = t.shape[2]
+    return t, ld
+
+
+def _mha_desc(q, k, v, h, scale):
+    """buctd_mha_args of the forward operands -> (descriptor, tensors to keep alive, B, T, hd); k=None: q holds q | k"""
+    B, T = q.shape[0], q.shape[1]
+    hd = v.shape[2]
+    q, ldq = _mha_rows(q, T, "mha q")
+    v, ldv = _mha_rows(v, T, "mha v")
+    if k is None:
+        if q.shape[2] != 2 * hd:
+            raise _C.BuctdHipError("mha: the packed form holds q | k, twice the width of v")
+        k, ldk, kp = q, ldq, q.data_ptr() + 4 * hd
+    else:
+        k, ldk = _mha_rows(k, T, "mha k")
+        kp = k.data_ptr()
+    if (k is not q and (q.shape[2] != hd or k.shape[2] != hd)) or k.shape[1] != T or v.shape[1] != T or hd % h:
+        raise _C.BuctdHipError("mha: q, k, v must have the same token count and width (Tq == Tk, dk == dv)")
+    a = _C.MhaArgs()
+    a.B, a.T, a.h, a.dh = B, T, h, hd // h
+    a.q, a.k, a.v = ptr(q), kp, ptr(v)
+    a.ldq, a.ldk, a.ldv = ldq, ldk, ldv
+    a.scale = (1.0 / math.sqrt(hd // h)) if scale is None else float(scale)
+    return a, (q, k, v), B, T, hd
+
+
+def mha_fwd(qk, v, scale=None, h=1, k=None):
+    """softmax(scale * q k^T) v per head without the T x T matrix.  Inference / no-dropout path.
+    Packed form (k=None): qk [B, T, 2d] = q | k side by side (the packed nn.MultiheadAttention input projection), v [B, T, d]
+    -> [B, T, d].  Unpacked form: qk = q, k, v [B, T, d] separate tensors (contiguous, or channel slices of wider ones).
+    h heads of width d / h; scale defaults to 1 / sqrt(d / h)."""
+    B, T = qk.shape[0], qk.shape[1]
+    d = v.shape[2]
+    if k is not None or h != 1 or lib().buctd_mha_fwd_supported(T, d) != 1:
+        a, keep, B, T, d = _mha_desc(qk, k, v, int(h), scale)
+        out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
+        a.out, a.ldo = ptr(out), d
+        fn = lib().buctd_mha_heads_fwd_bf16x6 if _conv_math["mode"] == "bf16x6" and _MHA_X6 else lib().buctd_mha_heads_fwd
+        check(fn(C.byref(a), stream_ptr()), "mha_fwd")
+        return out
     _f32(qk, "mha qk")
     _f32(v, "mha v")
-    B, T, two_d = qk.shape
-    d = two_d // 2
+    two_d = qk.shape[2]
     out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
     kptr = C.c_void_p(qk.data_ptr() + 4 * d)
     # default math mode: both products in bf16x6 (fp32 class on the bf16 matrix cores); fp32 mode: exact fp32 MFMA
@@ -2487,49 +2539,49 @@ def mha_fwd(qk, v, scale=None):
 
 def mha_train_ok(T, d, h=1):
     """True when the fused training attention (attn_mha_train.hip: forward with dropout + lse, flash-style backward) covers
-    this shape."""
-    return h == 1 and _memo(("mhatr", int(T), int(d)), lambda: lib().buctd_mha_train_supported(int(T), int(d)) == 1)
+    T tokens of total width d in h heads."""
+    return _memo(("mhatr", int(T), int(d), int(h)),
+                 lambda: lib().buctd_mha_heads_train_supported(int(T), int(h), _head_width(d, h)) == 1)
 
 
 class FusedMHA(torch.autograd.Function):
-    """softmax(q k^T / sqrt(d)) -> dropout -> . v for ONE head without the T x T matrix, forward and backward (reference
-    nn.MultiheadAttention inside transpose_h.py:192-197, training).  qk [B, T, 2d] = q | k side by side (the packed input
-    projection), v [B, T, d] -> [B, T, d]; the backward returns the packed gradient d(q | k) and dv."""
+    """softmax(q k^T / sqrt(dh)) -> dropout -> . v per head without the T x T matrix, forward and backward (reference
+    nn.MultiheadAttention inside transpose_h.py:192-197, training; self_attention.py:74-86).
+    Packed form (k=None): qk [B, T, 2d] = q | k side by side (the packed input projection), v [B, T, d] -> [B, T, d]; the
+    backward returns the packed gradient d(q | k) and dv.  Unpacked form: qk = q, k, v [B, T, d] separate tensors.
+    h heads of width d / h; the dropout mask is the one PositionAttention draws for the same seed."""
 
     @staticmethod
-    def forward(ctx, qk, v, p_drop, training):
-        qk, v = _contig(qk), _contig(v)
-        _f32(qk, "mha qk")
-        _f32(v, "mha v")
-        B, T, two_d = qk.shape
-        d = two_d // 2
-        scale = 1.0 / math.sqrt(d)
+    def forward(ctx, qk, v, p_drop, training, h=1, k=None):
+        a, keep, B, T, d = _mha_desc(qk, k, v, int(h), None)
         p_eff = float(p_drop) if training else 0.0
         seed = next_seed()
         out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
-        lse = torch.empty((B, T), dtype=torch.float32, device=qk.device)
-        fn, s = _seeded("buctd_mha_fwd_train", seed)
-        check(fn(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], scale, p_eff, s, ptr(out),
-                 ptr(lse), stream_ptr()), "mha_fwd_train")
-        ctx.meta = (scale, p_eff, seed)
-        ctx.save_for_backward(qk, v, out, lse)
+        lse = torch.empty((B, int(h), T), dtype=torch.float32, device=qk.device)
+        a.out, a.ldo, a.lse, a.p_drop = ptr(out), d, ptr(lse), p_eff
+        fn, s = _seeded("buctd_mha_heads_fwd_train", seed)
+        check(fn(C.byref(a), s, stream_ptr()), "mha_fwd_train")
+        ctx.meta = (int(h), p_eff, seed, k is None)
+        ctx.save_for_backward(*keep, out, lse)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        scale, p_eff, seed = ctx.meta
-        qk, v, out, lse = ctx.saved_tensors
-        dout = _contig(dout)
-        B, T, two_d = qk.shape
-        d = two_d // 2
-        dqk = torch.empty_like(qk)
-        dv = torch.empty_like(v)
-        ws = workspace(lib().buctd_mha_bwd_workspace(B, T), qk.device)
-        fn, s = _seeded("buctd_mha_bwd", seed)
-        check(fn(B, T, d, ptr(qk), C.c_void_p(qk.data_ptr() + 4 * d), ptr(v), two_d, v.shape[2], ptr(out), ptr(dout), ptr(lse),
-                 scale, p_eff, s, ptr(dqk), C.c_void_p(dqk.data_ptr() + 4 * d), two_d, ptr(dv), dv.shape[2], ptr(ws),
-                 ws.numel(), stream_ptr()), "mha_bwd")
-        return dqk, dv, None, None
+        h, p_eff, seed, packed = ctx.meta
+        q, k, v, out, lse = ctx.saved_tensors
+        a, _, B, T, d = _mha_desc(q, None if packed else k, v, h, None)
+        dout, lddo = _mha_rows(dout, T, "mha dout")
+        dq = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        dk = dq if packed else torch.empty(k.shape, dtype=torch.float32, device=q.device)
+        dv = torch.empty(v.shape, dtype=torch.float32, device=q.device)
+        a.out, a.ldo, a.lse, a.p_drop = ptr(out), d, ptr(lse), p_eff
+        a.dout, a.lddo = ptr(dout), lddo
+        a.dq, a.dk, a.dv = ptr(dq), (dq.data_ptr() + 4 * d if packed else ptr(dk)), ptr(dv)
+        a.lddq, a.lddk, a.lddv = dq.shape[2], dk.shape[2], dv.shape[2]
+        ws = workspace(_memo(("mhabw", B, h, T), lambda: lib().buctd_mha_heads_bwd_workspace(B, h, T)), q.device)
+        fn, s = _seeded("buctd_mha_heads_bwd", seed)
+        check(fn(C.byref(a), s, ptr(ws), ws.numel(), stream_ptr()), "mha_bwd")
+        return dq, dv, None, None, None, (None if packed else dk)
 
 
 def attn_smallqk_ok(T, d_in, C, h=1):

@@ -614,6 +614,35 @@ int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, con
                         const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* General calling form of the fused attention above: h heads and q, k, v, out (dq, dk, dv) as separate tensors, each with
+ * its own row stride in floats (self_attention.py:74-86 with h heads; nn.MultiheadAttention with N_HEAD > 1).  Head i reads
+ * columns [i dh, (i + 1) dh) of q, k, v and writes the same columns of out / dq / dk / dv; lse is [B][h][T].  The packed
+ * one-head projection is the special case h = 1, k = q + dh, ldk = ldq.  Attention dropout draws the mask of
+ * buctd_softmax_dropout_fwd on a [B][h][T][T] tensor: counter ((b h + head) T + query) T + key.
+ * T % 64 == 0 (a last half block of query / key rows is masked), dh % 16 == 0, dh <= 128, Tq == Tk, dk == dv.
+ * Every pointer 16-byte aligned, ldq / ldk / ldv / lddo multiples of 4.  Fields a pass does not use may be NULL / 0. */
+typedef struct buctd_mha_args {
+  int B, T, h, dh;
+  const float* q; const float* k; const float* v;
+  int ldq, ldk, ldv;
+  float* out; int ldo;          /* forward: written; backward: the forward's result */
+  float* lse;                   /* [B][h][T]; eval forward: NULL ok; train forward: written; backward: read */
+  float scale, p_drop;          /* p_drop: train forward and backward only */
+  const float* dout; int lddo;  /* backward */
+  float* dq; float* dk; float* dv;
+  int lddq, lddk, lddv;
+} buctd_mha_args;
+int buctd_mha_heads_fwd_supported(int T, int h, int dh);
+int buctd_mha_heads_fwd(const buctd_mha_args* a, void* stream);         /* exact fp32 MFMA */
+int buctd_mha_heads_fwd_bf16x6(const buctd_mha_args* a, void* stream);  /* bf16x6, as buctd_mha_fwd_bf16x6 */
+int buctd_mha_heads_train_supported(int T, int h, int dh);
+int buctd_mha_heads_fwd_train(const buctd_mha_args* a, uint64_t seed, void* stream);
+size_t buctd_mha_heads_bwd_workspace(int B, int h, int T);              /* B h T floats: the row dots dout . out */
+int buctd_mha_heads_bwd(const buctd_mha_args* a, uint64_t seed, void* workspace, size_t workspace_bytes, void* stream);
+int buctd_mha_heads_fwd_train_dseed(const buctd_mha_args* a, const uint64_t* seed, void* stream);
+int buctd_mha_heads_bwd_dseed(const buctd_mha_args* a, const uint64_t* seed, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* ------------------------------------------------------- sample pipeline --- */
 /* Person crop of the per-sample pipeline (dataset/JointsDataset.py:287-294): cv2.warpAffine(img_u8, M, (w, h),
  * flags=INTER_LINEAR) restated bit for bit (OpenCV's fixed-point bilinear, BORDER_CONSTANT 0), fused with

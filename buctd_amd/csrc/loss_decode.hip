@@ -51,6 +51,161 @@ extern "C" int buctd_joints_mse(const float* pred, const float* gt, const float*
   return BUCTD_OK;
 }
 
+// ----------------------------------------------------------- joints OHKM MSE ----
+// JointsOHKMMSELoss (reference lib/core/loss.py:140-182): the mean over the samples of the mean of each sample's topk
+// largest per-joint losses.  The selection needs every per-joint sum first, so the heat-maps are read twice:
+//   rows   - one workgroup per (n,k) heat-map: l[n][k] = 0.5/HW w^2 sum (p-g)^2, accumulated in fp64 (the pass is
+//            HBM-bound, the fp64 adds are free) and rounded to fp32 once;
+//   select - one wavefront per sample ranks its K values in registers (rank = values that are greater + equal values at
+//            a lower joint index: ties go to the lower index), writes the per-(n,k) gradient scale - 0 for the joints
+//            that were not selected - and sums the selected losses in a fixed order (no atomics);
+//   grad   - one workgroup per heat-map: scale * (p-g), or zeros without reading p and g where the scale is 0.
+//
+// A heat-map starts at float offset row*HW, which is 16-byte aligned only when that is a multiple of 4: `head` scalar
+// elements lead up to the first aligned one, `nv` float4s follow, the rest is a scalar tail.  vec == 0 (a base pointer
+// off 16 bytes): everything goes through the scalar loop.
+struct RowSplit {
+  int head, nv, tail0, nscalar;
+};
+__device__ __forceinline__ RowSplit row_split(long base, int HW, int vec) {
+  RowSplit r;
+  r.head = vec ? min(HW, (int)((4 - (base & 3)) & 3)) : 0;
+  r.nv = vec ? (HW - r.head) >> 2 : 0;
+  r.tail0 = r.head + 4 * r.nv;
+  r.nscalar = r.head + (HW - r.tail0);
+  return r;
+}
+// i-th scalar element of the row: the head first, then the tail
+__device__ __forceinline__ int row_scalar_index(const RowSplit& r, int i) { return i < r.head ? i : r.tail0 + (i - r.head); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void ohkm_rows_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                        const float* __restrict__ w, int HW, int vec,
+                                                        float* __restrict__ l) {
+  __shared__ double sm[4];
+  const long row = blockIdx.x;
+  const long base = row * HW;
+  const RowSplit rs = row_split(base, HW, vec);
+  double s = 0.0;
+  const f32x4* pv = reinterpret_cast<const f32x4*>(pred + base + rs.head);
+  const f32x4* gv = reinterpret_cast<const f32x4*>(gt + base + rs.head);
+#pragma unroll 2
+  for (int i = threadIdx.x; i < rs.nv; i += 256) {
+    const f32x4 p = pv[i], g = gv[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double d = (double)p[j] - (double)g[j];
+      s += d * d;
+    }
+  }
+  for (int i = threadIdx.x; i < rs.nscalar; i += 256) {
+    const int e = row_scalar_index(rs, i);
+    const double d = (double)pred[base + e] - (double)gt[base + e];
+    s += d * d;
+  }
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double wt = w ? (double)w[row] : 1.0;
+    l[row] = (float)(0.5 / (double)HW * (wt * wt) * (((sm[0] + sm[1]) + sm[2]) + sm[3]));
+  }
+}
+
+// One workgroup of 16 wavefronts; wavefront v takes the samples v, v + 16, ...  gcoef = gscale / (HW * N * topk).
+__global__ __launch_bounds__(1024) void ohkm_select_kernel(const float* __restrict__ l, const float* __restrict__ w,
+                                                           int N, int K, int topk, double gcoef,
+                                                           float* __restrict__ scale, float* __restrict__ loss) {
+  __shared__ double sm[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double s = 0.0;
+  for (int n = wave; n < N; n += 16) {  // uniform over the wavefront
+    const long row = (long)n * K + lane;
+    const float v = lane < K ? l[row] : 0.f;
+    const float key = v != v ? INFINITY : v;  // torch.topk's order: a NaN is the largest value
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+      const float o = __shfl(key, j, 64);
+      rank += (o > key || (o == key && j < lane)) ? 1 : 0;
+    }
+    const bool sel = lane < K && rank < topk;
+    if (lane < K) {
+      const double wt = w ? (double)w[row] : 1.0;
+      scale[row] = sel ? (float)(wt * wt * gcoef) : 0.f;
+    }
+    s += wave_sum_f64(sel ? (double)v : 0.0);
+  }
+  if (lane == 0) sm[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 16; ++i) t += sm[i];
+    loss[0] = (float)(t / ((double)N * (double)topk));
+  }
+}
+
+__global__ __launch_bounds__(256) void ohkm_grad_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                        const float* __restrict__ scale, int HW, int vec,
+                                                        float* __restrict__ grad) {
+  const long row = blockIdx.x;
+  const long base = row * HW;
+  const RowSplit rs = row_split(base, HW, vec);
+  const float s = scale[row];  // uniform over the workgroup
+  f32x4* dv = reinterpret_cast<f32x4*>(grad + base + rs.head);
+  if (s == 0.f) {  // not selected (or weight 0): zeros, pred and gt are not read
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < rs.nv; i += 256) dv[i] = z;
+    for (int i = threadIdx.x; i < rs.nscalar; i += 256) grad[base + row_scalar_index(rs, i)] = 0.f;
+    return;
+  }
+  const f32x4* pv = reinterpret_cast<const f32x4*>(pred + base + rs.head);
+  const f32x4* gv = reinterpret_cast<const f32x4*>(gt + base + rs.head);
+#pragma unroll 2
+  for (int i = threadIdx.x; i < rs.nv; i += 256) dv[i] = (pv[i] - gv[i]) * s;
+  for (int i = threadIdx.x; i < rs.nscalar; i += 256) {
+    const int e = row_scalar_index(rs, i);
+    grad[base + e] = (pred[base + e] - gt[base + e]) * s;
+  }
+}
+
+extern "C" size_t buctd_joints_ohkm_mse_workspace(int N, int K) {
+  return N > 0 && K > 0 ? 2 * (size_t)N * (size_t)K * sizeof(float) : 0;
+}
+extern "C" int buctd_joints_ohkm_mse(const float* pred, const float* gt, const float* w, int N, int K, int HW, int topk,
+                                     float* loss, float* grad, float gscale, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  BUCTD_CHECK_ARG(pred && gt && loss && N > 0 && K > 0 && HW > 0, "buctd_joints_ohkm_mse: bad argument");
+  BUCTD_CHECK_ARG(K <= BUCTD_OHKM_MAX_JOINTS, "buctd_joints_ohkm_mse: K = %d exceeds the limit of %d joints", K,
+                  BUCTD_OHKM_MAX_JOINTS);
+  BUCTD_CHECK_ARG(topk >= 1 && topk <= K, "buctd_joints_ohkm_mse: topk = %d is outside 1..K = %d", topk, K);
+  BUCTD_CHECK_ARG((long)N * K <= 0x7fffffffL, "buctd_joints_ohkm_mse: N * K = %ld heat-maps exceed the grid limit",
+                  (long)N * K);
+  const size_t need = buctd_joints_ohkm_mse_workspace(N, K);
+  if (!workspace || workspace_bytes < need) {
+    buctd_set_error("buctd_joints_ohkm_mse: workspace %zu bytes < required %zu", workspace_bytes, need);
+    return BUCTD_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* l = (float*)workspace;
+  float* scale = l + (size_t)N * K;
+  const int vec = (((uintptr_t)pred | (uintptr_t)gt | (uintptr_t)grad) & 15) == 0;
+  hipLaunchKernelGGL(ohkm_rows_kernel, dim3(N * K), dim3(256), 0, st, pred, gt, w, HW, vec, l);
+  BUCTD_CHECK_LAUNCH("buctd_joints_ohkm_mse(rows)");
+  const double gcoef = (double)gscale / ((double)HW * (double)N * (double)topk);
+  hipLaunchKernelGGL(ohkm_select_kernel, dim3(1), dim3(1024), 0, st, (const float*)l, w, N, K, topk, gcoef, scale, loss);
+  BUCTD_CHECK_LAUNCH("buctd_joints_ohkm_mse(select)");
+  if (grad) {
+    hipLaunchKernelGGL(ohkm_grad_kernel, dim3(N * K), dim3(256), 0, st, pred, gt, (const float*)scale, HW, vec, grad);
+    BUCTD_CHECK_LAUNCH("buctd_joints_ohkm_mse(grad)");
+  }
+  return BUCTD_OK;
+}
+
 // ------------------------------------------------------------ argmax decode ----
 // First-index arg-max of one row h[0..HW) over a 256-thread block (numpy argmax order); the result is valid in thread 0.
 __device__ __forceinline__ void block_argmax_256(const float* __restrict__ h, int HW, float& best_out, int& bi_out,

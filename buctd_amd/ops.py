@@ -1410,6 +1410,19 @@ def joints_mse(pred, gt, w, want_grad, gscale=1.0):
     return loss, grad
 
 
+def joints_ohkm_mse(pred, gt, w, topk, want_grad, gscale=1.0):
+    """JointsOHKMMSELoss: the mean over samples of each sample's `topk` largest per-joint losses; the gradient is zero
+    for the joints that were not selected (ties: the lower joint index).  Selection runs on the device: no host read."""
+    N, K = pred.shape[0], pred.shape[1]
+    HW = pred.numel() // (N * K)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    grad = torch.empty_like(pred) if want_grad else None
+    ws = workspace(lib().buctd_joints_ohkm_mse_workspace(N, K), pred.device)
+    check(lib().buctd_joints_ohkm_mse(ptr(pred), ptr(gt), ptr(w), N, K, HW, int(topk), ptr(loss), ptr(grad), gscale,
+                                      ptr(ws), ws.numel(), stream_ptr()), "joints_ohkm_mse")
+    return loss, grad
+
+
 def argmax_decode(hm, refine=False, preds_out=None):
     """refine: also return the quarter-pixel offsets of get_final_preds' POST_PROCESS step ([N,K,2]).
     preds_out: a pinned host tensor [N,K,2] the kernel writes the coordinates into directly (the GPU maps pinned memory)."""
@@ -2787,3 +2800,18 @@ class JointsMSE(torch.autograd.Function):
         if grad is None:
             return None, None, None
         return scale(grad, dl.reshape(1).contiguous()), None, None
+
+
+class JointsOHKMMSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, w, topk):
+        loss, grad = joints_ohkm_mse(pred, gt, w, topk, want_grad=pred.requires_grad)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dl):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None
+        return scale(grad, dl.reshape(1).contiguous()), None, None, None

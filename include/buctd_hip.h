@@ -432,6 +432,19 @@ int buctd_layernorm_bwd(const float* dy, const float* x, const float* mean, cons
  * pred/gt are [N][K][HW] (NCHW heatmaps), w is [N][K] (NULL: weights 1). workspace: N*K floats. */
 int buctd_joints_mse(const float* pred, const float* gt, const float* w, int N, int K, int HW, float* loss,
                      float* grad, float gscale, void* workspace, size_t workspace_bytes, void* stream);
+/* JointsOHKMMSELoss (core/loss.py:140-182), online hard key-point mining: per-joint loss
+ *   l[n][k] = 0.5/HW * w[n][k]^2 * sum_hw (p-g)^2 ;  S_n = the topk joints of sample n with the largest l[n][.] ;
+ *   loss = 1/(N*topk) * sum_n sum_{k in S_n} l[n][k] ;
+ *   grad (NULL ok) = gscale * [k in S_n] * w^2 (p-g) / (HW*N*topk): exactly 0 for joints that were not selected.
+ * Ties are broken towards the lower joint index (the loss does not depend on the rule, only the gradient does); a NaN
+ * l ranks above every number, as in torch.topk, so exactly topk joints of every sample are selected.
+ * pred/gt are [N][K][HW], w is [N][K] (NULL: weights 1).  1 <= topk <= K and K <= BUCTD_OHKM_MAX_JOINTS (one wavefront
+ * ranks a sample) - anything else returns BUCTD_EINVAL.  workspace: buctd_joints_ohkm_mse_workspace(N, K) bytes (l and
+ * the per-joint gradient scale).  Three launches (two without grad), no atomics: the result is deterministic. */
+#define BUCTD_OHKM_MAX_JOINTS 64
+size_t buctd_joints_ohkm_mse_workspace(int N, int K);
+int buctd_joints_ohkm_mse(const float* pred, const float* gt, const float* w, int N, int K, int HW, int topk, float* loss,
+                          float* grad, float gscale, void* workspace, size_t workspace_bytes, void* stream);
 /* get_max_preds (core/inference.py:19-47): first-index argmax per [N*K] row of length H*W;
  * preds[row] = (x, y) zeroed where maxval <= 0. */
 int buctd_argmax_decode(const float* hm, int rows, int H, int W, float* preds, float* maxvals, int32_t* idx,

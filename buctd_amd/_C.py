@@ -214,6 +214,7 @@ SIGNATURES = {
     "buctd_argmax_decode": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "buctd_warp_affine_norm": (_I, [_P, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "buctd_cond_render_into": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _SZ, _P]),
+    "buctd_cond_geometry": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
     "buctd_mha_fwd_supported": (_I, [_I, _I]),
     "buctd_mha_fwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P]),

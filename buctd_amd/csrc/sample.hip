@@ -87,3 +87,69 @@ extern "C" int buctd_warp_affine_norm(const buctd_warp_item* items_device, int B
   BUCTD_CHECK_LAUNCH("buctd_warp_affine_norm");
   return BUCTD_OK;
 }
+
+// Condition key points of a generative-sampling train batch (JointsDataset.py:257-259, 293-295): what
+// DeviceSamplePipeline.geometry does to cond_joints on the host, for poses that buctd_synthesize_pose left on the
+// device.  One thread per (sample, joint).  flip: fliplr_joints (utils/transforms.py:61-75) - x = W - x - 1, the
+// left/right exchange of joints and visibilities, joints * joints_vis (so a "missed" joint (0, 0) comes back as
+// (W - 1, 0) times its visibility, like in the reference); then the crop affine where vis[., 0] > 0.  Every float64
+// product and sum is rounded on its own (__dmul_rn / __dadd_rn / __dsub_rn: never contracted into an fma).
+struct CondGeomParams {
+  const double* synth;           // [B][K][3]
+  const double* vis;             // [B][K][3]
+  const buctd_warp_item* items;  // [B]: flip, W, m
+  const int* pair;               // [K], -1 = no partner
+  int B, K;
+  double* out_joints;            // [B][K][3]
+  double* out_vis;               // [B][K][3]
+  float* out_trunc;              // [B][K][2]
+};
+
+__global__ __launch_bounds__(256) void cond_geometry_kernel(CondGeomParams p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.B * p.K) return;
+  const int b = i / p.K, j = i - b * p.K;
+  const buctd_warp_item* it = p.items + b;
+  const int flip = it->flip;
+  int src = j;
+  if (flip) {
+    const int q = p.pair[j];
+    if (q >= 0 && q < p.K) src = q;
+  }
+  const double* s = p.synth + ((long)b * p.K + src) * 3;
+  const double* v = p.vis + ((long)b * p.K + src) * 3;
+  double x = s[0], y = s[1], z = s[2];
+  const double v0 = v[0], v1 = v[1], v2 = v[2];
+  if (flip) {
+    x = __dsub_rn(__dsub_rn((double)it->W, x), 1.0);
+    x = __dmul_rn(x, v0);
+    y = __dmul_rn(y, v1);
+    z = __dmul_rn(z, v2);
+  }
+  if (v0 > 0.0) {
+    const double tx = __dadd_rn(__dadd_rn(__dmul_rn(it->m[0], x), __dmul_rn(it->m[1], y)), it->m[2]);
+    const double ty = __dadd_rn(__dadd_rn(__dmul_rn(it->m[3], x), __dmul_rn(it->m[4], y)), it->m[5]);
+    x = tx;
+    y = ty;
+  }
+  double* oj = p.out_joints + (long)i * 3;
+  double* ov = p.out_vis + (long)i * 3;
+  oj[0] = x; oj[1] = y; oj[2] = z;
+  ov[0] = v0; ov[1] = v1; ov[2] = v2;
+  p.out_trunc[(long)i * 2] = (float)trunc(x);        // np.array(kpts).astype(int) of JointsDataset.py:521, as float32
+  p.out_trunc[(long)i * 2 + 1] = (float)trunc(y);
+}
+
+extern "C" int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd_warp_item* items_device,
+                                   const int* pair_device, int B, int K, double* out_joints, double* out_vis,
+                                   float* out_trunc, void* stream) {
+  BUCTD_CHECK_ARG(synth && cond_vis && items_device && pair_device && out_joints && out_vis && out_trunc && B > 0 &&
+                      K > 0 && K <= 32 && B < (1 << 20),
+                  "buctd_cond_geometry: bad argument (K <= 32)");
+  CondGeomParams p;
+  p.synth = synth; p.vis = cond_vis; p.items = items_device; p.pair = pair_device; p.B = B; p.K = K;
+  p.out_joints = out_joints; p.out_vis = out_vis; p.out_trunc = out_trunc;
+  hipLaunchKernelGGL(cond_geometry_kernel, dim3(ceil_div((long)B * K, 256)), dim3(256), 0, (hipStream_t)stream, p);
+  BUCTD_CHECK_LAUNCH("buctd_cond_geometry");
+  return BUCTD_OK;
+}

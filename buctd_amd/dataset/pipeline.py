@@ -11,6 +11,11 @@ IterativeRefiner chains conditional top-down passes without touching disk: the r
 and hands the predictions over through the results json (scripts/test/test_BUCTD_COAM_gen_sample.sh:21,
 lib/dataset/dataloader.py:454-508): prediction k -> box from its key points (+ margin, clipped) -> center / scale ->
 new crop + re-rendered condition -> prediction k+1, with the rescoring of dataloader.py:596-612.
+
+Generative sampling (DATASET.SYNTHESIS_POSE, JointsDataset.py:165-215): in train mode the condition is a pose synthesized
+from the ground truth, fresh for every sample.  DeviceSamplePipeline.__call__ draws it for the whole batch with one
+buctd_synthesize_pose launch, takes it through flip and crop affine with buctd_cond_geometry and renders it - the pose
+never leaves the device between the synthesis and the network input.
 """
 import ctypes as C
 import math
@@ -22,7 +27,12 @@ import torch
 from .. import ops
 from .._C import check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
-from ..utils.transforms import affine_transform, fliplr_joints, get_affine_transform
+from ..utils.transforms import _swap_table, affine_transform, fliplr_joints, get_affine_transform
+from .pose_synthesis import synthesize_pose_batch
+
+_M64 = (1 << 64) - 1
+NO_CONDITION = ("Training with empirical sampling is not possible without providing 'cond_kpts'; "
+                "please train with generative sampling (DATASET.SYNTHESIS_POSE=True)")
 
 
 class _WarpItem(C.Structure):
@@ -51,7 +61,73 @@ def box_from_keypoints(kp, margin, img_w, img_h):
     return [xmin, ymin, xmax - xmin, ymax - ymin]
 
 
+def synthesis_area(cond):
+    """cond [B, K, 3] -> [B]: width * height of the box around the non-zero condition coordinates
+    (JointsDataset.py:204-210), every record at once."""
+    cond = np.asarray(cond, dtype=np.float64)
+    xs, ys = cond[:, :, 0], cond[:, :, 1]
+    nx, ny = xs != 0, ys != 0
+    if not (nx.any(1) & ny.any(1)).all():
+        raise ValueError("pose synthesis: a condition without a non-zero x or y coordinate has no area")
+    w = np.where(nx, xs, -np.inf).max(1) - np.where(nx, xs, np.inf).min(1)
+    h = np.where(ny, ys, -np.inf).max(1) - np.where(ny, ys, np.inf).min(1)
+    return w * h
+
+
+def pad_near_joints(near, num_joints):
+    """near: per record the neighbours' key points in any shape that reshapes to [M_b, K, 3] (JointsDataset.py:212).
+    Returns [B, M, K, 3] with M the batch's largest M_b, absent neighbours as zeros (visibility 0: the form
+    synthesize_pose_batch takes), or None when no record has a neighbour."""
+    per = [np.asarray(n, dtype=np.float64).reshape(-1, num_joints, 3) for n in near]
+    m = max((n.shape[0] for n in per), default=0)
+    if m == 0:
+        return None
+    out = np.zeros((len(per), m, num_joints, 3), dtype=np.float64)
+    for b, n in enumerate(per):
+        out[b, :n.shape[0]] = n
+    return out
+
+
+def target_centres(joints, stride):
+    """joints [B, K, >=2] float64 crop coordinates -> float32 [B, K, 3]: per joint a coordinate that the target kernel's
+    (int)(v / stride + 0.5f) maps to the reference's heat-map centre mu = int(j / stride + 0.5) (see render())."""
+    joints = np.asarray(joints, dtype=np.float64)
+    jt = np.zeros(joints.shape[:2] + (3,), dtype=np.float32)
+    for a in (0, 1):
+        mu = (joints[:, :, a] / stride[a] + 0.5).astype(int)
+        jt[:, :, a] = np.where(mu < 0, mu - 1, mu) * stride[a]
+    return jt
+
+
+def trunc_condition(cond):
+    """cond [B, K, >=2] float64 -> float32 [B, K, 2]: np.array(kpts).astype(int) of JointsDataset.py:521 as floats."""
+    return np.ascontiguousarray(np.trunc(np.asarray(cond, dtype=np.float64)[:, :, :2]).astype(np.float32))
+
+
+def batch_seed(seed, call):
+    """64-bit synthesis seed of call number `call` of a pipeline seeded with `seed` (splitmix64 finaliser: seeds of
+    consecutive calls share no counter sequence of the generator in csrc/synth.hip)."""
+    z = ((int(seed) & _M64) * 0x9E3779B97F4A7C15 + int(call) + 1) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 class DeviceSamplePipeline:
+    """Batched sample pipeline.  pipe(records, aug=None, seed=None) -> (input, target, target_weight, meta).
+
+    Generative sampling: with is_train, MODEL.CONDITIONAL_TOPDOWN and DATASET.SYNTHESIS_POSE the condition of every
+    record is synthesized on the device (one launch per batch; person index = batch index; num_overlap 0; `seed`, or
+    a 64-bit value from the pipeline's seed and a call counter when seed is None: two calls differ, two pipelines with
+    the same seed repeat each other).  A record without 'cond_joints' takes joints_3d / joints_3d_vis as its condition
+    (JointsDataset.py:165-167); records carry 'near_joints' (anything that reshapes to [M, K, 3]; may be empty).  On
+    this path meta['cond_joints'] / meta['cond_joints_vis'] are float64 DEVICE tensors (crop coordinates) and
+    meta['synth_joints'] is the synthesized pose in image coordinates, on the device as well; nothing is copied back.
+    If any record of the batch has use_bu_bbox=True its crop box depends on the synthesized pose: the batch then takes
+    a host fallback - one copy of the synthesized poses to the host, then geometry() and render() as without synthesis
+    (same result, slower; meta['cond_joints'] / ['cond_joints_vis'] are host tensors there).  With is_train=False the
+    flag changes nothing.  Without the flag a conditional train pipeline refuses records that lack 'cond_joints'."""
+
     def __init__(self, cfg, flip_pairs=(), upper_body_ids=(), kpt_colors=None, mean=(0.485, 0.456, 0.406),
                  std=(0.229, 0.224, 0.225), is_train=False, seed=0):
         self.cfg = cfg
@@ -79,6 +155,11 @@ class DeviceSamplePipeline:
         self.std = np.asarray(std, dtype=np.float32)
         self.np_rng = np.random.RandomState(seed)
         self.py_rng = random.Random(seed)
+        self.synthesis_pose = bool(getattr(ds, "SYNTHESIS_POSE", False))
+        self.dataset = getattr(ds, "DATASET", None)
+        self.seed = int(seed)
+        self.synth_calls = 0
+        self._pair_dev = {}
 
     # ---- host-side scalar geometry (reference expressions, float64) -----------------------------------------
     def half_body_transform(self, joints, joints_vis):
@@ -116,17 +197,42 @@ class DeviceSamplePipeline:
         flip = self.flip and self.py_rng.random() <= 0.5
         return center, scale, rot, flip
 
-    def geometry(self, rec, aug=None):
+    def condition(self, rec):
+        """(cond_joints, cond_joints_vis, has_cond) of a record as float64 copies.  A conditional train pipeline gives a
+        record without 'cond_joints' its own joints (JointsDataset.py:165-169) - under DATASET.SYNTHESIS_POSE only."""
+        joints, joints_vis = rec["joints_3d"], rec["joints_3d_vis"]
+        if "cond_joints" in rec:
+            if self.synthesizes and isinstance(rec["cond_joints"], dict):
+                raise ValueError("pose synthesis needs one condition per record: 'cond_joints' is a dict of conditions")
+            return (np.array(rec["cond_joints"], dtype=np.float64).copy(),
+                    np.array(rec["cond_joints_vis"], dtype=np.float64).copy(), True)
+        if self.conditional and self.is_train:
+            if not self.synthesis_pose:
+                raise ValueError(NO_CONDITION)
+            return np.array(joints, dtype=np.float64).copy(), np.array(joints_vis, dtype=np.float64).copy(), True
+        return np.zeros_like(joints, dtype=np.float64), np.zeros_like(joints_vis, dtype=np.float64), False
+
+    @property
+    def synthesizes(self):
+        """Whether __call__ replaces the condition by a synthesized pose (JointsDataset.py:202: `and self.is_train`)."""
+        return self.synthesis_pose and self.is_train and self.conditional
+
+    def geometry(self, rec, aug=None, cond=None):
         """Everything of a sample that is scalar: returns dict(trans, center, scale, rot, flip, joints, joints_vis,
         cond_joints, cond_joints_vis) with the key points already in crop coordinates.  aug = (center, scale, rot, flip)
-        replaces the random draws (parity tests); center is the value BEFORE the flip mirrors it, like in the reference."""
+        replaces the random draws (parity tests); center is the value BEFORE the flip mirrors it, like in the reference.
+        cond = (cond_joints, cond_joints_vis) replaces the record's condition (a synthesized pose); cond = False leaves
+        the condition out (it is transformed on the device): cond_joints / cond_joints_vis come back as zeros."""
         img = rec["image"]
         ih, iw = int(img.shape[0]), int(img.shape[1])
         joints = np.array(rec["joints_3d"], dtype=np.float64).copy()
         joints_vis = np.array(rec["joints_3d_vis"], dtype=np.float64).copy()
-        has_cond = "cond_joints" in rec
-        cj = np.array(rec["cond_joints"], dtype=np.float64).copy() if has_cond else np.zeros_like(joints)
-        cv = np.array(rec["cond_joints_vis"], dtype=np.float64).copy() if has_cond else np.zeros_like(joints_vis)
+        if cond is None:
+            cj, cv, has_cond = self.condition(rec)
+        elif cond is False:
+            cj, cv, has_cond = np.zeros_like(joints), np.zeros_like(joints_vis), False
+        else:
+            cj, cv, has_cond = np.array(cond[0], dtype=np.float64).copy(), np.array(cond[1], dtype=np.float64).copy(), True
         if rec.get("use_bu_bbox", False) and has_cond and cj[:, 0].sum() != 0 and cj[0, 1].sum() != 0:
             x, y, w, h = box_from_keypoints(cj, self.bu_bbox_margin, iw, ih)
             center, scale = xywh2cs(x, y, w, h, self.aspect_ratio, self.scale_thre)
@@ -152,14 +258,10 @@ class DeviceSamplePipeline:
                     joints_vis=joints_vis, cond_joints=cj, cond_joints_vis=cv)
 
     # ---- batched device work -----------------------------------------------------------------------------------
-    def render(self, images, geos, want_crop=False):
-        """images: uint8 HWC device tensors; geos: geometry() results.  Returns input [B, 3(+3), H, W], target
-        [B, K, h, w], target_weight [B, K, 1] (+ the uint8 crops) on the device."""
-        dev = images[0].device
-        B, K = len(images), self.num_joints
-        W, H = int(self.image_size[0]), int(self.image_size[1])
-        cc = (K if self.stacked else 3) if self.conditional else 0      # stacked: one condition channel per joint
-        x = torch.empty((B, 3 + cc, H, W), dtype=torch.float32, device=dev)
+    def warp_table(self, images, geos):
+        """The per-sample table of the device kernels (buctd_warp_item: source image, flip, keep-rectangle, crop affine)
+        as a uint8 device tensor."""
+        B = len(images)
         items = (_WarpItem * B)()
         for b, (img, g) in enumerate(zip(images, geos)):
             if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not img.is_cuda:
@@ -170,7 +272,37 @@ class DeviceSamplePipeline:
             items[b].rx, items[b].ry, items[b].rw, items[b].rh = (int(v) for v in rect) if rect is not None else (0, 0, 0, 0)
             for k, v in enumerate(np.asarray(g["trans"], dtype=np.float64).reshape(6)):
                 items[b].m[k] = float(v)
-        table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
+        return torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(images[0].device)
+
+    def cond_geometry(self, synth, cond_vis, table):
+        """Flip + crop affine of device-resident condition poses (buctd_cond_geometry).  synth, cond_vis: float64 device
+        tensors [B, K, 3]; table: warp_table().  Returns cond_joints, cond_joints_vis (float64) and the truncated
+        coordinates float32 [B, K, 2] that render(cond_trunc=...) takes - all on the device."""
+        dev = synth.device
+        B, K = int(synth.shape[0]), int(synth.shape[1])
+        pair = self._pair_dev.get(dev)
+        if pair is None:
+            swap = _swap_table(K, self.flip_pairs)
+            pair = torch.from_numpy(np.where(swap == np.arange(K), -1, swap).astype(np.int32)).to(dev)
+            self._pair_dev[dev] = pair
+        cj, cv = torch.empty_like(synth), torch.empty_like(cond_vis)
+        cjt = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+        check(lib().buctd_cond_geometry(ptr(synth), ptr(cond_vis), ptr(table), ptr(pair), B, K, ptr(cj), ptr(cv), ptr(cjt),
+                                        stream_ptr()), "cond_geometry")
+        return cj, cv, cjt
+
+    def render(self, images, geos, want_crop=False, table=None, cond_trunc=None):
+        """images: uint8 HWC device tensors; geos: geometry() results.  Returns input [B, 3(+3), H, W], target
+        [B, K, h, w], target_weight [B, K, 1] (+ the uint8 crops) on the device.  table: warp_table(images, geos) if the
+        caller built it already; cond_trunc: the condition coordinates as cond_geometry() returns them, instead of
+        geos[.]['cond_joints']."""
+        dev = images[0].device
+        B, K = len(images), self.num_joints
+        W, H = int(self.image_size[0]), int(self.image_size[1])
+        cc = (K if self.stacked else 3) if self.conditional else 0      # stacked: one condition channel per joint
+        x = torch.empty((B, 3 + cc, H, W), dtype=torch.float32, device=dev)
+        if table is None:
+            table = self.warp_table(images, geos)
         crop = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if want_crop else None
         mean = (C.c_float * 3)(*self.mean.tolist())
         std = (C.c_float * 3)(*self.std.tolist())
@@ -182,20 +314,15 @@ class DeviceSamplePipeline:
         # (v / stride + 0.5 = mu - 0.5 truncates to mu; mu * stride would give mu + 0.5 -> mu + 1 for negative centres:
         # visible joints left of / above the crop would get a shifted Gaussian and a shifted target_weight cut-off)
         stride = self.image_size / self.heatmap_size
-        jt = np.zeros((B, K, 3), dtype=np.float32)
-        vis = np.zeros((B, K), dtype=np.float32)
-        for b, g in enumerate(geos):
-            mu_x = (g["joints"][:, 0] / stride[0] + 0.5).astype(int)
-            mu_y = (g["joints"][:, 1] / stride[1] + 0.5).astype(int)
-            jt[b, :, 0] = np.where(mu_x < 0, mu_x - 1, mu_x) * stride[0]
-            jt[b, :, 1] = np.where(mu_y < 0, mu_y - 1, mu_y) * stride[1]
-            vis[b] = g["joints_vis"][:, 0]
+        jt = target_centres(np.stack([g["joints"] for g in geos]), stride)
+        vis = np.stack([g["joints_vis"][:, 0] for g in geos]).astype(np.float32)
         target, weight = ops.gaussian_target(torch.from_numpy(jt).to(dev), torch.from_numpy(vis).to(dev),
                                              self.heatmap_size, self.image_size, self.sigma)
         if cc:
             # np.array(kpts).astype(int) truncates in float64 (JointsDataset.py:521): hand the kernel the integers
-            cj = np.stack([np.trunc(g["cond_joints"][:, :2]) for g in geos]).astype(np.float32)
-            cjt = torch.from_numpy(np.ascontiguousarray(cj)).to(dev)
+            cjt = cond_trunc
+            if cjt is None:
+                cjt = torch.from_numpy(trunc_condition(np.stack([g["cond_joints"] for g in geos]))).to(dev)
             colors = None
             if self.colored:
                 colors = torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:K])).to(dev)
@@ -219,12 +346,47 @@ class DeviceSamplePipeline:
                                                        ws.numel(), stream_ptr()), "cond_render_into")
         return (x, target, weight, crop) if want_crop else (x, target, weight)
 
-    def __call__(self, records, aug=None):
+    def synthesis_inputs(self, records):
+        """Host side of JointsDataset.py:165-167 and 204-212 for a batch: ground-truth joints [B, K, 3], the conditions
+        they are perturbed around and their visibilities, the neighbours [B, M, K, 3] (or None) and the areas [B]."""
+        K = self.num_joints
+        conds = [self.condition(r) for r in records]
+        J = np.stack([np.array(r["joints_3d"], dtype=np.float64).reshape(K, 3) for r in records])
+        E = np.stack([c[0].reshape(K, 3) for c in conds])
+        V = np.stack([c[1].reshape(K, 3) for c in conds])
+        near = pad_near_joints([r.get("near_joints", ()) for r in records], K)
+        return J, E, V, near, synthesis_area(E)
+
+    def __call__(self, records, aug=None, seed=None):
         """records: dicts with 'image' (uint8 HWC device tensor), 'joints_3d', 'joints_3d_vis', 'center', 'scale' and,
-        for conditional models, 'cond_joints' / 'cond_joints_vis' (+ 'score', 'annotation_id', 'use_bu_bbox').
+        for conditional models, 'cond_joints' / 'cond_joints_vis' (+ 'score', 'annotation_id', 'use_bu_bbox'; under
+        generative sampling 'near_joints', see the class docstring).  seed: of the pose synthesis of this batch.
         Returns (input, target, target_weight, meta) like a collated DataLoader batch of the reference."""
-        geos = [self.geometry(r, None if aug is None else aug[i]) for i, r in enumerate(records)]
-        x, target, weight = self.render([r["image"] for r in records], geos)
+        images = [r["image"] for r in records]
+        extra = {}
+        if self.synthesizes:
+            if seed is None:
+                seed = batch_seed(self.seed, self.synth_calls)
+                self.synth_calls += 1
+            J, E, V, near, area = self.synthesis_inputs(records)
+            synth = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
+                                          device=images[0].device)
+            extra["synth_joints"] = synth
+            if any(r.get("use_bu_bbox", False) for r in records):
+                # the crop box itself comes from the synthesized pose (JointsDataset.py:218-228): host geometry
+                host = synth.cpu().numpy()
+                geos = [self.geometry(r, None if aug is None else aug[i], cond=(host[i], V[i]))
+                        for i, r in enumerate(records)]
+                x, target, weight = self.render(images, geos)
+            else:
+                geos = [self.geometry(r, None if aug is None else aug[i], cond=False) for i, r in enumerate(records)]
+                table = self.warp_table(images, geos)
+                cj, cv, cjt = self.cond_geometry(synth, torch.from_numpy(V).to(synth.device), table)
+                x, target, weight = self.render(images, geos, table=table, cond_trunc=cjt)
+                extra["cond_joints"], extra["cond_joints_vis"] = cj, cv
+        else:
+            geos = [self.geometry(r, None if aug is None else aug[i]) for i, r in enumerate(records)]
+            x, target, weight = self.render(images, geos)
         meta = {
             "image": [r.get("image_file", "") for r in records],
             "joints": torch.from_numpy(np.stack([g["joints"] for g in geos])),
@@ -237,6 +399,7 @@ class DeviceSamplePipeline:
             "score": torch.tensor([float(r.get("score", 1)) for r in records]),
             "annotation_id": torch.tensor([int(r.get("annotation_id", -1)) for r in records]),
         }
+        meta.update(extra)
         return x, target, weight, meta
 
 

@@ -3,6 +3,7 @@
 sampling" recipe (DATASET.SYNTHESIS_POSE True).  synthesize_pose keeps the reference signature for one person;
 synthesize_pose_batch does a whole batch in one kernel launch (one wavefront per person and joint)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -44,7 +45,9 @@ def _joint_classes(dataset, k):
     return jit, miss, inv, swap, sym, np.array(sig) / 10.0, vis
 
 
+@functools.lru_cache(maxsize=None)
 def make_tables(dataset, num_joints):
+    """Per-dataset constants of the kernel (buctd_synth_tables), built once per (dataset, K); callers do not modify it."""
     jit, miss, inv, swap, sym, sig, vis = _joint_classes(dataset, num_joints)
     if len(sig) != num_joints or num_joints > _MAXK:
         raise ValueError(f"{dataset} has {len(sig)} key points, MODEL.NUM_JOINTS is {num_joints}")

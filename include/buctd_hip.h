@@ -677,6 +677,17 @@ int buctd_warp_affine_norm(const buctd_warp_item* items_device, int B, int dst_h
 int buctd_cond_render_into(const float* joints, int js, const float* colors, int B, int K, int Cc, int H, int W,
                            int truncate, float* cond, long cond_batch_stride, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* Condition key points of a generative-sampling train batch, from the synthesized poses to the render kernel's input
+ * without leaving the device (JointsDataset.py:257-259 and 293-295, as DeviceSamplePipeline.geometry does them on the
+ * host): per (sample, joint), with items[b].flip set, fliplr_joints - x = W - x - 1 (W = items[b].W), joints and
+ * visibilities exchanged with pair[j] (-1: no partner), joints * visibilities - then (x, y) through items[b].m where
+ * the (flipped) visibility's first column is > 0.  synth (straight from buctd_synthesize_pose, image coordinates) and
+ * cond_vis are float64 [B][K][3]; items_device is the table buctd_warp_affine_norm takes (only flip, W and m are read);
+ * pair_device int [K].  out_joints / out_vis float64 [B][K][3]; out_trunc float32 [B][K][2] = trunc(x), trunc(y),
+ * the `joints` argument of buctd_cond_render_into with js = 2.  float64 products and sums are never fused.  K <= 32. */
+int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd_warp_item* items_device,
+                        const int* pair_device, int B, int K, double* out_joints, double* out_vis, float* out_trunc,
+                        void* stream);
 
 /* Generative pose synthesis (dataset/pose_synthesis.py:234-817, called from JointsDataset.py:202-215): for every person
  * and joint one of the error types jitter / miss / inversion / swap / good is drawn and a key point proposed

@@ -168,8 +168,6 @@ SIGNATURES = {
     "buctd_stream_fork": (_I, [_P, _P]),
     "buctd_basic_branches_fwd_train": (_I, [_I, _I, C.POINTER(BasicBlockDesc), _P]),
     "buctd_basic_branches_bwd": (_I, [_I, _I, C.POINTER(BasicBlockDesc), C.POINTER(BasicBlockGrads), _P, _P]),
-    "buctd_basic_block_fwd_train": (_I, [C.POINTER(BasicBlockDesc), _P]),
-    "buctd_basic_block_bwd": (_I, [C.POINTER(BasicBlockDesc), C.POINTER(BasicBlockGrads), _P, _P]),
     "buctd_basic_chain_fwd_train": (_I, [_I, C.POINTER(BasicBlockDesc), _P]),
     "buctd_basic_chain_bwd": (_I, [_I, C.POINTER(BasicBlockDesc), C.POINTER(BasicBlockGrads), _P, _P]),
     "buctd_x6_image_dims": (_I, [_I, _I, _I, _P, _P]),

@@ -35,14 +35,24 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        if (self.training and self.downsample is None and self.stride == 1 and x.is_cuda and torch.is_grad_enabled()
-                and self.conv1.bias is None and self.conv2.bias is None and self.bn1.training and self.bn2.training):
-            nn._as_channels_last_(self.conv1.weight)
-            nn._as_channels_last_(self.conv2.weight)
-            return ops.BasicBlockFn.apply(x, self.conv1.weight, self.bn1, self.conv2.weight, self.bn2)
+        if self.training and x.is_cuda and torch.is_grad_enabled() and _native_block(self):
+            return ops.BasicBlockFn.apply(x, *_block_params(self))
         residual = x if self.downsample is None else self.downsample(x)
         out = nn.conv_bn_act(x, self.conv1, self.bn1, relu=True)
         return nn.conv_bn_act(out, self.conv2, self.bn2, relu=True, residual=residual)
+
+
+def _native_block(m):
+    """A plain BasicBlock in train mode: what the native sequences (ops.BasicBlockFn / BasicChainFn / BasicBranchesFn) take."""
+    return (type(m) is BasicBlock and m.downsample is None and m.stride == 1 and m.conv1.bias is None and m.conv2.bias is None
+            and m.bn1.training and m.bn2.training and m.bn1.track_running_stats == m.bn2.track_running_stats)
+
+
+def _block_params(m):
+    """-> (w1, bn1, w2, bn2) of a BasicBlock as the ops take them: the weights in channels_last memory."""
+    nn._as_channels_last_(m.conv1.weight)
+    nn._as_channels_last_(m.conv2.weight)
+    return m.conv1.weight, m.bn1, m.conv2.weight, m.bn2
 
 
 class Bottleneck(nn.Module):
@@ -82,16 +92,9 @@ class BlockChain(nn.Chain):
 
     def forward(self, x):
         if (len(self) > 1 and self.training and x.is_cuda and torch.is_grad_enabled() and ops.native_chain_ok(tuple(x.shape))
-                and all(type(m) is BasicBlock and m.downsample is None and m.stride == 1 and m.conv1.bias is None
-                        and m.conv2.bias is None and m.bn1.training and m.bn2.training
-                        and m.bn1.track_running_stats == m.bn2.track_running_stats == self[0].bn1.track_running_stats for m in self)
+                and all(_native_block(m) and m.bn1.track_running_stats == self[0].bn1.track_running_stats for m in self)
                 and ops.bn_in_fusable(tuple(x.shape), self[0].conv1.weight)):
-            blocks = []
-            for m in self:
-                nn._as_channels_last_(m.conv1.weight)
-                nn._as_channels_last_(m.conv2.weight)
-                blocks.append((m.conv1.weight, m.bn1, m.conv2.weight, m.bn2))
-            return ops.BasicChainFn.apply(x, self[0].conv1.weight, blocks)
+            return ops.BasicChainFn.apply(x, self[0].conv1.weight, [_block_params(m) for m in self])
         return super().forward(x)
 
 
@@ -176,18 +179,12 @@ class HighResolutionModule(nn.Module):
             return None
         chains = []
         for br in self.branches:
-            if not all(type(m) is BasicBlock and m.downsample is None and m.stride == 1 and m.conv1.bias is None
-                       and m.conv2.bias is None and m.bn1.track_running_stats == m.bn2.track_running_stats
-                       == br[0].bn1.track_running_stats and m.bn1.training and m.bn2.training for m in br):
+            if not all(_native_block(m) and m.bn1.track_running_stats == br[0].bn1.track_running_stats for m in br):
                 return None
-            chains.append([(m.conv1.weight, m.bn1, m.conv2.weight, m.bn2) for m in br])
+            chains.append([_block_params(m) for m in br])
         xs = [x[i] for i in range(nb)]
         if not ops.group_branches_ok(xs, chains):
             return None
-        for chain in chains:
-            for (w1, _, w2, _) in chain:
-                nn._as_channels_last_(w1)
-                nn._as_channels_last_(w2)
         parts = ops.group_branch_partition(nb)
         if len(parts) == 1:
             return list(ops.BasicBranchesFn.apply(chains[0][0][0], chains, *xs))
@@ -211,12 +208,8 @@ class HighResolutionModule(nn.Module):
                        and m.conv2.bias is None and not m.bn1.training and not m.bn2.training
                        and m.bn1.running_mean is not None and m.bn2.running_mean is not None for m in br):
                 return None
-            chains.append([(m.conv1.weight, m.bn1, m.conv2.weight, m.bn2) for m in br])
+            chains.append([_block_params(m) for m in br])
         xs = [x[i] for i in range(self.num_branches)]
-        for chain in chains:
-            for (w1, _, w2, _) in chain:
-                nn._as_channels_last_(w1)
-                nn._as_channels_last_(w2)
         if not ops.eval_branches_ok(xs, chains):
             return None
         return ops.basic_branches_eval(xs, chains)

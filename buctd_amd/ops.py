@@ -841,6 +841,13 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, bias=None, stats=False, residual
     return (dx, part, info) if stats else dx
 
 
+def _wgrad3x3_workspace(mode, N, H, W, Ci, Co):
+    """Workspace bytes of the 3x3 / stride 1 / pad 1 weight gradient in a split-bf16 mode; -1: no kernel for this shape."""
+    return _memo(("wg3", mode, N, H, W, Ci, Co),
+                 lambda: (getattr(lib(), "buctd_conv3x3_wgrad_" + mode + "_workspace")(N, H, W, Ci, Co)
+                          if getattr(lib(), "buctd_conv3x3_wgrad_" + mode + "_supported")(N, H, W, Ci, Co) == 1 else -1))
+
+
 def conv_wgrad(x, dy, w_like, stride=1, pad=0, out=None, accumulate=0, x_bn=None, stream=None):
     """x_bn = (mean, invstd, gamma, beta, relu): like conv_fwd's in_bn, for the X operand of the weight gradient.
     stream: a torch.cuda.Stream to launch on WITHOUT making it current (entering a stream context costs ~15 us of host time
@@ -861,10 +868,7 @@ def conv_wgrad(x, dy, w_like, stride=1, pad=0, out=None, accumulate=0, x_bn=None
     mode = _conv_math["mode"]
     if mode != "fp32" and d.R == 3 and d.S == 3 and d.stride == 1 and d.pad == 1:
         fn = getattr(lib(), "buctd_conv3x3_wgrad_" + mode)
-        need = _memo(("wg3", mode, d.N, d.H, d.W, d.Ci, d.Co),
-                     lambda: (getattr(lib(), "buctd_conv3x3_wgrad_" + mode + "_workspace")(d.N, d.H, d.W, d.Ci, d.Co)
-                              if getattr(lib(), "buctd_conv3x3_wgrad_" + mode + "_supported")(d.N, d.H, d.W, d.Ci, d.Co) == 1
-                              else -1))
+        need = _wgrad3x3_workspace(mode, d.N, d.H, d.W, d.Ci, d.Co)
         if need >= 0:
             ws = workspace_(need, x.device)
             if x_bn is not None:
@@ -1580,6 +1584,11 @@ def _contig(g):
     return g if g.is_contiguous() else g.contiguous()
 
 
+def _count_batch(bn):
+    """One more train-mode batch through bn: on the host where the module defers the count (nn.BatchNorm2d.count_batch)."""
+    bn.count_batch() if hasattr(bn, "count_batch") else bn.num_batches_tracked.add_(1)
+
+
 class ConvBnAct(torch.autograd.Function):
     """conv (+bias) -> BatchNorm2d -> (+residual) -> (ReLU), train or eval mode.
 
@@ -1610,7 +1619,7 @@ class ConvBnAct(torch.autograd.Function):
                                            bn.running_mean if track else None, bn.running_var if track else None)
                 y = bn_apply(z, mean, invstd, gamma, beta, residual, relu)
             if track:
-                bn.count_batch() if hasattr(bn, "count_batch") else bn.num_batches_tracked.add_(1)
+                _count_batch(bn)
             ctx.has_res = residual is not None
             # without a residual the ReLU mask is rebuilt from z in the backward kernels: y is not kept (nor re-read)
             ctx.save_for_backward(x, z, mean, invstd, y if (relu and ctx.has_res) else None)
@@ -1795,7 +1804,11 @@ class BasicBlockFn(torch.autograd.Function):
         veto = native_block_veto["fn"]
         if (fuse and bn_in_fusable(tuple(x.shape), w1) and bn1.track_running_stats == bn2.track_running_stats
                 and not (veto is not None and veto(tuple(x.shape)))):
-            return BasicBlockFn._forward_native(ctx, x, w1, bn1, w2, bn2)
+            # the same five kernels through ONE library call, the chain of one block: the nine ctypes calls and dozen small
+            # allocations of the step-by-step path cost ~95 us of host time per block - more than HRNet-W32 needs on the GPU
+            ctx.native = True
+            return _chain_forward(ctx, x, [(w1, bn1, w2, bn2)])
+        ctx.native = False
         z1, part, info = conv_fwd(x, w1, None, 1, 1, stats="acc")
         Cn = z1.shape[-1]
         rows = z1.numel() // Cn
@@ -1826,105 +1839,15 @@ class BasicBlockFn(torch.autograd.Function):
             y = bn_apply(z2, mean2, invstd2, bn2.weight, bn2.bias, x, True)
         for bn in (bn1, bn2):
             if bn.track_running_stats:
-                bn.count_batch() if hasattr(bn, "count_batch") else bn.num_batches_tracked.add_(1)
+                _count_batch(bn)
         ctx.meta = (w1, bn1, w2, bn2, fuse)
         ctx.save_for_backward(x, z1, mean1, invstd1, None if fuse else y1, z2, mean2, invstd2, y)
         return y
 
     @staticmethod
-    def _forward_native(ctx, x, w1, bn1, w2, bn2):
-        """The same five kernels through ONE library call (block.hip): the nine ctypes calls and dozen small allocations of
-        the step-by-step path cost ~95 us of host time per block - more than HRNet-W32 needs on the GPU."""
-        N, H, W, Cn = x.shape
-        dev = x.device
-        act = torch.empty((3, N, H, W, Cn), dtype=torch.float32, device=dev)       # z1 | z2 | y
-        stat = torch.empty((4, Cn), dtype=torch.float32, device=dev)               # mean1 | invstd1 | mean2 | invstd2
-        d = _C.BasicBlockDesc()
-        d.N, d.H, d.W, d.C = N, H, W, Cn
-        d.x = x.data_ptr()
-        d.w1_fwd = _conv3x3_prepared(w1, 0).data_ptr()
-        d.w2_fwd = _conv3x3_prepared(w2, 0).data_ptr()
-        d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-        d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-        track = bn1.track_running_stats
-        if track:
-            d.running_mean1, d.running_var1 = bn1.running_mean.data_ptr(), bn1.running_var.data_ptr()
-            d.running_mean2, d.running_var2 = bn2.running_mean.data_ptr(), bn2.running_var.data_ptr()
-        d.eps1, d.momentum1 = bn1.eps, 0.1 if bn1.momentum is None else bn1.momentum
-        d.eps2, d.momentum2 = bn2.eps, 0.1 if bn2.momentum is None else bn2.momentum
-        base, step = act.data_ptr(), 4 * N * H * W * Cn
-        d.z1, d.z2, d.y = base, base + step, base + 2 * step
-        d.acc, d.stat = AccRef(Cn, dev, 2).ptr, stat.data_ptr()
-        check(lib().buctd_basic_block_fwd_train(C.byref(d), stream_ptr()), "basic_block_fwd_train")
-        if track:
-            for bn in (bn1, bn2):
-                bn.count_batch() if hasattr(bn, "count_batch") else bn.num_batches_tracked.add_(1)
-        y = act[2]
-        ctx.meta = (w1, bn1, w2, bn2, "native")
-        ctx.save_for_backward(x, act, stat)
-        return y
-
-    @staticmethod
-    def _backward_native(ctx, dy):
-        w1, bn1, w2, bn2, _ = ctx.meta
-        x, act, stat = ctx.saved_tensors
-        dy = _contig(dy)
-        N, H, W, Cn = x.shape
-        dev = x.device
-        want_dx = ctx.needs_input_grad[0]
-        tmp = torch.empty((5 if want_dx else 4, N, H, W, Cn), dtype=torch.float32, device=dev)   # dz2 | dres | dy1 | dz1 | dx
-        d = _C.BasicBlockDesc()
-        d.N, d.H, d.W, d.C = N, H, W, Cn
-        d.x = x.data_ptr()
-        d.w1_fwd = d.w2_fwd = 0
-        d.w1_bwd = _conv3x3_prepared(w1, 1).data_ptr()
-        d.w2_bwd = _conv3x3_prepared(w2, 1).data_ptr()
-        d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-        d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-        base, step = act.data_ptr(), 4 * N * H * W * Cn
-        d.z1, d.z2, d.y = base, base + step, base + 2 * step
-        d.stat = stat.data_ptr()
-        g = _C.BasicBlockGrads()
-        tb = tmp.data_ptr()
-        g.dy, g.dz2, g.dres, g.dy1, g.dz1 = dy.data_ptr(), tb, tb + step, tb + 2 * step, tb + 3 * step
-        g.dx = tb + 4 * step if want_dx else 0
-        dg2, acc_g2 = grad_target(bn2.weight)
-        db2, acc_b2 = grad_target(bn2.bias)
-        dw2, acc_w2 = grad_target(w2)
-        dg1, acc_g1 = grad_target(bn1.weight)
-        db1, acc_b1 = grad_target(bn1.bias)
-        dw1, acc_w1 = grad_target(w1)
-        assert acc_g2 == acc_b2 and acc_g1 == acc_b1
-        weight_rsc(dw1)
-        weight_rsc(dw2)
-        g.dw1, g.dw2 = dw1.data_ptr(), dw2.data_ptr()
-        g.dgamma1, g.dbeta1, g.dgamma2, g.dbeta2 = dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr()
-        g.acc_w1, g.acc_w2, g.acc_bn1, g.acc_bn2 = int(acc_w1), int(acc_w2), int(acc_g1), int(acc_g2)
-        g.bn_acc = AccRef(Cn, dev, 2).ptr
-        main = torch.cuda.current_stream(dev)
-        use_side = _side["on"]
-        side = _side_stream(dev) if use_side else main
-        need = _memo(("wg3", "bf16x6", N, H, W, Cn, Cn),
-                     lambda: (lib().buctd_conv3x3_wgrad_bf16x6_workspace(N, H, W, Cn, Cn)
-                              if lib().buctd_conv3x3_wgrad_bf16x6_supported(N, H, W, Cn, Cn) == 1 else -1))
-        wg_ws = workspace_on(side, need, dev)      # the side stream's own scratch buffer
-        g.wg_ws, g.wg_ws_bytes = wg_ws.data_ptr(), wg_ws.numel()
-        check(lib().buctd_basic_block_bwd(C.byref(d), C.byref(g), main.cuda_stream, side.cuda_stream if use_side else None),
-              "basic_block_bwd")
-        if use_side:
-            for t in (x, act, stat, tmp):
-                t.record_stream(side)
-            _queue_join()
-        elif _branch["on"]:
-            _queue_join()
-        grad_done(bn2.weight, bn2.bias, w2)
-        grad_done(bn1.weight, bn1.bias, w1)
-        return (tmp[4] if want_dx else None), None, None, None, None
-
-    @staticmethod
     def backward(ctx, dy):
-        if ctx.meta[4] == "native":
-            return BasicBlockFn._backward_native(ctx, dy)
+        if ctx.native:
+            return _chain_backward(ctx, dy, ctx.needs_input_grad[0]), None, None, None, None
         w1, bn1, w2, bn2, fuse = ctx.meta
         x, z1, mean1, invstd1, y1, z2, mean2, invstd2, y2 = ctx.saved_tensors
         dy = _contig(dy)
@@ -1952,113 +1875,137 @@ class BasicBlockFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+def _block_desc(d, shape, step, xin, params, act, stat, acc=None):
+    """Fill the BasicBlockDesc of one block (block.hip) with input address xin: act -> its z1 | z2 | y slabs of `step` bytes,
+    stat -> its 4 * C floats.  acc = address of its two forward statistics accumulators: the forward (flip-0 weight images,
+    running statistics, the batch is counted); None: the backward (flip-1 images).  Returns the address of y - the next
+    block's input."""
+    w1, bn1, w2, bn2 = params
+    d.N, d.H, d.W, d.C = shape
+    d.x = xin
+    d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
+    d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
+    d.z1, d.z2, d.y = act, act + step, act + 2 * step
+    d.stat = stat
+    if acc is None:
+        d.w1_bwd = _conv3x3_prepared(w1, 1).data_ptr()
+        d.w2_bwd = _conv3x3_prepared(w2, 1).data_ptr()
+    else:
+        d.w1_fwd = _conv3x3_prepared(w1, 0).data_ptr()
+        d.w2_fwd = _conv3x3_prepared(w2, 0).data_ptr()
+        if bn1.track_running_stats:
+            d.running_mean1, d.running_var1 = bn1.running_mean.data_ptr(), bn1.running_var.data_ptr()
+            d.running_mean2, d.running_var2 = bn2.running_mean.data_ptr(), bn2.running_var.data_ptr()
+            _count_batch(bn1)
+            _count_batch(bn2)
+        d.eps1, d.momentum1 = bn1.eps, 0.1 if bn1.momentum is None else bn1.momentum
+        d.eps2, d.momentum2 = bn2.eps, 0.1 if bn2.momentum is None else bn2.momentum
+        d.acc = acc
+    return act + 2 * step
+
+
+def _block_grads(g, tmp, step, dy, want_dx, params, bn_acc, ws, ws_bytes):
+    """Fill the BasicBlockGrads of one block: tmp -> its dz2 | dres | dy1 | dz1 (| dx) slabs of `step` bytes, dy = address of
+    the upstream gradient, bn_acc = its two backward accumulators, ws = weight-gradient workspace.  Takes the gradient
+    targets of the six parameters (grad_target)."""
+    w1, bn1, w2, bn2 = params
+    g.dy = dy
+    g.dz2, g.dres, g.dy1, g.dz1 = tmp, tmp + step, tmp + 2 * step, tmp + 3 * step
+    g.dx = tmp + 4 * step if want_dx else 0
+    dg2, acc_g2 = grad_target(bn2.weight)
+    db2, acc_b2 = grad_target(bn2.bias)
+    dw2, acc_w2 = grad_target(w2)
+    dg1, acc_g1 = grad_target(bn1.weight)
+    db1, acc_b1 = grad_target(bn1.bias)
+    dw1, acc_w1 = grad_target(w1)
+    assert acc_g2 == acc_b2 and acc_g1 == acc_b1
+    weight_rsc(dw1)
+    weight_rsc(dw2)
+    g.dw1, g.dw2 = dw1.data_ptr(), dw2.data_ptr()
+    g.dgamma1, g.dbeta1, g.dgamma2, g.dbeta2 = dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr()
+    g.acc_w1, g.acc_w2, g.acc_bn1, g.acc_bn2 = int(acc_w1), int(acc_w2), int(acc_g1), int(acc_g2)
+    g.bn_acc = bn_acc
+    g.wg_ws, g.wg_ws_bytes = ws, ws_bytes
+
+
+def _native_bwd_done(side, tensors, blocks):
+    """Behind a native backward call: `tensors` were read or written on the side stream (None: it is off), the end-of-backward
+    join is queued, and the gradients of `blocks` - listed in the order their kernels were enqueued - are reported ready."""
+    if side is not None:
+        for t in tensors:
+            t.record_stream(side)
+        _queue_join()
+    elif _branch["on"]:
+        _queue_join()
+    for (w1, bn1, w2, bn2) in blocks:
+        grad_done(bn2.weight, bn2.bias, w2)
+        grad_done(bn1.weight, bn1.bias, w1)
+
+
+def _chain_forward(ctx, x, blocks):
+    """The native forward of BasicChainFn and - with one block - of BasicBlockFn: one library call (block.hip)."""
+    n = len(blocks)
+    shape = N, H, W, Cn = x.shape
+    dev = x.device
+    act = torch.empty((n, 3, N, H, W, Cn), dtype=torch.float32, device=dev)        # per block: z1 | z2 | y
+    stat = torch.empty((n, 4, Cn), dtype=torch.float32, device=dev)     # per block: mean1 | invstd1 | mean2 | invstd2
+    descs = (_C.BasicBlockDesc * n)()
+    step = 4 * N * H * W * Cn
+    accb = acc_bytes(Cn)
+    abase, pbase, sbase = act.data_ptr(), AccRef(Cn, dev, 2 * n).ptr, stat.data_ptr()
+    xin = x.data_ptr()
+    for k, blk in enumerate(blocks):
+        xin = _block_desc(descs[k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4, pbase + k * 2 * accb)
+    check(lib().buctd_basic_chain_fwd_train(n, descs, stream_ptr()), "basic_chain_fwd_train")
+    ctx.blocks = blocks
+    ctx.save_for_backward(x, act, stat)
+    return act[n - 1, 2]
+
+
+def _chain_backward(ctx, dy, want_dx):
+    """-> the gradient of the chain's input, or None."""
+    blocks = ctx.blocks
+    n = len(blocks)
+    x, act, stat = ctx.saved_tensors
+    dy = _contig(dy)
+    shape = N, H, W, Cn = x.shape
+    dev = x.device
+    # per block: dz2 | dres | dy1 | dz1 | dx; a single block whose input needs no gradient does without the last slab
+    tmp = torch.empty((n, 5 if (n > 1 or want_dx) else 4, N, H, W, Cn), dtype=torch.float32, device=dev)
+    step = 4 * N * H * W * Cn
+    abase, sbase, tb = act.data_ptr(), stat.data_ptr(), tmp.data_ptr()
+    descs = (_C.BasicBlockDesc * n)()
+    grads = (_C.BasicBlockGrads * n)()
+    main = torch.cuda.current_stream(dev)
+    use_side = _side["on"]
+    side = _side_stream(dev) if use_side else main
+    accb = acc_bytes(Cn)
+    bn_acc = AccRef(Cn, dev, 2 * n).ptr
+    wg_ws = workspace_on(side, _wgrad3x3_workspace("bf16x6", N, H, W, Cn, Cn), dev)     # the side stream's own scratch buffer
+    ws, ws_bytes = wg_ws.data_ptr(), wg_ws.numel()
+    xin = x.data_ptr()
+    for k, blk in enumerate(blocks):
+        xin = _block_desc(descs[k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4)
+        up = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
+        _block_grads(grads[k], tb + 5 * step * k, step, up, k > 0 or want_dx, blk, bn_acc + k * 2 * accb, ws, ws_bytes)
+    check(lib().buctd_basic_chain_bwd(n, descs, grads, main.cuda_stream, side.cuda_stream if use_side else None),
+          "basic_chain_bwd")
+    _native_bwd_done(side if use_side else None, (x, act, stat, tmp, dy), reversed(blocks))
+    return tmp[0, 4] if want_dx else None
+
+
 class BasicChainFn(torch.autograd.Function):
     """A chain of residual BasicBlocks (an HRNet branch: pose_hrnet.py:165-185) as ONE autograd node and one library call
-    per direction (block.hip: buctd_basic_chain_*): the launches of BasicBlockFn's native path, a quarter of its host work
+    per direction (block.hip: buctd_basic_chain_*): the launches of n BasicBlockFn nodes, a quarter of their host work
     per block.  blocks: [(w1, bn1, w2, bn2), ...]; w_first only makes autograd build the node when x needs no gradient."""
 
     @staticmethod
     def forward(ctx, x, w_first, blocks):
-        n = len(blocks)
-        N, H, W, Cn = x.shape
-        dev = x.device
-        act = torch.empty((n, 3, N, H, W, Cn), dtype=torch.float32, device=dev)        # per block: z1 | z2 | y
-        stat = torch.empty((n, 4, Cn), dtype=torch.float32, device=dev)
-        descs = (_C.BasicBlockDesc * n)()
-        step = 4 * N * H * W * Cn
-        accb = acc_bytes(Cn)
-        abase, pbase, sbase = act.data_ptr(), AccRef(Cn, dev, 2 * n).ptr, stat.data_ptr()
-        xin = x.data_ptr()
-        for k, (w1, bn1, w2, bn2) in enumerate(blocks):
-            d = descs[k]
-            d.N, d.H, d.W, d.C = N, H, W, Cn
-            d.x = xin
-            d.w1_fwd = _conv3x3_prepared(w1, 0).data_ptr()
-            d.w2_fwd = _conv3x3_prepared(w2, 0).data_ptr()
-            d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-            d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-            if bn1.track_running_stats:
-                d.running_mean1, d.running_var1 = bn1.running_mean.data_ptr(), bn1.running_var.data_ptr()
-                d.running_mean2, d.running_var2 = bn2.running_mean.data_ptr(), bn2.running_var.data_ptr()
-                bn1.count_batch() if hasattr(bn1, "count_batch") else bn1.num_batches_tracked.add_(1)
-                bn2.count_batch() if hasattr(bn2, "count_batch") else bn2.num_batches_tracked.add_(1)
-            d.eps1, d.momentum1 = bn1.eps, 0.1 if bn1.momentum is None else bn1.momentum
-            d.eps2, d.momentum2 = bn2.eps, 0.1 if bn2.momentum is None else bn2.momentum
-            b0 = abase + 3 * step * k
-            d.z1, d.z2, d.y = b0, b0 + step, b0 + 2 * step
-            d.acc, d.stat = pbase + k * 2 * accb, sbase + k * 4 * Cn * 4
-            xin = d.y
-        check(lib().buctd_basic_chain_fwd_train(n, descs, stream_ptr()), "basic_chain_fwd_train")
-        ctx.blocks = blocks
-        ctx.save_for_backward(x, act, stat)
-        return act[n - 1, 2]
+        return _chain_forward(ctx, x, blocks)
 
     @staticmethod
     def backward(ctx, dy):
-        blocks = ctx.blocks
-        n = len(blocks)
-        x, act, stat = ctx.saved_tensors
-        dy = _contig(dy)
-        N, H, W, Cn = x.shape
-        dev = x.device
-        want_dx = ctx.needs_input_grad[0]
-        tmp = torch.empty((n, 5, N, H, W, Cn), dtype=torch.float32, device=dev)     # per block: dz2 | dres | dy1 | dz1 | dx
-        step = 4 * N * H * W * Cn
-        abase, sbase, tb = act.data_ptr(), stat.data_ptr(), tmp.data_ptr()
-        descs = (_C.BasicBlockDesc * n)()
-        grads = (_C.BasicBlockGrads * n)()
-        main = torch.cuda.current_stream(dev)
-        use_side = _side["on"]
-        side = _side_stream(dev) if use_side else main
-        accb = acc_bytes(Cn)
-        bn_acc = AccRef(Cn, dev, 2 * n).ptr
-        need = _memo(("wg3", "bf16x6", N, H, W, Cn, Cn),
-                     lambda: (lib().buctd_conv3x3_wgrad_bf16x6_workspace(N, H, W, Cn, Cn)
-                              if lib().buctd_conv3x3_wgrad_bf16x6_supported(N, H, W, Cn, Cn) == 1 else -1))
-        wg_ws = workspace_on(side, need, dev)
-        xin = x.data_ptr()
-        for k, (w1, bn1, w2, bn2) in enumerate(blocks):
-            d, g = descs[k], grads[k]
-            d.N, d.H, d.W, d.C = N, H, W, Cn
-            d.x = xin
-            d.w1_bwd = _conv3x3_prepared(w1, 1).data_ptr()
-            d.w2_bwd = _conv3x3_prepared(w2, 1).data_ptr()
-            d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-            d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-            b0 = abase + 3 * step * k
-            d.z1, d.z2, d.y = b0, b0 + step, b0 + 2 * step
-            d.stat = sbase + k * 4 * Cn * 4
-            xin = d.y
-            t0 = tb + 5 * step * k
-            g.dy = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
-            g.dz2, g.dres, g.dy1, g.dz1 = t0, t0 + step, t0 + 2 * step, t0 + 3 * step
-            g.dx = t0 + 4 * step if (k > 0 or want_dx) else 0
-            dg2, acc_g2 = grad_target(bn2.weight)
-            db2, acc_b2 = grad_target(bn2.bias)
-            dw2, acc_w2 = grad_target(w2)
-            dg1, acc_g1 = grad_target(bn1.weight)
-            db1, acc_b1 = grad_target(bn1.bias)
-            dw1, acc_w1 = grad_target(w1)
-            assert acc_g2 == acc_b2 and acc_g1 == acc_b1
-            weight_rsc(dw1)
-            weight_rsc(dw2)
-            g.dw1, g.dw2 = dw1.data_ptr(), dw2.data_ptr()
-            g.dgamma1, g.dbeta1, g.dgamma2, g.dbeta2 = dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr()
-            g.acc_w1, g.acc_w2, g.acc_bn1, g.acc_bn2 = int(acc_w1), int(acc_w2), int(acc_g1), int(acc_g2)
-            g.bn_acc = bn_acc + k * 2 * accb
-            g.wg_ws, g.wg_ws_bytes = wg_ws.data_ptr(), wg_ws.numel()
-        check(lib().buctd_basic_chain_bwd(n, descs, grads, main.cuda_stream, side.cuda_stream if use_side else None),
-              "basic_chain_bwd")
-        if use_side:
-            for t in (x, act, stat, tmp, dy):
-                t.record_stream(side)
-            _queue_join()
-        elif _branch["on"]:
-            _queue_join()
-        for (w1, bn1, w2, bn2) in reversed(blocks):
-            grad_done(bn2.weight, bn2.bias, w2)
-            grad_done(bn1.weight, bn1.bias, w1)
-        return (tmp[0, 4] if want_dx else None), None, None
+        return _chain_backward(ctx, dy, ctx.needs_input_grad[0]), None, None
 
 
 _GROUP_BRANCHES = {"on": True}
@@ -2175,7 +2122,7 @@ class BasicBranchesFn(torch.autograd.Function):
         descs = (_C.BasicBlockDesc * (nb * n))()
         acts, stats = [], []
         for b, x in enumerate(xs):
-            N, H, W, Cn = x.shape
+            shape = N, H, W, Cn = x.shape
             act = torch.empty((n, 3, N, H, W, Cn), dtype=torch.float32, device=dev)        # per block: z1 | z2 | y
             stat = torch.empty((n, 4, Cn), dtype=torch.float32, device=dev)
             acts.append(act)
@@ -2184,25 +2131,9 @@ class BasicBranchesFn(torch.autograd.Function):
             accb = acc_bytes(Cn)
             abase, pbase, sbase = act.data_ptr(), AccRef(Cn, dev, 2 * n).ptr, stat.data_ptr()
             xin = x.data_ptr()
-            for k, (w1, bn1, w2, bn2) in enumerate(chains[b]):
-                d = descs[b * n + k]
-                d.N, d.H, d.W, d.C = N, H, W, Cn
-                d.x = xin
-                d.w1_fwd = _conv3x3_prepared(w1, 0).data_ptr()
-                d.w2_fwd = _conv3x3_prepared(w2, 0).data_ptr()
-                d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-                d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-                if bn1.track_running_stats:
-                    d.running_mean1, d.running_var1 = bn1.running_mean.data_ptr(), bn1.running_var.data_ptr()
-                    d.running_mean2, d.running_var2 = bn2.running_mean.data_ptr(), bn2.running_var.data_ptr()
-                    bn1.count_batch() if hasattr(bn1, "count_batch") else bn1.num_batches_tracked.add_(1)
-                    bn2.count_batch() if hasattr(bn2, "count_batch") else bn2.num_batches_tracked.add_(1)
-                d.eps1, d.momentum1 = bn1.eps, 0.1 if bn1.momentum is None else bn1.momentum
-                d.eps2, d.momentum2 = bn2.eps, 0.1 if bn2.momentum is None else bn2.momentum
-                b0 = abase + 3 * step * k
-                d.z1, d.z2, d.y = b0, b0 + step, b0 + 2 * step
-                d.acc, d.stat = pbase + k * 2 * accb, sbase + k * 4 * Cn * 4
-                xin = d.y
+            for k, blk in enumerate(chains[b]):
+                xin = _block_desc(descs[b * n + k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4,
+                                  pbase + k * 2 * accb)
         check(lib().buctd_basic_branches_fwd_train(nb, n, descs, stream_ptr()), "basic_branches_fwd_train")
         ctx.chains = chains
         ctx.save_for_backward(*xs, *acts, *stats)
@@ -2229,7 +2160,7 @@ class BasicBranchesFn(torch.autograd.Function):
         ws_ptr = wg_ws.data_ptr()
         tmps, keep = [], []
         for b, x in enumerate(xs):
-            N, H, W, Cn = x.shape
+            shape = N, H, W, Cn = x.shape
             dy = dys[b]
             dy = torch.zeros_like(x) if dy is None else _contig(dy)
             keep.append(dy)
@@ -2241,50 +2172,16 @@ class BasicBranchesFn(torch.autograd.Function):
             accb = acc_bytes(Cn)
             bn_acc = AccRef(Cn, dev, 2 * n).ptr
             xin = x.data_ptr()
-            for k, (w1, bn1, w2, bn2) in enumerate(chains[b]):
-                d, g = descs[b * n + k], grads[b * n + k]
-                d.N, d.H, d.W, d.C = N, H, W, Cn
-                d.x = xin
-                d.w1_bwd = _conv3x3_prepared(w1, 1).data_ptr()
-                d.w2_bwd = _conv3x3_prepared(w2, 1).data_ptr()
-                d.gamma1, d.beta1 = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-                d.gamma2, d.beta2 = bn2.weight.data_ptr(), bn2.bias.data_ptr()
-                b0 = abase + 3 * step * k
-                d.z1, d.z2, d.y = b0, b0 + step, b0 + 2 * step
-                d.stat = sbase + k * 4 * Cn * 4
-                xin = d.y
-                t0 = tb + 5 * step * k
-                g.dy = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
-                g.dz2, g.dres, g.dy1, g.dz1 = t0, t0 + step, t0 + 2 * step, t0 + 3 * step
-                g.dx = t0 + 4 * step if (k > 0 or want_dx) else 0
-                dg2, acc_g2 = grad_target(bn2.weight)
-                db2, acc_b2 = grad_target(bn2.bias)
-                dw2, acc_w2 = grad_target(w2)
-                dg1, acc_g1 = grad_target(bn1.weight)
-                db1, acc_b1 = grad_target(bn1.bias)
-                dw1, acc_w1 = grad_target(w1)
-                assert acc_g2 == acc_b2 and acc_g1 == acc_b1
-                weight_rsc(dw1)
-                weight_rsc(dw2)
-                g.dw1, g.dw2 = dw1.data_ptr(), dw2.data_ptr()
-                g.dgamma1, g.dbeta1, g.dgamma2, g.dbeta2 = dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr()
-                g.acc_w1, g.acc_w2, g.acc_bn1, g.acc_bn2 = int(acc_w1), int(acc_w2), int(acc_g1), int(acc_g2)
-                g.bn_acc = bn_acc + k * 2 * accb
-                g.wg_ws, g.wg_ws_bytes = ws_ptr, needs[b]
+            for k, blk in enumerate(chains[b]):
+                xin = _block_desc(descs[b * n + k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4)
+                up = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
+                _block_grads(grads[b * n + k], tb + 5 * step * k, step, up, k > 0 or want_dx, blk, bn_acc + k * 2 * accb,
+                             ws_ptr, needs[b])
             ws_ptr += needs[b]
         check(lib().buctd_basic_branches_bwd(nb, n, descs, grads, main.cuda_stream, side.cuda_stream if use_side else None),
               "basic_branches_bwd")
-        if use_side:
-            for t in list(xs) + list(acts) + list(stats) + tmps + keep:
-                t.record_stream(side)
-            _queue_join()
-        elif _branch["on"]:
-            _queue_join()
-        for k in range(n - 1, -1, -1):
-            for b in range(nb):
-                w1, bn1, w2, bn2 = chains[b][k]
-                grad_done(bn2.weight, bn2.bias, w2)
-                grad_done(bn1.weight, bn1.bias, w1)
+        _native_bwd_done(side if use_side else None, list(xs) + list(acts) + list(stats) + tmps + keep,
+                         (chains[b][k] for k in range(n - 1, -1, -1) for b in range(nb)))
         return (None, None) + tuple(tmps[b][0, 4] if ctx.needs_input_grad[2 + b] else None for b in range(nb))
 
 

@@ -513,14 +513,15 @@ int buctd_gconv_wgrad_x6(int kind, int N, int H, int W, int Ci, int Co, const fl
                          int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------- BasicBlock sequences --- */
-/* The kernel sequence of one residual BasicBlock in train mode (pose_hrnet.py:28-57: stride 1, C -> C, no downsample,
- * bf16x6 math) behind ONE call per direction: conv1 (+ statistics), conv2 with bn1 + ReLU applied in its input staging
- * (+ statistics), bn2 + skip + ReLU - three launches, the BatchNorm statistics travel as accumulators (no finalize) - and
- * the mirrored backward (two BatchNorm-backward applies, two data gradients that also form the BatchNorm sums, two weight
- * gradients on `side_stream`; NULL: same stream).  Pure launch sequences of the entry points above (bit-identical
- * results); they exist because a dozen calls per block through a Python binding cost more host time than HRNet-W32 needs
- * GPU time.  acc: 2 * buctd_bn_acc_bytes(C) ZEROED bytes (forward statistics of conv1 | conv2); stat: 4 * C floats receiving
- * mean1, invstd1, mean2, invstd2 (saved for the backward).  running_* may be NULL. */
+/* The kernel sequences of residual BasicBlocks in train mode (pose_hrnet.py:28-57: stride 1, C -> C, no downsample, bf16x6
+ * math) behind ONE call per direction, buctd_basic_chain_*: n chained blocks (an HRNet branch, pose_hrnet.py:165-185), n = 1
+ * for a single block.  Per block: conv1 (+ statistics), conv2 with bn1 + ReLU applied in its input staging (+ statistics),
+ * bn2 + skip + ReLU - three launches, the BatchNorm statistics travel as accumulators (no finalize) - and the mirrored
+ * backward (two BatchNorm-backward applies, two data gradients that also form the BatchNorm sums, two weight gradients on
+ * `side_stream`; NULL: same stream).  Pure launch sequences of the entry points above (bit-identical results); they exist
+ * because a dozen calls per block through a Python binding cost more host time than HRNet-W32 needs GPU time.
+ * The structs below describe ONE block.  acc: 2 * buctd_bn_acc_bytes(C) ZEROED bytes (forward statistics of conv1 | conv2);
+ * stat: 4 * C floats receiving mean1, invstd1, mean2, invstd2 (saved for the backward).  running_* may be NULL. */
 typedef struct {
   int N, H, W, C;
   const float* x;
@@ -542,10 +543,8 @@ typedef struct {
   void* bn_acc;                         /* 2 * buctd_bn_acc_bytes(C) ZEROED bytes: backward sums of bn1 | bn2 */
   void* wg_ws; size_t wg_ws_bytes;      /* buctd_conv3x3_wgrad_bf16x6_workspace, used on `side_stream` */
 } buctd_basic_block_grads;
-int buctd_basic_block_fwd_train(const buctd_basic_block* b, void* stream);
-int buctd_basic_block_bwd(const buctd_basic_block* b, const buctd_basic_block_grads* g, void* stream, void* side_stream);
-/* n chained blocks (an HRNet branch, pose_hrnet.py:165-185) behind one call per direction: blocks[k].x = blocks[k-1].y,
- * grads[k].dy = grads[k+1].dx; the caller wires the pointers.  Same launches as n single calls. */
+/* blocks[k].x = blocks[k-1].y, grads[k].dy = grads[k+1].dx; the caller wires the pointers.  Inside a chain the sums of block
+ * k-1's bn2 backward are formed by block k's conv1 data gradient. */
 int buctd_basic_chain_fwd_train(int n, const buctd_basic_block* blocks, void* stream);
 int buctd_basic_chain_bwd(int n, const buctd_basic_block* blocks, const buctd_basic_block_grads* grads, void* stream,
                           void* side_stream);

@@ -313,3 +313,57 @@ def test_eval_bn_fold_cache_follows_training_updates(dev):
         bn.weight.mul_(1.5)                  # parameter update (version bump)
         d = run(False)
         assert (d - ref()).abs().max().item() <= 1e-4 and not torch.equal(c, d)
+
+
+@pytest.mark.parametrize("shape,track", [((3, 12, 10, 48), True), ((2, 16, 12, 32), True), ((2, 16, 12, 32), False),
+                                         ((2, 3, 3, 384), True)])
+def test_native_block_is_chain_of_one(dev, shape, track):
+    """The native BasicBlockFn is BasicChainFn with one block: the same launches on the same streams, so every output,
+    gradient and BatchNorm statistic is equal bit for bit - with an input gradient, without one (dx NULL), and on a second
+    backward that accumulates into existing .grad tensors (the acc_* flags)."""
+    import torch.nn as tnn
+    from buctd_amd import nn as bnn
+    from buctd_amd import ops
+    N, H, W, Cn = shape
+    g = torch.Generator().manual_seed(N * H + Cn)
+    x = torch.randn(N, H, W, Cn, generator=g).to(dev)
+    dy = torch.randn(N, H, W, Cn, generator=g).to(dev)
+    w0 = [(torch.randn(Cn, Cn, 3, 3, generator=g) * 0.08).contiguous(memory_format=torch.channels_last) for _ in range(2)]
+    bn0 = [(torch.rand(Cn, generator=g) + 0.5, torch.randn(Cn, generator=g) * 0.2) for _ in range(2)]
+    res = {}
+    for mode in ("block", "chain"):
+        w1, w2 = (tnn.Parameter(w.clone().to(dev)) for w in w0)
+        bns = []
+        for gamma, beta in bn0:
+            bn = bnn.BatchNorm2d(Cn, track_running_stats=track).to(dev).train()
+            with torch.no_grad():
+                bn.weight.copy_(gamma)
+                bn.bias.copy_(beta)
+            bns.append(bn)
+        bn1, bn2 = bns
+        params = [w1, w2, bn1.weight, bn1.bias, bn2.weight, bn2.bias]
+        assert ops.bn_in_fusable(shape, w1) and ops.bn_in_fusable(shape, w2) and ops.native_chain_ok(shape)
+        out = []
+        # fresh gradients with dx | a second backward into the existing .grad | no input gradient
+        for want_dx, fresh in ((True, True), (True, False), (False, True)):
+            if fresh:
+                for q in params:
+                    q.grad = None
+            xi = x.clone().requires_grad_(want_dx)
+            if mode == "block":
+                y = ops.BasicBlockFn.apply(xi, w1, bn1, w2, bn2)
+            else:
+                y = ops.BasicChainFn.apply(xi, w1, [(w1, bn1, w2, bn2)])
+            y.backward(dy)
+            torch.cuda.synchronize()
+            assert (xi.grad is not None) == want_dx
+            out += [y.detach().clone()] + ([xi.grad.clone()] if want_dx else []) + [q.grad.clone() for q in params]
+        if track:
+            for bn in bns:
+                bn.flush_batches()
+                assert int(bn.num_batches_tracked) == 3
+                out += [bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone()]
+        res[mode] = out
+    assert len(res["block"]) == len(res["chain"]) == 3 * 7 + 2 + (6 if track else 0)
+    for i, (a, b) in enumerate(zip(res["block"], res["chain"])):
+        assert torch.equal(a, b), f"tensor {i}: single block vs chain of one differ by {(a - b).abs().max().item():.3e}"

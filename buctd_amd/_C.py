@@ -116,6 +116,7 @@ SIGNATURES = {
     "buctd_conv2d_stats_groups": (_I, [_PD, _I, _PI, _PI]),
     "buctd_conv2d_wgrad_workspace": (_SZ, [_PD]),
     "buctd_conv2d_wgrad": (_I, [_PD, _P, _P, _P, _I, _P, _SZ, _P]),
+    "buctd_conv2d_plan": (_I, [_PD, _I, _I, _PI]),
     "buctd_matmul_workspace": (_SZ, [_PM]),
     "buctd_matmul": (_I, [_PM, _P, _P, _P, _P, _P, _SZ, _P]),
     "buctd_bn_finalize": (_I, [_P, _P, _I, _I, _L, _I, _F, _F, _P, _P, _P, _P, _P]),

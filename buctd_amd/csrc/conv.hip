@@ -494,8 +494,10 @@ static int check_desc(const buctd_conv_desc* d, const char* who) {
   return BUCTD_OK;
 }
 
+// geo != nullptr: no launch - only the tile this instance computes, {BM, BN, WM, MF} (buctd_conv2d_plan)
 template <class T, bool DGRAD, bool VEC>
-static void launch_conv(const ConvArgs& a, hipStream_t st) {
+static void launch_conv(const ConvArgs& a, hipStream_t st, int* geo) {
+  if (geo) { geo[0] = T::BM; geo[1] = T::BN; geo[2] = T::WM; geo[3] = T::MF; return; }
   dim3 grid(ceil_div(a.M, T::BM), ceil_div(a.OC, T::BN));
   if (DGRAD && a.par) {   // four parity classes; the (even, even) one is the largest
     const long mc = (long)a.N * ((a.RH + 1) / 2) * ((a.RW + 1) / 2);
@@ -520,20 +522,21 @@ static ConvTileSel conv_tile_select(int oc, long M, bool vec) {
   return small_m ? ConvTileSel{9, 64, 2, 2} : ConvTileSel{10, 128, 2, 4};                 // 64x128 / 128x128
 }
 
+// tile: the id of conv_tile_select
 template <bool DGRAD>
-static void dispatch_conv(const ConvArgs& a, bool vec, hipStream_t st) {
-  switch (conv_tile_select(a.OC, a.M, vec).id) {
-    case 0: launch_conv<TileCfg<4, 1, 2, 4>, DGRAD, false>(a, st); break;
-    case 1: launch_conv<TileCfg<4, 1, 4, 1>, DGRAD, true>(a, st); break;
-    case 2: launch_conv<TileCfg<4, 1, 2, 2>, DGRAD, true>(a, st); break;
-    case 3: launch_conv<TileCfg<4, 1, 1, 3>, DGRAD, true>(a, st); break;
-    case 4: launch_conv<TileCfg<4, 1, 2, 3>, DGRAD, true>(a, st); break;
-    case 5: launch_conv<TileCfg<4, 1, 1, 4>, DGRAD, true>(a, st); break;
-    case 6: launch_conv<TileCfg<4, 1, 2, 4>, DGRAD, true>(a, st); break;
-    case 7: launch_conv<TileCfg<2, 2, 2, 3>, DGRAD, true>(a, st); break;
-    case 8: launch_conv<TileCfg<2, 2, 4, 3>, DGRAD, true>(a, st); break;
-    case 9: launch_conv<TileCfg<2, 2, 2, 4>, DGRAD, true>(a, st); break;
-    default: launch_conv<TileCfg<2, 2, 4, 4>, DGRAD, true>(a, st); break;
+static void dispatch_conv(const ConvArgs& a, int tile, hipStream_t st, int* geo = nullptr) {
+  switch (tile) {
+    case 0: launch_conv<TileCfg<4, 1, 2, 4>, DGRAD, false>(a, st, geo); break;
+    case 1: launch_conv<TileCfg<4, 1, 4, 1>, DGRAD, true>(a, st, geo); break;
+    case 2: launch_conv<TileCfg<4, 1, 2, 2>, DGRAD, true>(a, st, geo); break;
+    case 3: launch_conv<TileCfg<4, 1, 1, 3>, DGRAD, true>(a, st, geo); break;
+    case 4: launch_conv<TileCfg<4, 1, 2, 3>, DGRAD, true>(a, st, geo); break;
+    case 5: launch_conv<TileCfg<4, 1, 1, 4>, DGRAD, true>(a, st, geo); break;
+    case 6: launch_conv<TileCfg<4, 1, 2, 4>, DGRAD, true>(a, st, geo); break;
+    case 7: launch_conv<TileCfg<2, 2, 2, 3>, DGRAD, true>(a, st, geo); break;
+    case 8: launch_conv<TileCfg<2, 2, 4, 3>, DGRAD, true>(a, st, geo); break;
+    case 9: launch_conv<TileCfg<2, 2, 2, 4>, DGRAD, true>(a, st, geo); break;
+    default: launch_conv<TileCfg<2, 2, 4, 4>, DGRAD, true>(a, st, geo); break;
   }
 }
 
@@ -1131,6 +1134,62 @@ static bool fwd_thin_ok(const buctd_conv_desc* d) {
          d->Wo == d->W && (long)d->N * d->H * d->W >= 4096;
 }
 
+// ---- routing ------------------------------------------------------------------------
+// Which kernel a forward / data-gradient call runs, decided by the descriptor and by WHICH optional inputs are present (the
+// BUCTD_CONV_* bits of buctd_hip.h).  buctd_conv2d_fwd / _dgrad and the host-only query buctd_conv2d_plan both call these.
+enum { FWD_GEMM = 0, FWD_THIN_PX4_C4 = 1, FWD_THIN_PX4_C8 = 2, FWD_THIN = 3, FWD_THIN_IN = 4 };
+enum { DGRAD_GEMM = 0, DGRAD_THIN_S2 = 1, DGRAD_THIN_PX4_TR = 2, DGRAD_THIN_PX4 = 3, DGRAD_THIN = 4 };
+struct ConvRoute {
+  int route;
+  ConvTileSel tile;   // route 0 only
+  bool vec;
+  int par;
+};
+
+static int fwd_route(const buctd_conv_desc* d, int flags, ConvRoute* r) {
+  const bool epilogue = (flags & (BUCTD_CONV_SCALE | BUCTD_CONV_RESIDUAL | BUCTD_CONV_RELU)) != 0;
+  const bool stats = (flags & BUCTD_CONV_STATS) != 0;
+  *r = ConvRoute{FWD_GEMM, ConvTileSel{0, 0, 0, 0}, false, 0};
+  if (fwd_thin_ok(d) && !epilogue && !stats) {     // plain conv (+ bias), <= 4 output channels
+    if ((d->Ci % THIN4_CH == 0 || d->Ci <= 4) && d->Co <= 3) r->route = d->Ci <= 4 ? FWD_THIN_PX4_C4 : FWD_THIN_PX4_C8;   // four pixels per thread (64 -> 3, 3 -> 3)
+    else r->route = FWD_THIN;
+    return BUCTD_OK;
+  }
+  // buctd_conv2d_stats_groups reports the thin kernel's grouping for these shapes whatever the epilogue: statistics together
+  // with an epilogue the thin kernel does not have would send the launch to the implicit-GEMM kernel, whose (more) groups
+  // overrun the caller's partials buffer
+  BUCTD_CHECK_ARG(!(fwd_thin_in_ok(d) && stats && epilogue),
+                  "buctd_conv2d_fwd: statistics of a thin-input convolution cannot be combined with scale / residual / relu");
+  if (fwd_thin_in_ok(d) && !epilogue) {            // 3 -> 64 3x3 of the preNet: lane = output channel
+    r->route = FWD_THIN_IN;
+    return BUCTD_OK;
+  }
+  r->vec = fwd_vec_ok(d);
+  r->tile = conv_tile_select(d->Co, d->N * d->Ho * d->Wo, r->vec);
+  return BUCTD_OK;
+}
+
+static int dgrad_route(const buctd_conv_desc* d, int flags, ConvRoute* r) {
+  const bool plain = (flags & (BUCTD_CONV_BIAS | BUCTD_CONV_STATS)) == 0;
+  *r = ConvRoute{DGRAD_GEMM, ConvTileSel{0, 0, 0, 0}, false, 0};
+  if (dgrad_thin_s2_ok(d) && plain) { r->route = DGRAD_THIN_S2; return BUCTD_OK; }             // stem conv1 behind a preNet: thin dx, stride 2
+  if (fwd_thin_ok(d) && plain) {
+    if (d->Ci <= 3) r->route = DGRAD_THIN_PX4_TR;                            // thin on both sides (3 -> 3 7x7): the forward kernel, filter transposed
+    else if (d->Ci % 16 == 0 && d->Co <= 3) r->route = DGRAD_THIN_PX4;       // 64 -> 3: four dx pixels per thread
+    else r->route = DGRAD_THIN;                                              // the preNet 7x7 with <= 4 output channels: thin dy, wide dx
+    return BUCTD_OK;
+  }
+  r->vec = dgrad_vec_ok(d);
+  r->tile = conv_tile_select(d->Ci, d->N * d->H * d->W, r->vec);
+  r->par = (d->stride == 2 && d->R == 3 && d->S == 3 && d->pad == 1 && !(flags & BUCTD_CONV_STATS) && r->vec) ? 1 : 0;
+  return BUCTD_OK;
+}
+
+static int conv_flags(const void* bias, const void* scale, const void* residual, int relu, const void* stats) {
+  return (bias ? BUCTD_CONV_BIAS : 0) | (scale ? BUCTD_CONV_SCALE : 0) | (residual ? BUCTD_CONV_RESIDUAL : 0) |
+         (relu ? BUCTD_CONV_RELU : 0) | (stats ? BUCTD_CONV_STATS : 0);
+}
+
 extern "C" int buctd_conv2d_stats_groups(const buctd_conv_desc* d, int transposed, int* ngroups,
                                          int* rows_per_group) {
   int rc = check_desc(d, "buctd_conv2d_stats_groups");
@@ -1160,14 +1219,16 @@ extern "C" int buctd_conv2d_fwd(const buctd_conv_desc* d, const float* x, const 
   if (rc) return rc;
   BUCTD_CHECK_ARG(x && w && y, "buctd_conv2d_fwd: null tensor pointer");
   BUCTD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "buctd_conv2d_fwd: scale and shift go together");
-  if (fwd_thin_ok(d) && !scale && !residual && !relu && !stats_partials) {     // plain conv (+ bias), <= 4 output channels
+  ConvRoute rt;
+  if ((rc = fwd_route(d, conv_flags(bias, scale, residual, relu, stats_partials), &rt))) return rc;
+  if (rt.route == FWD_THIN_PX4_C4 || rt.route == FWD_THIN_PX4_C8 || rt.route == FWD_THIN) {
     ThinFwdArgs ta;
     ta.x = x; ta.w = w; ta.bias = bias; ta.y = y;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Co = d->Co;
-    if ((d->Ci % THIN4_CH == 0 || d->Ci <= 4) && d->Co <= 3) {          // four pixels per thread (64 -> 3, 3 -> 3)
+    if (rt.route != FWD_THIN) {
       ta.tiles_y = ceil_div(d->H, THIN4_T); ta.tiles_x = ceil_div(d->W, THIN4_T);
       const dim3 grid(d->N * ta.tiles_y * ta.tiles_x);
-      if (d->Ci <= 4) launch_thin_px4<4, false>(ta, grid, (hipStream_t)stream);
+      if (rt.route == FWD_THIN_PX4_C4) launch_thin_px4<4, false>(ta, grid, (hipStream_t)stream);
       else launch_thin_px4<8, false>(ta, grid, (hipStream_t)stream);
       BUCTD_CHECK_LAUNCH("buctd_conv2d_fwd(thin, four pixels per thread)");
       return BUCTD_OK;
@@ -1177,12 +1238,7 @@ extern "C" int buctd_conv2d_fwd(const buctd_conv_desc* d, const float* x, const 
     BUCTD_CHECK_LAUNCH("buctd_conv2d_fwd(thin)");
     return BUCTD_OK;
   }
-  // buctd_conv2d_stats_groups reports the thin kernel's grouping for these shapes whatever the epilogue: statistics together
-  // with an epilogue the thin kernel does not have would send the launch to the implicit-GEMM kernel, whose (more) groups
-  // overrun the caller's partials buffer
-  BUCTD_CHECK_ARG(!(fwd_thin_in_ok(d) && stats_partials && (scale || residual || relu)),
-                  "buctd_conv2d_fwd: statistics of a thin-input convolution cannot be combined with scale / residual / relu");
-  if (fwd_thin_in_ok(d) && !scale && !residual && !relu) {      // 3 -> 64 3x3 of the preNet: lane = output channel
+  if (rt.route == FWD_THIN_IN) {
     ThinInArgs ta;
     ta.x = x; ta.w = w; ta.bias = bias; ta.y = y; ta.part = stats_partials;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Ho = d->Ho; ta.Wo = d->Wo;
@@ -1208,7 +1264,7 @@ extern "C" int buctd_conv2d_fwd(const buctd_conv_desc* d, const float* x, const 
   a.M = d->N * d->Ho * d->Wo; a.K = d->R * d->S * d->Ci;
   a.wRSCi = d->R * d->S * d->Ci; a.wCi = d->Ci;
   a.relu = relu; a.par = 0;
-  dispatch_conv<false>(a, fwd_vec_ok(d), (hipStream_t)stream);
+  dispatch_conv<false>(a, rt.tile.id, (hipStream_t)stream);
   BUCTD_CHECK_LAUNCH("buctd_conv2d_fwd");
   return BUCTD_OK;
 }
@@ -1218,7 +1274,9 @@ extern "C" int buctd_conv2d_dgrad(const buctd_conv_desc* d, const float* dy, con
   int rc = check_desc(d, "buctd_conv2d_dgrad");
   if (rc) return rc;
   BUCTD_CHECK_ARG(dy && w && dx, "buctd_conv2d_dgrad: null tensor pointer");
-  if (dgrad_thin_s2_ok(d) && !bias && !stats_partials) {  // stem conv1 behind a preNet: thin dx, stride 2
+  ConvRoute rt;
+  if ((rc = dgrad_route(d, conv_flags(bias, nullptr, nullptr, 0, stats_partials), &rt))) return rc;
+  if (rt.route == DGRAD_THIN_S2) {
     ThinS2Args ta;
     ta.dy = dy; ta.w = w; ta.dx = dx;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Co = d->Co; ta.Ho = d->Ho; ta.Wo = d->Wo;
@@ -1228,7 +1286,7 @@ extern "C" int buctd_conv2d_dgrad(const buctd_conv_desc* d, const float* dy, con
     BUCTD_CHECK_LAUNCH("buctd_conv2d_dgrad(thin s2)");
     return BUCTD_OK;
   }
-  if (fwd_thin_ok(d) && d->Ci <= 3 && !bias && !stats_partials) {      // thin on both sides (3 -> 3 7x7): the forward kernel, filter transposed
+  if (rt.route == DGRAD_THIN_PX4_TR) {
     ThinFwdArgs ta;
     ta.x = dy; ta.w = w; ta.bias = nullptr; ta.y = dx;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Co; ta.Co = d->Ci;
@@ -1237,7 +1295,7 @@ extern "C" int buctd_conv2d_dgrad(const buctd_conv_desc* d, const float* dy, con
     BUCTD_CHECK_LAUNCH("buctd_conv2d_dgrad(thin, four pixels per thread)");
     return BUCTD_OK;
   }
-  if (fwd_thin_ok(d) && !bias && !stats_partials && d->Ci % 16 == 0 && d->Co <= 3) {      // 64 -> 3: four dx pixels per thread
+  if (rt.route == DGRAD_THIN_PX4) {
     ThinDgradArgs ta;
     ta.dy = dy; ta.w = w; ta.dx = dx;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Co = d->Co;
@@ -1246,7 +1304,7 @@ extern "C" int buctd_conv2d_dgrad(const buctd_conv_desc* d, const float* dy, con
     BUCTD_CHECK_LAUNCH("buctd_conv2d_dgrad(thin, four pixels per thread)");
     return BUCTD_OK;
   }
-  if (fwd_thin_ok(d) && !bias && !stats_partials) {      // the preNet 7x7 with <= 4 output channels: thin dy, wide dx
+  if (rt.route == DGRAD_THIN) {
     ThinDgradArgs ta;
     ta.dy = dy; ta.w = w; ta.dx = dx;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Co = d->Co;
@@ -1264,8 +1322,8 @@ extern "C" int buctd_conv2d_dgrad(const buctd_conv_desc* d, const float* dy, con
   a.M = d->N * d->H * d->W; a.K = d->R * d->S * d->Co;
   a.wRSCi = d->R * d->S * d->Ci; a.wCi = d->Ci;
   a.relu = 0;
-  a.par = (d->stride == 2 && d->R == 3 && d->S == 3 && d->pad == 1 && !stats_partials && dgrad_vec_ok(d)) ? 1 : 0;
-  dispatch_conv<true>(a, dgrad_vec_ok(d), (hipStream_t)stream);
+  a.par = rt.par;
+  dispatch_conv<true>(a, rt.tile.id, (hipStream_t)stream);
   BUCTD_CHECK_LAUNCH("buctd_conv2d_dgrad");
   return BUCTD_OK;
 }
@@ -1573,20 +1631,51 @@ static void wgrad_plan(const buctd_conv_desc* d, int* bm, int* bn, int* nsplit, 
   *nsplit = (int)((Mpix + per - 1) / per);
 }
 
-extern "C" size_t buctd_conv2d_wgrad_workspace(const buctd_conv_desc* d) {
-  if (check_desc(d, "buctd_conv2d_wgrad_workspace")) return 0;
-  if (wgrad_thin_rows_ok(d)) return (size_t)thin_rows_wgs(d) * d->Co * d->R * d->S * d->Ci * sizeof(float);
-  if (wgrad_thin_ok(d)) return (size_t)thin_splits(d) * d->Co * d->R * d->S * d->Ci * sizeof(float);
-  if (fwd_thin_in_ok(d)) return (size_t)thin_in_wgs(d) * d->Co * d->R * d->S * d->Ci * sizeof(float);
-  int bm, bn, ns, pps;
-  wgrad_plan(d, &bm, &bn, &ns, &pps);
-  return (size_t)ns * d->Co * d->R * d->S * d->Ci * sizeof(float);
+// Which kernel a weight gradient runs and how its pixels are split; buctd_conv2d_wgrad, its workspace size and the host-only
+// query buctd_conv2d_plan all call this.  cfg (route 0): 0 = 64x64 scalar loads, 1..4 = 48 / 64 / 96 / 128 x 64 vector loads.
+enum { WGRAD_GEMM = 0, WGRAD_THIN_ROWS = 1, WGRAD_THIN = 2, WGRAD_THIN_IN = 3 };
+struct WgradRoute {
+  int route, cfg, nsplit, pps;
+  bool vec_reduce;    // slab reduction in float4 (Co * R * S * Ci a multiple of 4)
+};
+static WgradRoute wgrad_route(const buctd_conv_desc* d) {
+  int bm, bn;
+  WgradRoute r{WGRAD_GEMM, 0, 1, 0, false};
+  wgrad_plan(d, &bm, &bn, &r.nsplit, &r.pps);
+  const bool vec = (d->Ci % 4 == 0) && (d->Co % 4 == 0);
+  r.cfg = !vec ? 0 : bm == 48 ? 1 : bm == 64 ? 2 : bm == 96 ? 3 : 4;
+  r.vec_reduce = ((long)d->Co * d->R * d->S * d->Ci) % 4 == 0;
+  if (wgrad_thin_ok(d)) {
+    if (wgrad_thin_rows_ok(d)) { r.route = WGRAD_THIN_ROWS; r.nsplit = thin_rows_wgs(d); }   // 64 -> 3 7x7: rolling rows
+    else { r.route = WGRAD_THIN; r.nsplit = thin_splits(d); }
+  } else if (fwd_thin_in_ok(d)) {                                                             // 3 -> 64 3x3: lane = output channel
+    r.route = WGRAD_THIN_IN; r.nsplit = thin_in_wgs(d);
+  }
+  return r;
 }
 
+extern "C" size_t buctd_conv2d_wgrad_workspace(const buctd_conv_desc* d) {
+  if (check_desc(d, "buctd_conv2d_wgrad_workspace")) return 0;
+  return (size_t)wgrad_route(d).nsplit * d->Co * d->R * d->S * d->Ci * sizeof(float);
+}
+
+// geo != nullptr: no launch - only the tile this instance computes, {BM, BN, WM, MF} (buctd_conv2d_plan)
 template <class T, bool VEC>
-static void launch_wgrad(const WgradArgs& a, int nsplit, hipStream_t st) {
+static void launch_wgrad(const WgradArgs& a, int nsplit, hipStream_t st, int* geo) {
+  if (geo) { geo[0] = T::BM; geo[1] = T::BN; geo[2] = T::WM; geo[3] = T::MF; return; }
   dim3 grid(ceil_div(a.Co, T::BM), ceil_div(a.Ncols, T::BN), nsplit);
   hipLaunchKernelGGL((conv_wgrad_kernel<T, VEC>), grid, dim3(256), 0, st, a);
+}
+
+// cfg: WgradRoute::cfg
+static void dispatch_wgrad(const WgradArgs& a, int cfg, int nsplit, hipStream_t st, int* geo = nullptr) {
+  switch (cfg) {
+    case 0: launch_wgrad<TileCfg<2, 2, 2, 2>, false>(a, nsplit, st, geo); break;  // 64x64 generic
+    case 1: launch_wgrad<TileCfg<1, 4, 3, 1>, true>(a, nsplit, st, geo); break;   // 48x64
+    case 2: launch_wgrad<TileCfg<2, 2, 2, 2>, true>(a, nsplit, st, geo); break;   // 64x64
+    case 3: launch_wgrad<TileCfg<2, 2, 3, 2>, true>(a, nsplit, st, geo); break;   // 96x64
+    default: launch_wgrad<TileCfg<2, 2, 4, 2>, true>(a, nsplit, st, geo); break;  // 128x64
+  }
 }
 
 extern "C" int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, const float* dy, float* dw,
@@ -1594,20 +1683,16 @@ extern "C" int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, cons
   int rc = check_desc(d, "buctd_conv2d_wgrad");
   if (rc) return rc;
   BUCTD_CHECK_ARG(x && dy && dw, "buctd_conv2d_wgrad: null tensor pointer");
-  int bm, bn, ns, pps;
-  wgrad_plan(d, &bm, &bn, &ns, &pps);
-  const bool thin = wgrad_thin_ok(d);
-  const bool thin_rows = thin && wgrad_thin_rows_ok(d);  // 64 -> 3 7x7: rolling rows
-  const bool thin_in = !thin && fwd_thin_in_ok(d);       // 3 -> 64 3x3: lane = output channel
-  if (thin) ns = thin_splits(d);
-  if (thin_rows) ns = thin_rows_wgs(d);
-  if (thin_in) ns = thin_in_wgs(d);
+  const WgradRoute rt = wgrad_route(d);
+  const int ns = rt.nsplit;
   const size_t need = (size_t)ns * d->Co * d->R * d->S * d->Ci * sizeof(float);
   if (workspace == nullptr || workspace_bytes < need) {
     buctd_set_error("buctd_conv2d_wgrad: workspace %zu bytes < required %zu", workspace_bytes, need);
     return BUCTD_EWORKSPACE;
   }
-  if (thin_rows) {
+  hipStream_t st = (hipStream_t)stream;
+  const int ncols = d->R * d->S * d->Ci;
+  if (rt.route == WGRAD_THIN_ROWS) {
     ThinRowsArgs ta;
     ta.x = x; ta.dy = dy; ta.part = (float*)workspace;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Co = d->Co;
@@ -1617,34 +1702,20 @@ extern "C" int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, cons
     if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(conv_wgrad_thin_rows_kernel), (int)lds, attr_done,
                                              "buctd_conv2d_wgrad(thin rows)"))
       return rc;
-    hipLaunchKernelGGL(conv_wgrad_thin_rows_kernel, dim3(ns), dim3(256), lds, (hipStream_t)stream, ta);
+    hipLaunchKernelGGL(conv_wgrad_thin_rows_kernel, dim3(ns), dim3(256), lds, st, ta);
     BUCTD_CHECK_LAUNCH("buctd_conv2d_wgrad(thin rows)");
-  } else
-  if (thin) {
+  } else if (rt.route == WGRAD_THIN) {
     ThinArgs ta;
     ta.x = x; ta.dy = dy; ta.part = (float*)workspace;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Co = d->Co;
     ta.tiles_y = ceil_div(d->H, THIN_TH); ta.tiles_x = ceil_div(d->W, THIN_TW);
     ta.ntiles = d->N * ta.tiles_y * ta.tiles_x;
-    hipStream_t tst = (hipStream_t)stream;
-    const bool wide_dy = d->Co > d->Ci;
-    if (d->R == 7) {
-      if (wide_dy) hipLaunchKernelGGL((conv_wgrad_thin_kernel<7, true>), dim3(ns), dim3(256), 0, tst, ta);
-      else hipLaunchKernelGGL((conv_wgrad_thin_kernel<7, false>), dim3(ns), dim3(256), 0, tst, ta);
-    } else {
-      if (wide_dy) hipLaunchKernelGGL((conv_wgrad_thin_kernel<3, true>), dim3(ns), dim3(256), 0, tst, ta);
-      else hipLaunchKernelGGL((conv_wgrad_thin_kernel<3, false>), dim3(ns), dim3(256), 0, tst, ta);
-    }
+    // (a 3x3 here always has its thin side on dy: wgrad_thin_ok leaves 3 -> 64 to the other kernels)
+    if (d->R == 7 && d->Co > d->Ci) hipLaunchKernelGGL((conv_wgrad_thin_kernel<7, true>), dim3(ns), dim3(256), 0, st, ta);
+    else if (d->R == 7) hipLaunchKernelGGL((conv_wgrad_thin_kernel<7, false>), dim3(ns), dim3(256), 0, st, ta);
+    else hipLaunchKernelGGL((conv_wgrad_thin_kernel<3, false>), dim3(ns), dim3(256), 0, st, ta);
     BUCTD_CHECK_LAUNCH("buctd_conv2d_wgrad(thin)");
-  }
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.part = (float*)workspace;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
-  a.R = d->R; a.S = d->S; a.stride = d->stride; a.pad = d->pad;
-  a.Mpix = d->N * d->Ho * d->Wo; a.Ncols = d->R * d->S * d->Ci; a.pix_per_split = pps;
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec = (d->Ci % 4 == 0) && (d->Co % 4 == 0);
-  if (thin_in) {
+  } else if (rt.route == WGRAD_THIN_IN) {
     ThinInWgradArgs ta;
     ta.x = x; ta.dy = dy; ta.part = (float*)workspace;
     ta.N = d->N; ta.H = d->H; ta.W = d->W; ta.Ci = d->Ci; ta.Ho = d->Ho; ta.Wo = d->Wo;
@@ -1657,16 +1728,17 @@ extern "C" int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, cons
     }
     THIN_IN_WG(1) THIN_IN_WG(2) THIN_IN_WG(3) THIN_IN_WG(4)
 #undef THIN_IN_WG
-  } else
-  if (thin) {}                                                             // launched above
-  else if (!vec) launch_wgrad<TileCfg<2, 2, 2, 2>, false>(a, ns, st);     // 64x64 generic
-  else if (bm == 48) launch_wgrad<TileCfg<1, 4, 3, 1>, true>(a, ns, st);  // 48x64
-  else if (bm == 96) launch_wgrad<TileCfg<2, 2, 3, 2>, true>(a, ns, st);  // 96x64
-  else if (bm == 64) launch_wgrad<TileCfg<2, 2, 2, 2>, true>(a, ns, st);  // 64x64
-  else launch_wgrad<TileCfg<2, 2, 4, 2>, true>(a, ns, st);                // 128x64
+  } else {
+    WgradArgs a;
+    a.x = x; a.dy = dy; a.part = (float*)workspace;
+    a.N = d->N; a.H = d->H; a.W = d->W; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
+    a.R = d->R; a.S = d->S; a.stride = d->stride; a.pad = d->pad;
+    a.Mpix = d->N * d->Ho * d->Wo; a.Ncols = ncols; a.pix_per_split = rt.pps;
+    dispatch_wgrad(a, rt.cfg, ns, st);
+  }
   BUCTD_CHECK_LAUNCH("buctd_conv2d_wgrad");
-  const long n = (long)d->Co * a.Ncols;
-  if (n % 4 == 0) {
+  const long n = (long)d->Co * ncols;
+  if (rt.vec_reduce) {
     int blocks = ceil_div(n / 4, 32);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, dw, n, ns,
@@ -1678,5 +1750,44 @@ extern "C" int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, cons
                        accumulate, 1.0f);
   }
   BUCTD_CHECK_LAUNCH("buctd_conv2d_wgrad(reduce)");
+  return BUCTD_OK;
+}
+
+// ---- plan query -----------------------------------------------------------------------
+// What the three entry points above would launch, from the routing functions they call themselves; no launch, no device.
+extern "C" int buctd_conv2d_plan(const buctd_conv_desc* d, int direction, int flags, int* out) {
+  int rc = check_desc(d, "buctd_conv2d_plan");
+  if (rc) return rc;
+  BUCTD_CHECK_ARG(out != nullptr && direction >= 0 && direction <= 2, "buctd_conv2d_plan: null output or direction %d not 0..2",
+                  direction);
+  BUCTD_CHECK_ARG((flags & ~(BUCTD_CONV_BIAS | BUCTD_CONV_SCALE | BUCTD_CONV_RESIDUAL | BUCTD_CONV_RELU | BUCTD_CONV_STATS)) == 0,
+                  "buctd_conv2d_plan: unknown flag bits 0x%x", flags);
+  for (int i = 0; i < BUCTD_CONV_PLAN_INTS; ++i) out[i] = 0;
+  int geo[4] = {0, 0, 0, 0};
+  if (direction == 2) {
+    BUCTD_CHECK_ARG(flags == 0, "buctd_conv2d_plan: a weight gradient takes no flags");
+    const WgradRoute rt = wgrad_route(d);
+    out[0] = rt.route;
+    out[8] = rt.nsplit;
+    out[10] = rt.vec_reduce ? 1 : 0;
+    if (rt.route != WGRAD_GEMM) return BUCTD_OK;
+    dispatch_wgrad(WgradArgs{}, rt.cfg, rt.nsplit, nullptr, geo);
+    out[1] = rt.cfg;
+    out[6] = rt.cfg != 0;
+    out[9] = rt.pps;
+  } else {
+    BUCTD_CHECK_ARG(direction == 0 || (flags & (BUCTD_CONV_SCALE | BUCTD_CONV_RESIDUAL | BUCTD_CONV_RELU)) == 0,
+                    "buctd_conv2d_plan: the data gradient has no scale / residual / relu epilogue");
+    ConvRoute rt;
+    if ((rc = direction == 0 ? fwd_route(d, flags, &rt) : dgrad_route(d, flags, &rt))) return rc;
+    out[0] = rt.route;
+    if (rt.route != 0) return BUCTD_OK;
+    if (direction == 0) dispatch_conv<false>(ConvArgs{}, rt.tile.id, nullptr, geo);
+    else dispatch_conv<true>(ConvArgs{}, rt.tile.id, nullptr, geo);
+    out[1] = rt.tile.id;
+    out[6] = rt.vec ? 1 : 0;
+    out[7] = rt.par;
+  }
+  out[2] = geo[0]; out[3] = geo[1]; out[4] = geo[2]; out[5] = geo[3];
   return BUCTD_OK;
 }

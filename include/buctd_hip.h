@@ -61,6 +61,30 @@ int buctd_conv2d_stats_groups(const buctd_conv_desc* d, int transposed, int* ngr
 size_t buctd_conv2d_wgrad_workspace(const buctd_conv_desc* d);
 int buctd_conv2d_wgrad(const buctd_conv_desc* d, const float* x, const float* dy, float* dw, int accumulate,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* What the three entry points above would launch for this descriptor: no launch, no device (the query and the launches call
+ * the same routing functions).  direction: 0 buctd_conv2d_fwd, 1 buctd_conv2d_dgrad, 2 buctd_conv2d_wgrad.  flags: which
+ * optional inputs the call passes (the routing reads nothing else of them); scale / residual / relu are forward only, a
+ * weight gradient takes 0.  out[BUCTD_CONV_PLAN_INTS]:
+ *   [0] route   0 = the implicit-GEMM kernel, else a thin-channel kernel of that direction:
+ *               forward          1 / 2 four pixels per thread (<= 4 / a multiple of 8 input channels), 3 one pixel per
+ *                                thread, 4 thin input (<= 4 channels -> 64, 3x3)
+ *               data gradient    1 stride-2 thin dx, 2 thin on both sides, 3 four dx pixels per thread, 4 one per thread
+ *               weight gradient  1 rolling rows (64 -> <= 3, 7x7), 2 tile kernel, 3 thin input
+ *   route 0 only ([8] also for the thin weight gradients; everything else is 0 on a thin route):
+ *   [1] tile id 0..10 (forward / data gradient) or weight-gradient configuration (0 = 64x64 scalar loads, 1..4 = 48 / 64 /
+ *       96 / 128 x 64 vector loads)
+ *   [2] BM  [3] BN  [4] WM  [5] MF    the workgroup tile, its wavefront rows and 16-row fragments per wavefront
+ *   [6] vec    16-byte operand loads
+ *   [7] par    stride-2 data gradient split into four output-parity classes
+ *   [8] nsplit  [9] pix_per_split  [10] 1 = float4 slab reduction      (weight gradient)
+ * Returns what the launch would return for a descriptor or a flag combination it refuses. */
+#define BUCTD_CONV_BIAS 1
+#define BUCTD_CONV_SCALE 2 /* scale and shift */
+#define BUCTD_CONV_RESIDUAL 4
+#define BUCTD_CONV_RELU 8
+#define BUCTD_CONV_STATS 16
+#define BUCTD_CONV_PLAN_INTS 11
+int buctd_conv2d_plan(const buctd_conv_desc* d, int direction, int flags, int* out);
 
 /* 3x3 / stride 1 / pad 1 convolution on the bf16 matrix cores with split-fp32 operands, fp32 accumulate
  * (csrc/conv3x3.hip).  Replaces the BasicBlock convs of pose_hrnet.py:28-57 (nn.Conv2d(k=3, s=1, p=1, bias=False)

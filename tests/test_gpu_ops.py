@@ -31,6 +31,9 @@ def close(a, b, tol, what=""):
     assert err <= tol * scale, f"{what}: max abs err {err:.3e} (scale {scale:.3e}) > tol {tol}"
 
 
+# These cases run in the default math mode (bf16x6): the 3x3 / s1 / p1 ones go to conv3x3.hip and the 1x1 / even-size 3x3 / s2
+# ones with gathered-kernel channel counts to conv_gather_x6.hip; only the rest (7x7, 4x4 / s2, odd sizes, 3 / 14 / 17 channels)
+# reaches the exact-fp32 implicit-GEMM kernels of conv.hip.  Those are tested tile by tile in test_gpu_conv2d_fp32.py.
 CONV_CASES = [
     # N, H, W, Ci, Co, k, stride, pad, bias
     (2, 24, 18, 48, 48, 3, 1, 1, False),

@@ -119,6 +119,7 @@ SIGNATURES = {
     "buctd_conv2d_plan": (_I, [_PD, _I, _I, _PI]),
     "buctd_matmul_workspace": (_SZ, [_PM]),
     "buctd_matmul": (_I, [_PM, _P, _P, _P, _P, _P, _SZ, _P]),
+    "buctd_matmul_plan": (_I, [_PM, _P, _P, _PI]),
     "buctd_bn_finalize": (_I, [_P, _P, _I, _I, _L, _I, _F, _F, _P, _P, _P, _P, _P]),
     "buctd_conv3x3_bf16x3_supported": (_I, [_I, _I, _I, _I, _I]),
     "buctd_conv3x3_bf16x3_stats_groups": (_I, [_I, _I, _I, _I, _I, _PI, _PI]),

@@ -236,23 +236,30 @@ __global__ __launch_bounds__(256) void matmul_splitk_reduce(const float* __restr
   }
 }
 
+// geo != nullptr: no launch - only the tile this instance computes, {BM, BN, WM, MF} (buctd_matmul_plan)
 template <class T, bool ACOL, bool BCOL, bool VEC>
-static void launch_mm(const MMArgs& a, int nbatch, hipStream_t st) {
+static void launch_mm(const MMArgs& a, int nbatch, hipStream_t st, int* geo) {
+  if (geo) { geo[0] = T::BM; geo[1] = T::BN; geo[2] = T::WM; geo[3] = T::MF; return; }
   dim3 grid(ceil_div(a.M, T::BM), ceil_div(a.N, T::BN), nbatch * a.nsplit);
   hipLaunchKernelGGL((matmul_kernel<T, ACOL, BCOL, VEC>), grid, dim3(256), 0, st, a);
 }
 
+// tile: the id of mm_route
 template <bool ACOL, bool BCOL>
-static void dispatch_mm(const MMArgs& a, int nbatch, bool vec, hipStream_t st) {
-  if (!vec) {
-    launch_mm<TileCfg<4, 1, 2, 4>, ACOL, BCOL, false>(a, nbatch, st);  // 128x64 generic
-  } else if (a.N <= 48) {
-    launch_mm<TileCfg<4, 1, 2, 3>, ACOL, BCOL, true>(a, nbatch, st);   // 128x48
-  } else if (a.N % 96 == 0 && a.N % 128 != 0) {
-    launch_mm<TileCfg<2, 2, 4, 3>, ACOL, BCOL, true>(a, nbatch, st);   // 128x96
-  } else {
-    launch_mm<TileCfg<2, 2, 4, 4>, ACOL, BCOL, true>(a, nbatch, st);   // 128x128
+static void dispatch_mm(const MMArgs& a, int nbatch, int tile, hipStream_t st, int* geo = nullptr) {
+  switch (tile) {
+    case 0: launch_mm<TileCfg<4, 1, 2, 4>, ACOL, BCOL, false>(a, nbatch, st, geo); break;  // 128x64 generic
+    case 1: launch_mm<TileCfg<4, 1, 2, 3>, ACOL, BCOL, true>(a, nbatch, st, geo); break;   // 128x48
+    case 2: launch_mm<TileCfg<2, 2, 4, 3>, ACOL, BCOL, true>(a, nbatch, st, geo); break;   // 128x96
+    default: launch_mm<TileCfg<2, 2, 4, 4>, ACOL, BCOL, true>(a, nbatch, st, geo); break;  // 128x128
   }
+}
+
+static void dispatch_layouts(const buctd_matmul_desc* d, const MMArgs& a, int tile, hipStream_t st, int* geo = nullptr) {
+  if (d->a_layout == 0 && d->b_layout == 0) dispatch_mm<false, false>(a, d->batch, tile, st, geo);
+  else if (d->a_layout == 0 && d->b_layout == 1) dispatch_mm<false, true>(a, d->batch, tile, st, geo);
+  else if (d->a_layout == 1 && d->b_layout == 0) dispatch_mm<true, false>(a, d->batch, tile, st, geo);
+  else dispatch_mm<true, true>(a, d->batch, tile, st, geo);
 }
 
 static void mm_split_plan(const buctd_matmul_desc* d, int* nsplit, int* kps) {
@@ -271,6 +278,35 @@ static void mm_split_plan(const buctd_matmul_desc* d, int* nsplit, int* kps) {
   *nsplit = (int)((d->K + per - 1) / per);
 }
 
+// What a call launches: the descriptor checks, 16-byte operand loads or not (A and B only for their alignment), the tile
+// (0 = 128x64 scalar loads, 1 = 128x48, 2 = 128x96, 3 = 128x128 vector loads) and the split of K.  buctd_matmul and the
+// host-only query buctd_matmul_plan both call this.
+struct MMRoute {
+  int tile, vec, nsplit, k_per_split;
+};
+
+static int mm_route(const buctd_matmul_desc* d, const void* A, const void* B, MMRoute* r) {
+  BUCTD_CHECK_ARG(d && A && B, "buctd_matmul: null argument");
+  BUCTD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->batch > 0, "buctd_matmul: non-positive dimension");
+  BUCTD_CHECK_ARG(d->Kc > 0 && d->Nc > 0, "buctd_matmul: Kc/Nc must be positive (use K / N for a single group)");
+  BUCTD_CHECK_ARG(d->a_layout == 0 || d->a_layout == 1, "buctd_matmul: a_layout must be 0 (rows) or 1 (cols)");
+  BUCTD_CHECK_ARG(d->b_layout == 0 || d->b_layout == 1, "buctd_matmul: b_layout must be 0 (rows) or 1 (cols)");
+  auto mult4 = [](long v) { return (v & 3) == 0; };
+  bool vec = mult4(d->lda) && mult4(d->ldb) && mult4(d->stride_a) && mult4(d->stride_b) &&
+             (((uintptr_t)A & 15) == 0) && (((uintptr_t)B & 15) == 0);
+  const bool rows_used = d->a_layout == 0 || d->b_layout == 0;
+  if (rows_used) vec = vec && (d->Kc % 4 == 0) && mult4(d->group_stride_a) && mult4(d->group_stride_bk) && (d->K % 4 == 0);
+  if (d->a_layout == 1) vec = vec && (d->M % 4 == 0);
+  if (d->b_layout == 1) vec = vec && (d->Nc % 4 == 0) && mult4(d->group_stride_bn) && (d->N % 4 == 0);
+  r->vec = vec ? 1 : 0;
+  if (!vec) r->tile = 0;
+  else if (d->N <= 48) r->tile = 1;
+  else if (d->N % 96 == 0 && d->N % 128 != 0) r->tile = 2;
+  else r->tile = 3;
+  mm_split_plan(d, &r->nsplit, &r->k_per_split);
+  return BUCTD_OK;
+}
+
 extern "C" size_t buctd_matmul_workspace(const buctd_matmul_desc* d) {
   if (!d) return 0;
   int ns, kps;
@@ -279,13 +315,28 @@ extern "C" size_t buctd_matmul_workspace(const buctd_matmul_desc* d) {
   return (size_t)d->batch * ns * d->M * d->N * sizeof(float);
 }
 
+extern "C" int buctd_matmul_plan(const buctd_matmul_desc* d, const void* A, const void* B, int* out) {
+  BUCTD_CHECK_ARG(out != nullptr, "buctd_matmul_plan: null output");
+  for (int i = 0; i < BUCTD_MATMUL_PLAN_INTS; ++i) out[i] = 0;
+  MMRoute r;
+  const int rc = mm_route(d, A, B, &r);
+  if (rc != BUCTD_OK) return rc;
+  int geo[4] = {0, 0, 0, 0};
+  dispatch_layouts(d, MMArgs{}, r.tile, nullptr, geo);
+  out[0] = r.tile;
+  out[1] = geo[0]; out[2] = geo[1]; out[3] = geo[2]; out[4] = geo[3];
+  out[5] = r.vec;
+  out[6] = r.nsplit;
+  out[7] = r.k_per_split;
+  return BUCTD_OK;
+}
+
 extern "C" int buctd_matmul(const buctd_matmul_desc* d, const float* A, const float* B, const float* bias, float* C,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  BUCTD_CHECK_ARG(d && A && B && C, "buctd_matmul: null argument");
-  BUCTD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->batch > 0, "buctd_matmul: non-positive dimension");
-  BUCTD_CHECK_ARG(d->Kc > 0 && d->Nc > 0, "buctd_matmul: Kc/Nc must be positive (use K / N for a single group)");
-  BUCTD_CHECK_ARG(d->a_layout == 0 || d->a_layout == 1, "buctd_matmul: a_layout must be 0 (rows) or 1 (cols)");
-  BUCTD_CHECK_ARG(d->b_layout == 0 || d->b_layout == 1, "buctd_matmul: b_layout must be 0 (rows) or 1 (cols)");
+  MMRoute r;
+  const int rc = mm_route(d, A, B, &r);
+  if (rc != BUCTD_OK) return rc;
+  BUCTD_CHECK_ARG(C, "buctd_matmul: null argument");
   MMArgs a;
   a.A = A; a.B = B; a.C = C; a.bias = bias;
   a.M = d->M; a.N = d->N; a.K = d->K;
@@ -295,16 +346,9 @@ extern "C" int buctd_matmul(const buctd_matmul_desc* d, const float* A, const fl
   a.Nc = d->Nc; a.gsBn = d->group_stride_bn; a.gsCn = d->group_stride_c;
   a.alpha = d->alpha;
   a.bias_axis = d->bias_axis;
-  mm_split_plan(d, &a.nsplit, &a.k_per_split);
+  a.nsplit = r.nsplit;
+  a.k_per_split = r.k_per_split;
   hipStream_t st = (hipStream_t)stream;
-
-  auto mult4 = [](long v) { return (v & 3) == 0; };
-  bool vec = mult4(d->lda) && mult4(d->ldb) && mult4(d->stride_a) && mult4(d->stride_b) &&
-             (((uintptr_t)A & 15) == 0) && (((uintptr_t)B & 15) == 0);
-  const bool rows_used = d->a_layout == 0 || d->b_layout == 0;
-  if (rows_used) vec = vec && (d->Kc % 4 == 0) && mult4(d->group_stride_a) && mult4(d->group_stride_bk) && (d->K % 4 == 0);
-  if (d->a_layout == 1) vec = vec && (d->M % 4 == 0);
-  if (d->b_layout == 1) vec = vec && (d->Nc % 4 == 0) && mult4(d->group_stride_bn) && (d->N % 4 == 0);
 
   MMArgs k = a;
   if (a.nsplit > 1) {
@@ -316,10 +360,7 @@ extern "C" int buctd_matmul(const buctd_matmul_desc* d, const float* A, const fl
     k.C = (float*)workspace;
     k.sCb = (long)a.nsplit * d->M * d->N;
   }
-  if (d->a_layout == 0 && d->b_layout == 0) dispatch_mm<false, false>(k, d->batch, vec, st);
-  else if (d->a_layout == 0 && d->b_layout == 1) dispatch_mm<false, true>(k, d->batch, vec, st);
-  else if (d->a_layout == 1 && d->b_layout == 0) dispatch_mm<true, false>(k, d->batch, vec, st);
-  else dispatch_mm<true, true>(k, d->batch, vec, st);
+  dispatch_layouts(d, k, r.tile, st);
   BUCTD_CHECK_LAUNCH("buctd_matmul");
   if (a.nsplit > 1) {
     const long total = (long)d->batch * d->M * d->N;

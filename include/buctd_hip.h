@@ -263,6 +263,16 @@ typedef struct {
 size_t buctd_matmul_workspace(const buctd_matmul_desc* d);
 int buctd_matmul(const buctd_matmul_desc* d, const float* A, const float* B, const float* bias, float* C,
                  void* workspace, size_t workspace_bytes, void* stream);
+/* What buctd_matmul would launch for this descriptor and these operand pointers: no launch, no device (the query and the
+ * launch call the same routing function).  A and B count only for their alignment (16-byte operand loads need 16-byte
+ * aligned pointers) and are never dereferenced.  out[BUCTD_MATMUL_PLAN_INTS]:
+ *   [0] tile id   0 = 128x64 scalar loads, 1 = 128x48, 2 = 128x96, 3 = 128x128 (16-byte loads)
+ *   [1] BM  [2] BN  [3] WM  [4] MF    the workgroup tile, its wavefront rows and 16-row fragments per wavefront
+ *   [5] vec    16-byte operand loads
+ *   [6] nsplit  [7] k_per_split       split-K: nsplit > 1 needs buctd_matmul_workspace(d) = batch*nsplit*M*N*4 bytes
+ * Returns what buctd_matmul would return for a descriptor it refuses. */
+#define BUCTD_MATMUL_PLAN_INTS 8
+int buctd_matmul_plan(const buctd_matmul_desc* d, const void* A, const void* B, int* out);
 
 /* ------------------------------------------------------------- batchnorm --- */
 /* Combine Welford partials -> mean, invstd (biased var, eps) and update running stats

@@ -1,5 +1,8 @@
-// Generative pose synthesis on the device (reference lib/dataset/pose_synthesis.py:234-817: the
+// Generative pose synthesis on the device (reference lib/dataset/pose_synthesis.py:6-817: the
 // training-time condition of every "generative sampling" recipe, ~34 ms of numpy per person on a CPU worker).
+// One kernel for the three variants of the reference (coco, crowdpose and the generic one every other data set takes,
+// synthesize_pose_fish): they differ in buctd_synth_tables only - sigmas, symmetric pairs, per-joint probability
+// classes, the probability ladders and the num_valid / num_overlap thresholds that pick a ladder's row.
 //
 // One wavefront per (person, joint).  The five error types of the reference (jitter, miss, inversion, swap, good) each
 // propose N candidates on a ring around a source key point and keep those far enough from the other sources; one
@@ -225,10 +228,12 @@ __global__ __launch_bounds__(64) void synth_pose_kernel(SynthArgs a) {
   single(61, 62, 0, SY_N / 4, 0.0, d85, 0, 0, -1, 4);                       // good
 
   const int ov = a.num_overlap[b];
-  const double p_jit = a.t.jitter_p[nv <= 10 ? 0 : 1][a.t.jitter_cls[j]];
-  const double p_miss = a.t.miss_p[nv <= 5 ? 0 : (nv <= 10 ? 1 : 2)][a.t.miss_cls[j]];
+  // which row of a ladder: the data set's thresholds (buctd_synth_tables)
+  const double p_jit = a.t.jitter_p[nv <= a.t.jitter_nv ? 0 : 1][a.t.jitter_cls[j]];
+  const double p_miss = a.t.miss_p[nv <= a.t.miss_nv[0] ? 0 : (nv <= a.t.miss_nv[1] ? 1 : 2)][a.t.miss_cls[j]];
   const double p_inv = a.t.inv_p[a.t.inv_cls[j]];
-  const bool crowded = (nv <= 10 && ov > 0) || (nv <= 15 && ov >= 3);
+  const bool crowded = (nv <= a.t.crowd_nv[0] && ov >= a.t.crowd_ov[0]) ||
+                       (nv <= a.t.crowd_nv[1] && ov >= a.t.crowd_ov[1]);
   const double p_swap = a.t.swap_p[crowded ? 0 : 1][a.t.swap_cls[j]];
   const double p_good = 1.0 - (p_jit + p_miss + p_inv + p_swap);
   double pr[5] = {have[0] ? p_jit : 0.0, have[1] ? p_miss : 0.0, have[2] ? p_inv : 0.0, have[3] ? p_swap : 0.0,

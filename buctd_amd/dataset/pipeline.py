@@ -126,10 +126,16 @@ class DeviceSamplePipeline:
     If any record of the batch has use_bu_bbox=True its crop box depends on the synthesized pose: the batch then takes
     a host fallback - one copy of the synthesized poses to the host, then geometry() and render() as without synthesis
     (same result, slower; meta['cond_joints'] / ['cond_joints_vis'] are host tensors there).  With is_train=False the
-    flag changes nothing.  Without the flag a conditional train pipeline refuses records that lack 'cond_joints'."""
+    flag changes nothing.  Without the flag a conditional train pipeline refuses records that lack 'cond_joints'.
+    The variant of the synthesis is cfg.DATASET.DATASET's: 'coco', 'crowdpose', or the generic one for any other name
+    (fish, marmosets, multimouse, a custom data set; pose_synthesis.py:798-816).
+
+    joints_weight ([K] or [K, 1], the data set class's self.joints_weight): with cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT
+    every target_weight is multiplied by it on the device (JointsDataset.py:450-451); without the flag, or with None,
+    it is not looked at."""
 
     def __init__(self, cfg, flip_pairs=(), upper_body_ids=(), kpt_colors=None, mean=(0.485, 0.456, 0.406),
-                 std=(0.229, 0.224, 0.225), is_train=False, seed=0):
+                 std=(0.229, 0.224, 0.225), is_train=False, seed=0, joints_weight=None):
         self.cfg = cfg
         self.is_train = is_train
         self.num_joints = cfg.MODEL.NUM_JOINTS
@@ -160,6 +166,13 @@ class DeviceSamplePipeline:
         self.seed = int(seed)
         self.synth_calls = 0
         self._pair_dev = {}
+        self.joints_weight = None
+        if joints_weight is not None and bool(getattr(getattr(cfg, "LOSS", None), "USE_DIFFERENT_JOINTS_WEIGHT", False)):
+            jw = np.asarray(joints_weight, dtype=np.float32)
+            if jw.shape not in ((self.num_joints,), (self.num_joints, 1)):
+                raise ValueError(f"joints_weight has shape {jw.shape}, MODEL.NUM_JOINTS is {self.num_joints}")
+            self.joints_weight = np.ascontiguousarray(jw.reshape(1, self.num_joints, 1))
+        self._weight_dev = {}
 
     # ---- host-side scalar geometry (reference expressions, float64) -----------------------------------------
     def half_body_transform(self, joints, joints_vis):
@@ -318,6 +331,12 @@ class DeviceSamplePipeline:
         vis = np.stack([g["joints_vis"][:, 0] for g in geos]).astype(np.float32)
         target, weight = ops.gaussian_target(torch.from_numpy(jt).to(dev), torch.from_numpy(vis).to(dev),
                                              self.heatmap_size, self.image_size, self.sigma)
+        if self.joints_weight is not None:
+            # np.multiply(target_weight, self.joints_weight) of JointsDataset.py:450-451, the batch at once
+            jw = self._weight_dev.get((dev, B))
+            if jw is None:
+                jw = self._weight_dev[(dev, B)] = torch.from_numpy(np.repeat(self.joints_weight, B, axis=0)).to(dev)
+            weight = ops.mul(weight, jw)
         if cc:
             # np.array(kpts).astype(int) truncates in float64 (JointsDataset.py:521): hand the kernel the integers
             cjt = cond_trunc

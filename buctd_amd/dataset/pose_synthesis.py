@@ -1,6 +1,7 @@
 """Generative pose synthesis on the device - drop-in for reference lib/dataset/pose_synthesis.py:779-817
-(synthesize_pose and its coco / crowdpose variants 234-775): the training-time condition of every "generative
-sampling" recipe (DATASET.SYNTHESIS_POSE True).  synthesize_pose keeps the reference signature for one person;
+(synthesize_pose and its variants: coco 505-775, crowdpose 234-501, and synthesize_pose_fish 6-231, the generic one that
+every other DATASET.DATASET takes - fish, marmosets, multimouse, a custom data set): the training-time condition of every
+"generative sampling" recipe (DATASET.SYNTHESIS_POSE True).  synthesize_pose keeps the reference signature for one person;
 synthesize_pose_batch does a whole batch in one kernel launch (one wavefront per person and joint)."""
 import ctypes as C
 import functools
@@ -17,13 +18,28 @@ class _Tables(C.Structure):
     _fields_ = [("sigmas", C.c_double * _MAXK), ("pair", C.c_int * _MAXK), ("jitter_cls", C.c_int * _MAXK),
                 ("miss_cls", C.c_int * _MAXK), ("inv_cls", C.c_int * _MAXK), ("swap_cls", C.c_int * _MAXK),
                 ("jitter_p", (C.c_double * 3) * 2), ("miss_p", (C.c_double * 3) * 3), ("inv_p", C.c_double * 3),
-                ("swap_p", (C.c_double * 3) * 2), ("out_vis", C.c_double)]
+                ("swap_p", (C.c_double * 3) * 2), ("out_vis", C.c_double), ("jitter_nv", C.c_int),
+                ("miss_nv", C.c_int * 2), ("crowd_nv", C.c_int * 2), ("crowd_ov", C.c_int * 2)]
+
+
+# The probability ladders [row][class] and the thresholds that pick the row: jitter row 0 while num_valid <= jitter_nv;
+# miss row 0 / 1 while num_valid <= miss_nv[0] / [1]; swap row 0 when "crowded" = for one of the two (nv, ov) pairs
+# num_valid <= nv and num_overlap >= ov.  coco and crowdpose share theirs (pose_synthesis.py:56-72, 91-112, 146-152,
+# 176-190 / 561-575, 597-618, 651-657, 680-694: `num_overlap > 0` is `>= 1`).
+_HUMAN_LADDERS = dict(jitter_p=[[0.15, 0.20, 0.25], [0.10, 0.15, 0.20]],
+                      miss_p=[[0.15, 0.20, 0.25], [0.10, 0.13, 0.15], [0.02, 0.05, 0.10]], inv_p=[0.01, 0.03, 0.06],
+                      swap_p=[[0.02, 0.15, 0.10], [0.01, 0.06, 0.03]],
+                      jitter_nv=10, miss_nv=(5, 10), crowd=((10, 1), (15, 3)))
+# synthesize_pose_fish (pose_synthesis.py:61-64, 86-91, 126, 150-153): one class, other thresholds
+_GENERIC_LADDERS = dict(jitter_p=[[0.20] * 3, [0.15] * 3], miss_p=[[0.20] * 3, [0.13] * 3, [0.05] * 3], inv_p=[0.03] * 3,
+                        swap_p=[[0.10] * 3, [0.04] * 3], jitter_nv=4, miss_nv=(2, 4), crowd=((4, 1), (5, 1)))
 
 
 def _joint_classes(dataset, k):
     """Per-joint probability classes of the reference's if / elif ladders (pose_synthesis.py:56-72, 91-112, 146-152,
     176-190 for crowdpose; 561-575, 597-618, 651-657, 680-694 for coco).  Crowdpose joints 12 and 13 fall through the
-    jitter ladder and inherit what joint 11 left in the variable: class 0."""
+    jitter ladder and inherit what joint 11 left in the variable: class 0.  Any other data set is the generic variant
+    (pose_synthesis.py:798-800, 815-816): k joints of sigma 0.1, no symmetry, no classes, visibility column 0 (line 229)."""
     if dataset == "coco":
         jit = [0 if (j == 0 or 13 <= j <= 16) else (1 if 1 <= j <= 10 else 2) for j in range(k)]
         miss = [0 if j <= 4 else (1 if j in (5, 6, 15, 16) else 2) for j in range(k)]
@@ -41,16 +57,21 @@ def _joint_classes(dataset, k):
         sig = [.79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89, .79, .79]
         vis = 0.0
     else:
-        raise NotImplementedError("pose synthesis: the BUCTD recipes use the coco and crowdpose variants")
+        jit = miss = inv = swap = [0] * k
+        sym, sig, vis = [], [1.] * k, 0.0
     return jit, miss, inv, swap, sym, np.array(sig) / 10.0, vis
 
 
 @functools.lru_cache(maxsize=None)
 def make_tables(dataset, num_joints):
-    """Per-dataset constants of the kernel (buctd_synth_tables), built once per (dataset, K); callers do not modify it."""
+    """Per-dataset constants of the kernel (buctd_synth_tables), built once per (dataset, K); callers do not modify it.
+    dataset: 'coco', 'crowdpose', or any other name for the generic variant with num_joints (1...32) key points."""
+    if not 1 <= num_joints <= _MAXK:
+        raise ValueError(f"pose synthesis takes 1 to {_MAXK} key points, MODEL.NUM_JOINTS is {num_joints}")
     jit, miss, inv, swap, sym, sig, vis = _joint_classes(dataset, num_joints)
-    if len(sig) != num_joints or num_joints > _MAXK:
+    if len(sig) != num_joints:
         raise ValueError(f"{dataset} has {len(sig)} key points, MODEL.NUM_JOINTS is {num_joints}")
+    lad = _HUMAN_LADDERS if dataset in ("coco", "crowdpose") else _GENERIC_LADDERS
     t = _Tables()
     pair = [-1] * _MAXK
     for a, b in sym:
@@ -62,18 +83,17 @@ def make_tables(dataset, num_joints):
         t.miss_cls[j] = miss[j] if j < num_joints else 0
         t.inv_cls[j] = inv[j] if j < num_joints else 0
         t.swap_cls[j] = swap[j] if j < num_joints else 0
-    for r, row in enumerate([[0.15, 0.20, 0.25], [0.10, 0.15, 0.20]]):
-        for c, v in enumerate(row):
-            t.jitter_p[r][c] = v
-    for r, row in enumerate([[0.15, 0.20, 0.25], [0.10, 0.13, 0.15], [0.02, 0.05, 0.10]]):
-        for c, v in enumerate(row):
-            t.miss_p[r][c] = v
-    for c, v in enumerate([0.01, 0.03, 0.06]):
+    for name in ("jitter_p", "miss_p", "swap_p"):
+        for r, row in enumerate(lad[name]):
+            for c, v in enumerate(row):
+                getattr(t, name)[r][c] = v
+    for c, v in enumerate(lad["inv_p"]):
         t.inv_p[c] = v
-    for r, row in enumerate([[0.02, 0.15, 0.10], [0.01, 0.06, 0.03]]):
-        for c, v in enumerate(row):
-            t.swap_p[r][c] = v
     t.out_vis = vis
+    t.jitter_nv = lad["jitter_nv"]
+    for i in range(2):
+        t.miss_nv[i] = lad["miss_nv"][i]
+        t.crowd_nv[i], t.crowd_ov[i] = lad["crowd"][i]
     return t
 
 

@@ -722,7 +722,7 @@ int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd
                         const int* pair_device, int B, int K, double* out_joints, double* out_vis, float* out_trunc,
                         void* stream);
 
-/* Generative pose synthesis (dataset/pose_synthesis.py:234-817, called from JointsDataset.py:202-215): for every person
+/* Generative pose synthesis (dataset/pose_synthesis.py:6-817, called from JointsDataset.py:202-215): for every person
  * and joint one of the error types jitter / miss / inversion / swap / good is drawn and a key point proposed
  * accordingly.  joints, estimated [B][K][3] and near_joints [B][M][K][3] (neighbours; visibility 0 = absent) are float64
  * device arrays, area [B] float64, num_overlap [B] int; out [B][K][3].  Randomness: a counter-based generator keyed by
@@ -731,11 +731,16 @@ typedef struct {
   double sigmas[32];
   int pair[32];                /* symmetric partner of a joint, -1 = none (kps_symmetry) */
   int jitter_cls[32], miss_cls[32], inv_cls[32], swap_cls[32];
-  double jitter_p[2][3];       /* [num_valid <= 10 | else][class] */
-  double miss_p[3][3];         /* [num_valid <= 5 | <= 10 | else][class] */
+  double jitter_p[2][3];       /* [num_valid <= jitter_nv | else][class] */
+  double miss_p[3][3];         /* [num_valid <= miss_nv[0] | <= miss_nv[1] | else][class] */
   double inv_p[3];
   double swap_p[2][3];         /* [crowded | else][class] */
-  double out_vis;              /* third column of a synthesized joint: 1 (coco) / 0 (crowdpose) */
+  double out_vis;              /* third column of a synthesized joint: 1 (coco) / 0 (crowdpose, generic) */
+  /* which row of a ladder a person takes (coco / crowdpose: 10; 5, 10; (10, 1), (15, 3) - the generic variant of every
+   * other data set, synthesize_pose_fish: 4; 2, 4; (4, 1), (5, 1), no pair, all classes 0, sigmas 0.1) */
+  int jitter_nv;               /* jitter_p row 0 while num_valid <= jitter_nv */
+  int miss_nv[2];              /* miss_p row 0 while num_valid <= miss_nv[0], row 1 while <= miss_nv[1] */
+  int crowd_nv[2], crowd_ov[2];/* crowded = (num_valid <= crowd_nv[i] and num_overlap >= crowd_ov[i]) for i = 0 or 1 */
 } buctd_synth_tables;
 int buctd_synthesize_pose(const buctd_synth_tables* tables, const double* joints, const double* estimated,
                           const double* near_joints, const double* area, const int* num_overlap, int B, int K, int M,

@@ -1942,20 +1942,53 @@ def _native_bwd_done(side, tensors, blocks):
         grad_done(bn1.weight, bn1.bias, w1)
 
 
+class _Chain:
+    """Buffers and descriptors of a chain of n BasicBlocks on input x (block.hip) - the owner of the slab layout (a slab: one
+    tensor of x's shape, `step` bytes).  The chain's descriptors are descs / grads[at : at + n] of the caller's arrays."""
+    ACT = 3       # forward slabs per block: z1 | z2 | y
+    STAT = 4      # [C] float rows per block: mean1 | invstd1 | mean2 | invstd2
+    TMP, DX = 5, 4        # backward slabs per block: dz2 | dres | dy1 | dz1 | dx, and the index of dx
+    ACCS = 2      # statistics accumulators per block and direction: bn1's | bn2's
+
+    def __init__(self, x, blocks, descs, at=0):
+        self.x, self.blocks, self.n, self.descs, self.at, self.shape = x, blocks, len(blocks), descs, at, tuple(x.shape)
+        self.step, self.accb = 4 * x.numel(), self.ACCS * acc_bytes(self.shape[3])
+
+    def _fill(self, act, stat, pbase=None):
+        shape, step, accb, descs, at = self.shape, self.step, self.accb, self.descs, self.at
+        xin, abase, sbase, astep, sstep = self.x.data_ptr(), act.data_ptr(), stat.data_ptr(), self.ACT * step, self.STAT * shape[3] * 4
+        for k, blk in enumerate(self.blocks):
+            xin = _block_desc(descs[at + k], shape, step, xin, blk, abase + astep * k, sbase + sstep * k, pbase and pbase + k * accb)
+
+    def forward(self):
+        """Allocates act and stat, draws the forward accumulators, fills the descriptors -> act, stat (act[n - 1, 2]: y)."""
+        n, shape, dev = self.n, self.shape, self.x.device
+        act = torch.empty((n, self.ACT) + shape, dtype=torch.float32, device=dev)
+        stat = torch.empty((n, self.STAT, shape[3]), dtype=torch.float32, device=dev)
+        self._fill(act, stat, AccRef(shape[3], dev, self.ACCS * n).ptr)
+        return act, stat
+
+    def grad_buffers(self, slabs=TMP):
+        """Allocates tmp (`slabs` slabs per block) and draws the backward accumulators -> tmp (tmp[0, DX]: dx of the chain)."""
+        self.tmp = torch.empty((self.n, slabs) + self.shape, dtype=torch.float32, device=self.x.device)
+        self.bn_acc = AccRef(self.shape[3], self.x.device, self.ACCS * self.n).ptr
+        return self.tmp
+
+    def backward(self, grads, act, stat, dy, want_dx, ws, ws_bytes):
+        """Behind grad_buffers: fills descriptors and grads; ws: the weight-gradient workspace."""
+        n, step, tb, at, bn_acc, accb = self.n, self.step, self.tmp.data_ptr(), self.at, self.bn_acc, self.accb
+        tstep = self.TMP * step
+        self._fill(act, stat)
+        for k, blk in enumerate(self.blocks):
+            up = dy.data_ptr() if k == n - 1 else tb + tstep * (k + 1) + self.DX * step      # the next block's dx
+            _block_grads(grads[at + k], tb + tstep * k, step, up, k > 0 or want_dx, blk, bn_acc + k * accb, ws, ws_bytes)
+
+
 def _chain_forward(ctx, x, blocks):
     """The native forward of BasicChainFn and - with one block - of BasicBlockFn: one library call (block.hip)."""
     n = len(blocks)
-    shape = N, H, W, Cn = x.shape
-    dev = x.device
-    act = torch.empty((n, 3, N, H, W, Cn), dtype=torch.float32, device=dev)        # per block: z1 | z2 | y
-    stat = torch.empty((n, 4, Cn), dtype=torch.float32, device=dev)     # per block: mean1 | invstd1 | mean2 | invstd2
     descs = (_C.BasicBlockDesc * n)()
-    step = 4 * N * H * W * Cn
-    accb = acc_bytes(Cn)
-    abase, pbase, sbase = act.data_ptr(), AccRef(Cn, dev, 2 * n).ptr, stat.data_ptr()
-    xin = x.data_ptr()
-    for k, blk in enumerate(blocks):
-        xin = _block_desc(descs[k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4, pbase + k * 2 * accb)
+    act, stat = _Chain(x, blocks, descs).forward()
     check(lib().buctd_basic_chain_fwd_train(n, descs, stream_ptr()), "basic_chain_fwd_train")
     ctx.blocks = blocks
     ctx.save_for_backward(x, act, stat)
@@ -1968,30 +2001,20 @@ def _chain_backward(ctx, dy, want_dx):
     n = len(blocks)
     x, act, stat = ctx.saved_tensors
     dy = _contig(dy)
-    shape = N, H, W, Cn = x.shape
-    dev = x.device
-    # per block: dz2 | dres | dy1 | dz1 | dx; a single block whose input needs no gradient does without the last slab
-    tmp = torch.empty((n, 5 if (n > 1 or want_dx) else 4, N, H, W, Cn), dtype=torch.float32, device=dev)
-    step = 4 * N * H * W * Cn
-    abase, sbase, tb = act.data_ptr(), stat.data_ptr(), tmp.data_ptr()
     descs = (_C.BasicBlockDesc * n)()
     grads = (_C.BasicBlockGrads * n)()
-    main = torch.cuda.current_stream(dev)
+    ch = _Chain(x, blocks, descs)
+    # a single block whose input needs no gradient does without the dx slab
+    tmp = ch.grad_buffers(_Chain.TMP if (n > 1 or want_dx) else _Chain.TMP - 1)
+    main = torch.cuda.current_stream(x.device)
     use_side = _side["on"]
-    side = _side_stream(dev) if use_side else main
-    accb = acc_bytes(Cn)
-    bn_acc = AccRef(Cn, dev, 2 * n).ptr
-    wg_ws = workspace_on(side, _wgrad3x3_workspace("bf16x6", N, H, W, Cn, Cn), dev)     # the side stream's own scratch buffer
-    ws, ws_bytes = wg_ws.data_ptr(), wg_ws.numel()
-    xin = x.data_ptr()
-    for k, blk in enumerate(blocks):
-        xin = _block_desc(descs[k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4)
-        up = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
-        _block_grads(grads[k], tb + 5 * step * k, step, up, k > 0 or want_dx, blk, bn_acc + k * 2 * accb, ws, ws_bytes)
+    side = _side_stream(x.device) if use_side else main
+    wg_ws = workspace_on(side, _wgrad3x3_workspace("bf16x6", *ch.shape, ch.shape[3]), x.device)     # the side stream's own buffer
+    ch.backward(grads, act, stat, dy, want_dx, wg_ws.data_ptr(), wg_ws.numel())
     check(lib().buctd_basic_chain_bwd(n, descs, grads, main.cuda_stream, side.cuda_stream if use_side else None),
           "basic_chain_bwd")
     _native_bwd_done(side if use_side else None, (x, act, stat, tmp, dy), reversed(blocks))
-    return tmp[0, 4] if want_dx else None
+    return tmp[0, _Chain.DX] if want_dx else None
 
 
 class BasicChainFn(torch.autograd.Function):
@@ -2118,22 +2141,8 @@ class BasicBranchesFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, w_first, chains, *xs):
         nb, n = len(xs), len(chains[0])
-        dev = xs[0].device
         descs = (_C.BasicBlockDesc * (nb * n))()
-        acts, stats = [], []
-        for b, x in enumerate(xs):
-            shape = N, H, W, Cn = x.shape
-            act = torch.empty((n, 3, N, H, W, Cn), dtype=torch.float32, device=dev)        # per block: z1 | z2 | y
-            stat = torch.empty((n, 4, Cn), dtype=torch.float32, device=dev)
-            acts.append(act)
-            stats.append(stat)
-            step = 4 * N * H * W * Cn
-            accb = acc_bytes(Cn)
-            abase, pbase, sbase = act.data_ptr(), AccRef(Cn, dev, 2 * n).ptr, stat.data_ptr()
-            xin = x.data_ptr()
-            for k, blk in enumerate(chains[b]):
-                xin = _block_desc(descs[b * n + k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4,
-                                  pbase + k * 2 * accb)
+        acts, stats = zip(*(_Chain(x, chains[b], descs, b * n).forward() for b, x in enumerate(xs)))
         check(lib().buctd_basic_branches_fwd_train(nb, n, descs, stream_ptr()), "basic_branches_fwd_train")
         ctx.chains = chains
         ctx.save_for_backward(*xs, *acts, *stats)
@@ -2160,29 +2169,18 @@ class BasicBranchesFn(torch.autograd.Function):
         ws_ptr = wg_ws.data_ptr()
         tmps, keep = [], []
         for b, x in enumerate(xs):
-            shape = N, H, W, Cn = x.shape
-            dy = dys[b]
-            dy = torch.zeros_like(x) if dy is None else _contig(dy)
+            # a branch whose output took no part in the loss still runs (its parameter gradients become zero)
+            dy = torch.zeros_like(x) if dys[b] is None else _contig(dys[b])
             keep.append(dy)
-            want_dx = ctx.needs_input_grad[2 + b]
-            tmp = torch.empty((n, 5, N, H, W, Cn), dtype=torch.float32, device=dev)   # per block: dz2 | dres | dy1 | dz1 | dx
-            tmps.append(tmp)
-            step = 4 * N * H * W * Cn
-            abase, sbase, tb = acts[b].data_ptr(), stats[b].data_ptr(), tmp.data_ptr()
-            accb = acc_bytes(Cn)
-            bn_acc = AccRef(Cn, dev, 2 * n).ptr
-            xin = x.data_ptr()
-            for k, blk in enumerate(chains[b]):
-                xin = _block_desc(descs[b * n + k], shape, step, xin, blk, abase + 3 * step * k, sbase + k * 4 * Cn * 4)
-                up = dy.data_ptr() if k == n - 1 else tb + 5 * step * (k + 1) + 4 * step      # the next block's dx
-                _block_grads(grads[b * n + k], tb + 5 * step * k, step, up, k > 0 or want_dx, blk, bn_acc + k * 2 * accb,
-                             ws_ptr, needs[b])
+            ch = _Chain(x, chains[b], descs, b * n)
+            tmps.append(ch.grad_buffers())          # always with the dx slab, whatever needs_input_grad says
+            ch.backward(grads, acts[b], stats[b], dy, ctx.needs_input_grad[2 + b], ws_ptr, needs[b])
             ws_ptr += needs[b]
         check(lib().buctd_basic_branches_bwd(nb, n, descs, grads, main.cuda_stream, side.cuda_stream if use_side else None),
               "basic_branches_bwd")
         _native_bwd_done(side if use_side else None, list(xs) + list(acts) + list(stats) + tmps + keep,
                          (chains[b][k] for k in range(n - 1, -1, -1) for b in range(nb)))
-        return (None, None) + tuple(tmps[b][0, 4] if ctx.needs_input_grad[2 + b] else None for b in range(nb))
+        return (None, None) + tuple(tmps[b][0, _Chain.DX] if ctx.needs_input_grad[2 + b] else None for b in range(nb))
 
 
 class Conv(torch.autograd.Function):

@@ -78,6 +78,53 @@ def test_branches_node_equals_chains(dev, shapes):
             assert torch.equal(a, b), "BatchNorm parameter gradients must be bit-identical to the chains"
 
 
+def test_branches_node_with_unused_branch_and_input_without_gradient(dev):
+    """What the shared chain builder decides per branch: branch 0's input needs no gradient (its first block writes no dx),
+    branch 1's output takes no part in the loss (its dy arrives as None: the node runs it on a zero gradient).  Against one
+    BasicChainFn per branch under the same conditions - there autograd never runs branch 1's backward, so a gradient it
+    leaves None must be exactly zero in the group run."""
+    from buctd_amd import ops
+    shapes = [(2, 8, 6, 32), (2, 4, 3, 64)]
+    xs, dys, chains = _make_chains(dev, shapes, 2, 7)
+    assert ops.group_branches_ok(xs, chains)
+    params = [q for ch in chains for b in ch for q in (b[0], b[2], b[1].weight, b[1].bias, b[3].weight, b[3].bias)]
+    res = {}
+    for mode in ("group", "chains"):
+        for q in params:
+            q.grad = None
+        for ch in chains:
+            for b in ch:
+                for bn in (b[1], b[3]):
+                    bn.running_mean.zero_(); bn.running_var.fill_(1.0)
+        xi = [xs[0].clone(), xs[1].clone().requires_grad_(True)]
+        if mode == "chains":
+            ys = [ops.BasicChainFn.apply(xi[b], chains[b][0][0], chains[b]) for b in range(2)]
+        else:
+            ys = ops.BasicBranchesFn.apply(chains[0][0][0], chains, *xi)
+        torch.autograd.backward([ys[0]], [dys[0]])
+        torch.cuda.synchronize()
+        assert xi[0].grad is None
+        clone = lambda t: None if t is None else t.clone()
+        res[mode] = ([y.detach().clone() for y in ys] + [bn.running_mean.clone() for ch in chains for b in ch for bn in (b[1], b[3])] +
+                     [bn.running_var.clone() for ch in chains for b in ch for bn in (b[1], b[3])],
+                     [clone(xi[1].grad)] + [clone(q.grad) for q in params])
+        del ys, xi
+    for a, b in zip(*(res[m][0] for m in ("group", "chains"))):
+        assert torch.equal(a, b), "outputs / running statistics must be bit-identical to the chains"
+    used = len(params) // 2      # the parameters of branch 0
+    for i, (a, b) in enumerate(zip(*(res[m][1] for m in ("group", "chains")))):
+        assert a is not None
+        if b is None:            # branch 1: its input gradient and its parameter gradients
+            assert i == 0 or i > used
+            assert torch.count_nonzero(a).item() == 0, "a gradient the per-chain run leaves None must be exactly zero"
+        elif a.dim() == 4 and i > 0:
+            sc = b.abs().max().item()
+            assert (a - b).abs().max().item() <= 5e-6 * sc, f"weight gradient: group vs chains {(a - b).abs().max().item():.3e} (scale {sc:.3e})"
+        else:
+            assert torch.equal(a, b), "input / BatchNorm parameter gradients must be bit-identical to the chains"
+    assert all(g is not None for g in res["chains"][1][1:1 + used]), "branch 0 is the used branch"
+
+
 def test_group_weight_gradient_matches_fp64(dev):
     """buctd_conv3x3_wgrad_bf16x6_group against an fp64 convolution weight gradient (<= 2e-6 of the largest element)."""
     import ctypes as C

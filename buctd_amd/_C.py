@@ -84,6 +84,14 @@ class MhaArgs(C.Structure):            # mirrors buctd_mha_args
                 [(n, C.c_void_p) for n in ("dq", "dk", "dv")] + [(n, C.c_int) for n in ("lddq", "lddk", "lddv")])
 
 
+class RefineArgs(C.Structure):          # mirrors buctd_refine_args
+    _fields_ = ([(n, C.c_void_p) for n in ("coords", "maxvals", "offset", "center", "scale", "box_score", "items",
+                                           "cond_trunc", "cond_joints", "status", "hist_preds", "hist_score",
+                                           "hist_box_score", "hist_keypoint_score", "hist_center", "hist_scale")] +
+                [(n, C.c_int) for n in ("B", "K", "pass_", "passes", "heatmap_w", "heatmap_h", "crop_w", "crop_h")] +
+                [(n, C.c_double) for n in ("margin", "aspect_ratio", "in_vis_thre", "scale_thre")])
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -215,6 +223,7 @@ SIGNATURES = {
     "buctd_warp_affine_norm": (_I, [_P, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "buctd_cond_render_into": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _SZ, _P]),
     "buctd_cond_geometry": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "buctd_refine_step": (_I, [C.POINTER(RefineArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
     "buctd_mha_fwd_supported": (_I, [_I, _I]),
     "buctd_mha_fwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P]),

@@ -153,3 +153,147 @@ extern "C" int buctd_cond_geometry(const double* synth, const double* cond_vis, 
   BUCTD_CHECK_LAUNCH("buctd_cond_geometry");
   return BUCTD_OK;
 }
+
+// One pass boundary of the iterative refinement (dataset/pipeline.py IterativeRefiner; reference dataloader.py:454-508,
+// 596-612): what get_final_preds, rescore, next_records and geometry() do per person on the host between the decode of
+// one pass and the crop of the next.  One wavefront per person, lanes over joints (K <= 32); the box and the score are
+// butterfly reductions in float64.  Every float64 product and sum is rounded on its own, like in cond_geometry_kernel.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// utils/transforms.py crop_affine_closed_form, line by line: x' = sx * x + tx, y' = sy * y + ty.
+struct CropAffine {
+  double sx, sy, tx, ty;
+  bool ok;               // false: the box has no extent (the host's solve is singular)
+};
+__device__ __forceinline__ CropAffine crop_affine(float cx, float cy, float scale0, int out_w, int out_h, bool inv) {
+  const float box = scale0 * 200.0f;
+  const float p1y = (float)__dadd_rn((double)cy, (double)(box * -0.5f));
+  const float dy = cy - p1y;
+  const float p2x = cx - dy;
+  const double ex = __dsub_rn((double)cx, (double)p2x), ey = __dsub_rn((double)cy, (double)p1y);
+  const double a = (double)out_w * 0.5, b = (double)out_h * 0.5;
+  CropAffine t;
+  t.ok = ex != 0.0 && ey != 0.0;
+  if (inv) {
+    t.sx = ex / a;
+    t.sy = ey / a;
+    t.tx = __dsub_rn((double)cx, __dmul_rn(t.sx, a));
+    t.ty = __dsub_rn((double)cy, __dmul_rn(t.sy, b));
+  } else {
+    t.sx = a / ex;
+    t.sy = a / ey;
+    t.tx = __dsub_rn(a, __dmul_rn(t.sx, (double)cx));
+    t.ty = __dsub_rn(b, __dmul_rn(t.sy, (double)cy));
+  }
+  return t;
+}
+
+__global__ __launch_bounds__(256) void refine_step_kernel(buctd_refine_args p) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), j = threadIdx.x & 63;
+  if (b >= p.B) return;                                   // whole wavefronts leave: the shuffles below see 64 lanes
+  const bool on = j < p.K;
+  const long row = (long)p.pass * p.B + b;                // row of this person in the history buffers
+  const float cx = p.center[2 * b], cy = p.center[2 * b + 1], s0 = p.scale[2 * b], s1 = p.scale[2 * b + 1];
+  const double box_score = p.box_score[b];
+  // predictions: coords (+ offset) in float32, inverse crop affine in float64, one rounding to float32
+  const CropAffine back = crop_affine(cx, cy, s0, p.heatmap_w, p.heatmap_h, true);
+  float px = 0.f, py = 0.f, mv = 0.f;
+  if (on) {
+    const long i = (long)b * p.K + j;
+    float hx = p.coords[2 * i], hy = p.coords[2 * i + 1];
+    if (p.offset) {
+      hx = hx + p.offset[2 * i];
+      hy = hy + p.offset[2 * i + 1];
+    }
+    mv = p.maxvals[i];
+    px = (float)__dadd_rn(__dmul_rn((double)hx, back.sx), back.tx);
+    py = (float)__dadd_rn(__dmul_rn((double)hy, back.sy), back.ty);
+    float* hp = p.hist_preds + (row * p.K + j) * 3;
+    hp[0] = px; hp[1] = py; hp[2] = mv;
+  }
+  // rescore: mean of the maxvals above the threshold (compared in float32, like numpy does), times the box score
+  const bool counted = on && mv > (float)p.in_vis_thre;
+  const int n = __popcll(__ballot(counted));
+  const double sum = wave_sum_f64(counted ? (double)mv : 0.0);
+  const double kpt_score = n > 0 ? sum / (double)n : 0.0;
+  const double score = __dmul_rn(kpt_score, box_score);
+  // box_from_keypoints: the non-zero x and the non-zero y, each on its own
+  const bool nx = on && px != 0.f, ny = on && py != 0.f;
+  const bool empty = __ballot(nx) == 0 || __ballot(ny) == 0;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  const double xlo = wave_min_f64(nx ? (double)px : inf), xhi = wave_max_f64(nx ? (double)px : -inf);
+  const double ylo = wave_min_f64(ny ? (double)py : inf), yhi = wave_max_f64(ny ? (double)py : -inf);
+  const buctd_warp_item* it = p.items + b;
+  const double W = (double)it->W, H = (double)it->H;
+  const double x0 = fmin(fmax(__dsub_rn(xlo, p.margin), 0.0), W), x1 = fmin(fmax(__dadd_rn(xhi, p.margin), 0.0), W);
+  const double y0 = fmin(fmax(__dsub_rn(ylo, p.margin), 0.0), H), y1 = fmin(fmax(__dadd_rn(yhi, p.margin), 0.0), H);
+  double w = __dsub_rn(x1, x0), h = __dsub_rn(y1, y0);
+  // xywh2cs
+  const float ncx = (float)__dadd_rn(x0, __dmul_rn(w, 0.5)), ncy = (float)__dadd_rn(y0, __dmul_rn(h, 0.5));
+  const double ah = __dmul_rn(p.aspect_ratio, h);
+  if (w > ah) h = w / p.aspect_ratio;
+  else if (w < ah) w = __dmul_rn(h, p.aspect_ratio);
+  float ns0 = (float)(w / 200.0), ns1 = (float)(h / 200.0);
+  if (ncx != -1.f) {
+    ns0 = ns0 * (float)p.scale_thre;
+    ns1 = ns1 * (float)p.scale_thre;
+  }
+  const CropAffine fwd = crop_affine(ncx, ncy, ns0, p.crop_w, p.crop_h, false);
+  const int bad = (empty ? 1 : 0) | (!empty && !fwd.ok ? 2 : 0);
+  if (j == 0) {
+    p.hist_score[row] = score;
+    p.hist_box_score[row] = box_score;
+    p.hist_keypoint_score[row] = kpt_score;
+    p.hist_center[2 * row] = cx; p.hist_center[2 * row + 1] = cy;
+    p.hist_scale[2 * row] = s0; p.hist_scale[2 * row + 1] = s1;
+    p.box_score[b] = score;
+    if (bad) p.status[b] = p.status[b] | bad;
+  }
+  if (bad) return;
+  if (j == 0) {
+    p.center[2 * b] = ncx; p.center[2 * b + 1] = ncy;
+    p.scale[2 * b] = ns0; p.scale[2 * b + 1] = ns1;
+    double* m = p.items[b].m;
+    m[0] = fwd.sx; m[1] = 0.0; m[2] = fwd.tx;
+    m[3] = 0.0; m[4] = fwd.sy; m[5] = fwd.ty;
+  }
+  if (on) {
+    // the next condition: the prediction through the new affine (all visibilities are 1), and its trunc() for the renderer
+    const long i = (long)b * p.K + j;
+    const double qx = __dadd_rn(__dmul_rn(fwd.sx, (double)px), fwd.tx), qy = __dadd_rn(__dmul_rn(fwd.sy, (double)py), fwd.ty);
+    if (p.cond_joints) {
+      p.cond_joints[2 * i] = qx;
+      p.cond_joints[2 * i + 1] = qy;
+    }
+    p.cond_trunc[2 * i] = (float)trunc(qx);
+    p.cond_trunc[2 * i + 1] = (float)trunc(qy);
+  }
+}
+
+extern "C" int buctd_refine_step(const buctd_refine_args* a, void* stream) {
+  BUCTD_CHECK_ARG(a && a->coords && a->maxvals && a->center && a->scale && a->box_score && a->items && a->cond_trunc &&
+                      a->status && a->hist_preds && a->hist_score && a->hist_box_score && a->hist_keypoint_score &&
+                      a->hist_center && a->hist_scale,
+                  "buctd_refine_step: NULL argument (only offset and cond_joints may be NULL)");
+  BUCTD_CHECK_ARG(a->B > 0 && a->B < (1 << 20) && a->K > 0 && a->K <= 32, "buctd_refine_step: B > 0, 0 < K <= 32");
+  BUCTD_CHECK_ARG(a->passes > 0 && a->pass >= 0 && a->pass < a->passes, "buctd_refine_step: pass outside [0, passes)");
+  BUCTD_CHECK_ARG(a->heatmap_w > 0 && a->heatmap_h > 0 && a->crop_w > 0 && a->crop_h > 0 && a->aspect_ratio > 0.0,
+                  "buctd_refine_step: sizes and the aspect ratio must be positive");
+  hipLaunchKernelGGL(refine_step_kernel, dim3(ceil_div(a->B, 4)), dim3(256), 0, (hipStream_t)stream, *a);
+  BUCTD_CHECK_LAUNCH("buctd_refine_step");
+  return BUCTD_OK;
+}

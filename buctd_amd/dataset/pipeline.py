@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._C import check, lib, ptr, stream_ptr
+from .._C import RefineArgs, check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
 from ..utils.transforms import _swap_table, affine_transform, fliplr_joints, get_affine_transform
 from .pose_synthesis import synthesize_pose_batch
@@ -342,28 +342,58 @@ class DeviceSamplePipeline:
             cjt = cond_trunc
             if cjt is None:
                 cjt = torch.from_numpy(trunc_condition(np.stack([g["cond_joints"] for g in geos]))).to(dev)
-            colors = None
-            if self.colored:
-                colors = torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:K])).to(dev)
-            ws = ops.workspace(lib().buctd_cond_render_workspace(B * K if self.stacked else B, 3, H, W), dev)
-            if self.stacked:
-                # get_stacked_condition (JointsDataset.py:471-498): every joint is its own single-impulse image, blurred
-                # and peak-normalised on its own - B * K one-joint "images" of one channel for the render kernel
-                tmp = torch.empty((B * K, 1, H, W), dtype=torch.float32, device=dev)
-                check(lib().buctd_cond_render_into(ptr(cjt), 2, None, B * K, 1, 1, H, W, 0, ptr(tmp), tmp.stride(0), ptr(ws),
-                                                   ws.numel(), stream_ptr()), "cond_render_into")
-                x[:, 3:] = tmp.view(B, K, H, W)
-            elif self.colored:
-                check(lib().buctd_cond_render_into(ptr(cjt), 2, ptr(colors), B, K, 3, H, W, 0,
-                                                   C.c_void_p(x[:, 3:].data_ptr()), x.stride(0), ptr(ws), ws.numel(),
-                                                   stream_ptr()), "cond_render_into")
-            else:
-                # mono: the one blurred, int-truncated channel replicated x3 (JointsDataset.py:513-514)
-                for c in range(3):
-                    check(lib().buctd_cond_render_into(ptr(cjt), 2, None, B, K, 1, H, W, 1,
-                                                       C.c_void_p(x[:, 3 + c:].data_ptr()), x.stride(0), ptr(ws),
-                                                       ws.numel(), stream_ptr()), "cond_render_into")
+            self.render_condition(x, cjt)
         return (x, target, weight, crop) if want_crop else (x, target, weight)
+
+    def condition_colors(self, dev):
+        """The colour table of a colored condition on the device (None for mono / stacked): a fresh upload per call."""
+        if not self.colored:
+            return None
+        return torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:self.num_joints])).to(dev)
+
+    def render_condition(self, x, cjt, colors=None):
+        """Condition heat-map of truncated crop coordinates cjt (float32 [B, K, 2], device) into channels [3, 3 + Cc) of the
+        network input x.  colors: condition_colors() if the caller uploaded it already."""
+        dev = x.device
+        B, K = int(x.shape[0]), self.num_joints
+        W, H = int(self.image_size[0]), int(self.image_size[1])
+        if colors is None:
+            colors = self.condition_colors(dev)
+        ws = ops.workspace(lib().buctd_cond_render_workspace(B * K if self.stacked else B, 3, H, W), dev)
+        if self.stacked:
+            # get_stacked_condition (JointsDataset.py:471-498): every joint is its own single-impulse image, blurred
+            # and peak-normalised on its own - B * K one-joint "images" of one channel for the render kernel
+            tmp = torch.empty((B * K, 1, H, W), dtype=torch.float32, device=dev)
+            check(lib().buctd_cond_render_into(ptr(cjt), 2, None, B * K, 1, 1, H, W, 0, ptr(tmp), tmp.stride(0), ptr(ws),
+                                               ws.numel(), stream_ptr()), "cond_render_into")
+            x[:, 3:] = tmp.view(B, K, H, W)
+        elif self.colored:
+            check(lib().buctd_cond_render_into(ptr(cjt), 2, ptr(colors), B, K, 3, H, W, 0,
+                                               C.c_void_p(x[:, 3:].data_ptr()), x.stride(0), ptr(ws), ws.numel(),
+                                               stream_ptr()), "cond_render_into")
+        else:
+            # mono: the one blurred, int-truncated channel replicated x3 (JointsDataset.py:513-514)
+            for c in range(3):
+                check(lib().buctd_cond_render_into(ptr(cjt), 2, None, B, K, 1, H, W, 1,
+                                                   C.c_void_p(x[:, 3 + c:].data_ptr()), x.stride(0), ptr(ws),
+                                                   ws.numel(), stream_ptr()), "cond_render_into")
+
+    def warp_and_condition(self, table, cond_trunc, colors=None):
+        """Network input [B, 3 + Cc, H, W] from a device-resident warp_table() and truncated condition coordinates
+        (float32 [B, K, 2], device): render() without the Gaussian targets and without any host array - the two kernels an
+        inference pass needs.  Nothing is uploaded when colors (condition_colors()) is handed in."""
+        if not self.conditional:
+            raise ValueError("warp_and_condition renders a condition: MODEL.CONDITIONAL_TOPDOWN is off")
+        dev = table.device
+        B, K = int(cond_trunc.shape[0]), self.num_joints
+        W, H = int(self.image_size[0]), int(self.image_size[1])
+        x = torch.empty((B, 3 + (K if self.stacked else 3), H, W), dtype=torch.float32, device=dev)
+        mean = (C.c_float * 3)(*self.mean.tolist())
+        std = (C.c_float * 3)(*self.std.tolist())
+        check(lib().buctd_warp_affine_norm(ptr(table), B, H, W, mean, std, ptr(x), x.stride(0), None, stream_ptr()),
+              "warp_affine_norm")
+        self.render_condition(x, cond_trunc, colors)
+        return x
 
     def synthesis_inputs(self, records):
         """Host side of JointsDataset.py:165-167 and 204-212 for a batch: ground-truth joints [B, K, 3], the conditions
@@ -424,12 +454,31 @@ class DeviceSamplePipeline:
 
 class IterativeRefiner:
     """BUCTD iterative refinement in one process (README.md:104 '3x iterative refinement'; reference = three CLI runs
-    chained through the results json).  use_dark: decode every pass with get_final_preds(..., use_dark=True)."""
+    chained through the results json).  use_dark: decode every pass with get_final_preds(..., use_dark=True).
 
-    def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False):
+    on_device=True: only pass 0 is set up on the host; from there on the predictions, scores, boxes, crop affines and
+    conditions of all passes stay on the device (buctd_refine_step between the decode kernel of one pass and the crop of
+    the next) and run() waits for the device once, after the last pass.  Same return value; a person whose predictions
+    have no non-zero x or y raises the host path's ValueError, after the last pass instead of in the middle.  Needs an
+    eval pipeline (no augmentation draws), a conditional config and NUM_JOINTS <= 32."""
+
+    MAX_DEVICE_JOINTS = 32     # buctd_refine_step: one lane per joint, as buctd_cond_geometry
+
+    def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False, on_device=False):
         self.cfg, self.model, self.pipe = cfg, model, pipeline
         self.use_dark = bool(use_dark)
         self.in_vis_thre = cfg.TEST.IN_VIS_THRE if in_vis_thre is None else in_vis_thre
+        self.on_device = bool(on_device)
+        if self.on_device:
+            if pipeline.is_train:
+                raise ValueError("IterativeRefiner(on_device=True) needs a pipeline built with is_train=False: the "
+                                 "augmentation draws of a train pipeline are made on the host")
+            if not pipeline.conditional:
+                raise ValueError("IterativeRefiner(on_device=True) needs a conditional config "
+                                 "(MODEL.CONDITIONAL_TOPDOWN): without a condition there is nothing to refine")
+            if pipeline.num_joints > self.MAX_DEVICE_JOINTS:
+                raise ValueError(f"IterativeRefiner(on_device=True) handles at most {self.MAX_DEVICE_JOINTS} joints "
+                                 f"(MODEL.NUM_JOINTS is {pipeline.num_joints})")
 
     @staticmethod
     def rescore(maxvals, box_score, in_vis_thre):
@@ -461,6 +510,8 @@ class IterativeRefiner:
     @torch.no_grad()
     def run(self, records, passes=3):
         """Returns per pass: dict(preds [B, K, 3] image coordinates + max-val, score, box_score, keypoint_score)."""
+        if self.on_device:
+            return self.run_on_device(records, passes)
         self.model.eval()
         history = []
         for _ in range(passes):
@@ -478,3 +529,92 @@ class IterativeRefiner:
                                 center=center, scale=scale))
             records = self.next_records(records, preds, score)
         return history
+
+    def refine_step(self, decoded, state, table, out, p, passes, cond_joints=None):
+        """One buctd_refine_step launch: decoded = (coords [B, K, 2], maxvals [B, K, 1], offsets [B, K, 2] or None) of pass
+        p; state = (center, scale, box_score, cond_trunc) device tensors, overwritten with those of pass p + 1; table:
+        warp_table(), its matrices overwritten; out: the history sections of _layout()."""
+        pipe = self.pipe
+        coords, maxvals, offset = decoded
+        a = RefineArgs()
+        a.coords, a.maxvals, a.offset = ptr(coords), ptr(maxvals), ptr(offset)
+        a.center, a.scale, a.box_score, a.cond_trunc = (ptr(t) for t in state)
+        a.items, a.cond_joints, a.status = ptr(table), ptr(cond_joints), ptr(out["status"])
+        a.hist_preds, a.hist_score, a.hist_box_score = ptr(out["preds"]), ptr(out["score"]), ptr(out["box_score"])
+        a.hist_keypoint_score, a.hist_center, a.hist_scale = ptr(out["keypoint_score"]), ptr(out["center"]), ptr(out["scale"])
+        a.B, a.K, a.pass_, a.passes = int(coords.shape[0]), int(coords.shape[1]), int(p), int(passes)
+        a.heatmap_w, a.heatmap_h = int(pipe.heatmap_size[0]), int(pipe.heatmap_size[1])
+        a.crop_w, a.crop_h = int(pipe.image_size[0]), int(pipe.image_size[1])
+        a.margin, a.aspect_ratio = float(pipe.bu_bbox_margin), float(pipe.aspect_ratio)
+        a.in_vis_thre, a.scale_thre = float(self.in_vis_thre), float(pipe.scale_thre)
+        check(lib().buctd_refine_step(C.byref(a), stream_ptr()), "refine_step")
+
+    @staticmethod
+    def _layout(sections):
+        """[(name, numpy dtype, shape)] -> ({name: (byte offset, dtype, shape)}, total bytes); widest items first, so every
+        section is aligned to its item size."""
+        at, off = {}, 0
+        for name, dt, shape in sorted(sections, key=lambda t: -np.dtype(t[1]).itemsize):
+            at[name] = (off, np.dtype(dt), tuple(shape))
+            off += int(np.prod(shape)) * np.dtype(dt).itemsize
+        return at, off
+
+    @staticmethod
+    def _views(buf, at):
+        """Typed views of the sections of a uint8 tensor (device) or numpy array (host)."""
+        out = {}
+        for name, (off, dt, shape) in at.items():
+            raw = buf[off:off + int(np.prod(shape)) * dt.itemsize]
+            if torch.is_tensor(raw):
+                out[name] = raw.view(getattr(torch, dt.name)).view(shape)
+            else:
+                out[name] = raw.view(dt).reshape(shape)
+        return out
+
+    def run_on_device(self, records, passes=3):
+        """run() with on_device=True: one upload before the first pass, one copy back after the last."""
+        self.model.eval()
+        pipe, cfg = self.pipe, self.cfg
+        B, K = len(records), pipe.num_joints
+        images = [r["image"] for r in records]
+        dev = images[0].device
+        # pass 0 on the host, as run() does it
+        geos = [pipe.geometry(r) for r in records]
+        table = pipe.warp_table(images, geos)
+        f32, f64 = np.float32, np.float64
+        at_in, n_in = self._layout([("box_score", f64, (B,)), ("center", f32, (B, 2)), ("scale", f32, (B, 2)),
+                                    ("cond_trunc", f32, (B, K, 2))])
+        host = np.zeros(n_in, dtype=np.uint8)
+        hv = self._views(host, at_in)
+        hv["box_score"][:] = [float(r.get("score", 1)) for r in records]
+        hv["center"][:] = np.stack([g["center"] for g in geos])
+        hv["scale"][:] = np.stack([g["scale"] for g in geos])
+        hv["cond_trunc"][:] = trunc_condition(np.stack([g["cond_joints"] for g in geos]))
+        sv = self._views(torch.from_numpy(host).to(dev), at_in)
+        state = (sv["center"], sv["scale"], sv["box_score"], sv["cond_trunc"])
+        at_out, n_out = self._layout([("score", f64, (passes, B)), ("box_score", f64, (passes, B)),
+                                      ("keypoint_score", f64, (passes, B)), ("preds", f32, (passes, B, K, 3)),
+                                      ("center", f32, (passes, B, 2)), ("scale", f32, (passes, B, 2)),
+                                      ("status", np.int32, (B,))])
+        result = torch.zeros(n_out, dtype=torch.uint8, device=dev)
+        out = self._views(result, at_out)
+        colors = pipe.condition_colors(dev)
+        refine = bool(cfg.TEST.POST_PROCESS)
+        for p in range(passes):
+            x = pipe.warp_and_condition(table, sv["cond_trunc"], colors)
+            hm = self.model(x)
+            hm = (hm[-1] if isinstance(hm, list) else hm).contiguous()
+            if self.use_dark:
+                res = ops.dark_decode(hm)
+            else:
+                res = ops.argmax_decode(hm, refine=refine)
+            self.refine_step((res[0], res[1], res[3] if (self.use_dark or refine) else None), state, table, out, p, passes)
+        got = self._views(result.cpu().numpy(), at_out)
+        bad = np.nonzero(got["status"])[0]
+        if bad.size:
+            raise ValueError(f"iterative refinement: person(s) {bad.tolist()} of the batch have predictions without a "
+                             "non-zero x or y coordinate, or a box without extent (status "
+                             f"{got['status'][bad].tolist()}): there is no box for the next pass")
+        return [dict(preds=got["preds"][p].copy(), score=got["score"][p].copy(), box_score=got["box_score"][p].copy(),
+                     keypoint_score=got["keypoint_score"][p].copy(), center=got["center"][p].copy(),
+                     scale=got["scale"][p].copy()) for p in range(passes)]

@@ -99,6 +99,30 @@ def get_affine_transform(center, scale, rot, output_size, shift=np.array([0, 0],
     return np.linalg.solve(system, to.astype(np.float64)).T
 
 
+def crop_affine_closed_form(center, scale, output_size, inv=0):
+    """get_affine_transform(center, scale, 0, output_size, inv=inv) for float32 center / scale and an integer output_size,
+    without the solve: with rot = 0 the three control points are the corners of an axis-parallel right-angled triangle, so
+    the matrix is diagonal.  The float32 roundings of the box triangle are those of _triangle / get_3rd_point; everything
+    after them is float64, one rounding per operation.  buctd_refine_step (csrc/sample.hip, crop_affine) restates these
+    lines; the solve differs from them by its own rounding only (tests/test_refine_closed_form.py: <= 1e-9)."""
+    cx, cy = np.float32(center[0]), np.float32(center[1])
+    box = np.float32(scale[0]) * np.float32(200.0)                       # scale * 200.0 in float32; only box[0] is used
+    p1y = np.float32(np.float64(cy) + np.float64(box * np.float32(-0.5)))  # pts[1] = origin + arm, stored as float32
+    dy = cy - p1y                                                        # get_3rd_point: float32 differences
+    p2x = cx - dy
+    # box triangle (cx, cy), (cx, p1y), (p2x, p1y) <-> crop triangle (a, b), (a, b - a), (0, b - a)
+    ex, ey = np.float64(cx) - np.float64(p2x), np.float64(cy) - np.float64(p1y)
+    a, b = np.float64(output_size[0]) * 0.5, np.float64(output_size[1]) * 0.5
+    t = np.zeros((2, 3), dtype=np.float64)
+    if inv:
+        t[0, 0], t[1, 1] = ex / a, ey / a
+        t[0, 2], t[1, 2] = np.float64(cx) - t[0, 0] * a, np.float64(cy) - t[1, 1] * b
+    else:
+        t[0, 0], t[1, 1] = a / ex, a / ey
+        t[0, 2], t[1, 2] = a - t[0, 0] * np.float64(cx), b - t[1, 1] * np.float64(cy)
+    return t
+
+
 def affine_transform(pt, t):
     return t[:, :2] @ np.array([pt[0], pt[1]], dtype=np.float64) + t[:, 2]
 

@@ -721,8 +721,54 @@ int buctd_cond_render_into(const float* joints, int js, const float* colors, int
 int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd_warp_item* items_device,
                         const int* pair_device, int B, int K, double* out_joints, double* out_vis, float* out_trunc,
                         void* stream);
+/* One pass boundary of the iterative refinement (dataset.pipeline.IterativeRefiner; reference: three tools/test.py runs
+ * chained through the results json, lib/dataset/dataloader.py:454-508 and 596-612): from the decode outputs of pass
+ * `pass` to the crop affine and the condition of pass `pass` + 1 without leaving the device.  Per person, in the host's
+ * order and with the host's roundings (float64 products and sums are never fused):
+ *   preds      coords (+ offset) in float32 (core/inference.py DeferredFinalPreds.final_preds), through the inverse crop
+ *              affine of (center, scale, heat-map size) in float64, rounded once to float32
+ *              (utils.transforms.transform_preds(...).astype(float32));
+ *   scores     keypoint_score = mean of the maxvals > float32(in_vis_thre), 0 when none is; score = keypoint_score *
+ *              box_score, summed in float64 (IterativeRefiner.rescore);
+ *   box        min / max of the non-zero x and of the non-zero y of the float32 preds, -+ margin, clipped to [0, W] and
+ *              [0, H] with W, H = items[b].W, items[b].H (dataset.pipeline.box_from_keypoints);
+ *   center, scale   dataset.pipeline.xywh2cs: float32(x + w * 0.5), float32(w / 200) * float32(scale_thre), the aspect
+ *              branches and the center[0] != -1 test;
+ *   items[b].m get_affine_transform(center, scale, 0, crop size) in the closed form of
+ *              utils.transforms.crop_affine_closed_form; src, H, W, flip and the rectangle are not written;
+ *   cond_trunc trunc() of the preds through the new m (all visibilities 1: IterativeRefiner.next_records), float32
+ *              [B][K][2]: the `joints` argument of buctd_cond_render_into with js = 2.
+ * center, scale (float32 [B][2]) and box_score (float64 [B]) are read as the values of this pass and overwritten with
+ * those of the next.  Row `pass` of the history buffers receives this pass's preds (x, y, maxval), score, box_score,
+ * keypoint_score, center and scale.  status (int32 [B], zeroed by the caller before the first pass, only ever or-ed
+ * into): bit 0 - the person has no non-zero x or no non-zero y (the host raises ValueError from min() of an empty array),
+ * bit 1 - the new box has no extent (the host's solve is singular); either way center, scale, m and cond_trunc of that
+ * person stay as they are.  One wavefront per person, lanes over joints: K <= 32.  One launch, no allocation, no
+ * synchronisation. */
+typedef struct {
+  const float* coords;      /* [B][K][2] heat-map coordinates of the decode kernels */
+  const float* maxvals;     /* [B][K] */
+  const float* offset;      /* [B][K][2] quarter-pixel or DARK offsets, NULL: none */
+  float* center;            /* [B][2] in / out */
+  float* scale;             /* [B][2] in / out */
+  double* box_score;        /* [B] in / out */
+  buctd_warp_item* items;   /* [B]: H, W read, m written */
+  float* cond_trunc;        /* [B][K][2] out */
+  double* cond_joints;      /* [B][K][2] out: the same coordinates before trunc(), NULL: not wanted */
+  int32_t* status;          /* [B] */
+  float* hist_preds;        /* [passes][B][K][3] */
+  double* hist_score;       /* [passes][B] */
+  double* hist_box_score;   /* [passes][B] */
+  double* hist_keypoint_score; /* [passes][B] */
+  float* hist_center;       /* [passes][B][2] */
+  float* hist_scale;        /* [passes][B][2] */
+  int B, K, pass, passes;
+  int heatmap_w, heatmap_h, crop_w, crop_h;
+  double margin, aspect_ratio, in_vis_thre, scale_thre;
+} buctd_refine_args;
+int buctd_refine_step(const buctd_refine_args* a, void* stream);
 
-/* Generative pose synthesis (dataset/pose_synthesis.py:6-817, called from JointsDataset.py:202-215): for every person
+/* Generative pose synthesis(dataset/pose_synthesis.py:6-817, called from JointsDataset.py:202-215): for every person
  * and joint one of the error types jitter / miss / inversion / swap / good is drawn and a key point proposed
  * accordingly.  joints, estimated [B][K][3] and near_joints [B][M][K][3] (neighbours; visibility 0 = absent) are float64
  * device arrays, area [B] float64, num_overlap [B] int; out [B][K][3].  Randomness: a counter-based generator keyed by

@@ -92,6 +92,15 @@ class RefineArgs(C.Structure):          # mirrors buctd_refine_args
                 [(n, C.c_double) for n in ("margin", "aspect_ratio", "in_vis_thre", "scale_thre")])
 
 
+class SampleGeomArgs(C.Structure):      # mirrors buctd_sample_geom_args
+    _fields_ = ([(n, C.c_void_p) for n in ("joints", "joints_vis", "cond", "cond_vis", "center", "scale", "bbox",
+                                           "half_body", "draws", "bbox_draws", "flags", "pair", "items", "out_joints",
+                                           "out_joints_vis", "out_cond", "out_cond_vis", "cond_trunc", "target_xy",
+                                           "target_vis", "out_center", "out_scale", "out_rotation", "status")] +
+                [(n, C.c_int) for n in ("B", "K", "crop_w", "crop_h", "keep_rect", "bbox_aug")] +
+                [(n, C.c_double) for n in ("margin", "aspect_ratio", "scale_thre", "stride_x", "stride_y")])
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -224,6 +233,7 @@ SIGNATURES = {
     "buctd_cond_render_into": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _SZ, _P]),
     "buctd_cond_geometry": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "buctd_refine_step": (_I, [C.POINTER(RefineArgs), _P]),
+    "buctd_sample_geometry": (_I, [C.POINTER(SampleGeomArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
     "buctd_mha_fwd_supported": (_I, [_I, _I]),
     "buctd_mha_fwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P]),

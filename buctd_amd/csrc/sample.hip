@@ -297,3 +297,239 @@ extern "C" int buctd_refine_step(const buctd_refine_args* a, void* stream) {
   BUCTD_CHECK_LAUNCH("buctd_refine_step");
   return BUCTD_OK;
 }
+
+// Scalar geometry of a train batch (dataset/pipeline.py DeviceSamplePipeline.geometry; reference JointsDataset.py:217-295):
+// box -> half-body override -> scale draw -> flip -> crop affine for any rotation -> joints, condition, target centres,
+// keep-rectangle.  One wavefront per sample, lanes over joints (K <= 32), like refine_step_kernel; every float64 and
+// float32 product, sum and difference is rounded on its own.  A keep-rectangle with a negative origin is cut at 0, which
+// is what oracle.sample.warp_affine_u8 keeps; the reference's negative slice indices wrap around instead (out of scope).
+// utils/transforms.py _two_sum, _split, _two_prod, _cross: error-free sums and products without a fused multiply-add
+struct Two { double s, e; };
+__device__ __forceinline__ Two two_sum(double a, double b) {
+  Two r;
+  r.s = __dadd_rn(a, b);
+  const double bb = __dsub_rn(r.s, a);
+  r.e = __dadd_rn(__dsub_rn(a, __dsub_rn(r.s, bb)), __dsub_rn(b, bb));
+  return r;
+}
+__device__ __forceinline__ Two split_f64(double a) {
+  const double c = __dmul_rn(134217729.0, a);
+  Two r;
+  r.s = __dsub_rn(c, __dsub_rn(c, a));
+  r.e = __dsub_rn(a, r.s);
+  return r;
+}
+__device__ __forceinline__ Two two_prod(double a, double b) {
+  Two r;
+  r.s = __dmul_rn(a, b);
+  const Two x = split_f64(a), y = split_f64(b);
+  r.e = __dadd_rn(__dadd_rn(__dadd_rn(__dsub_rn(__dmul_rn(x.s, y.s), r.s), __dmul_rn(x.s, y.e)), __dmul_rn(x.e, y.s)),
+                  __dmul_rn(x.e, y.e));
+  return r;
+}
+__device__ __forceinline__ double cross_f64(double a, Two u, double b, Two v) {   // a * (u.s + u.e) - b * (v.s + v.e)
+  const Two p1 = two_prod(a, u.s), p2 = two_prod(b, v.s);
+  const Two s = two_sum(p1.s, -p2.s);
+  return __dadd_rn(s.s, __dadd_rn(__dadd_rn(s.e, __dsub_rn(p1.e, p2.e)), __dsub_rn(__dmul_rn(a, u.e), __dmul_rn(b, v.e))));
+}
+
+struct RotAffine {
+  double m[6];
+  bool ok;               // false: the box has no extent (the host's solve is singular)
+};
+// utils/transforms.py crop_affine_rot_closed_form, line by line (scale in float64: the train path's dtype).
+__device__ __forceinline__ RotAffine crop_affine_rot(float cx, float cy, double scale0, double sn, double cs, int out_w,
+                                                     int out_h) {
+  const double box = __dmul_rn(scale0, 200.0);
+  const double y = __dmul_rn(box, -0.5);
+  const double ax = -__dmul_rn(y, sn), ay = __dmul_rn(y, cs);                   // get_dir([0, y], rot)
+  const float p1x = (float)__dadd_rn((double)cx, ax), p1y = (float)__dadd_rn((double)cy, ay);
+  const float dx = __fsub_rn(cx, p1x), dy = __fsub_rn(cy, p1y);                 // get_3rd_point: float32
+  const float p2x = __fsub_rn(p1x, dy), p2y = __fadd_rn(p1y, dx);
+  const double d1x = __dsub_rn((double)p1x, (double)cx), d1y = __dsub_rn((double)p1y, (double)cy);
+  const double d2x = __dsub_rn((double)p2x, (double)p1x), d2y = __dsub_rn((double)p2y, (double)p1y);
+  const double det = __dsub_rn(__dmul_rn(d1x, d2y), __dmul_rn(d2x, d1y));
+  const double a = (double)out_w * 0.5, b = (double)out_h * 0.5;
+  RotAffine t;
+  t.ok = det != 0.0;
+  t.m[0] = __dmul_rn(a, d1y) / det;
+  t.m[1] = -__dmul_rn(a, d1x) / det;
+  t.m[3] = -__dmul_rn(a, d2y) / det;
+  t.m[4] = __dmul_rn(a, d2x) / det;
+  // the translation over the same denominator, its two differences of products taken exactly
+  const double cxd = (double)cx, cyd = (double)cy;
+  t.m[2] = __dmul_rn(a, cross_f64(d1x, two_sum(d2y, cyd), d1y, two_sum(d2x, cxd))) / det;
+  const Two qx = two_prod(b, d1x), qy = two_prod(b, d1y);
+  Two wx = two_sum(qx.s, __dmul_rn(a, cxd)), wy = two_sum(qy.s, __dmul_rn(a, cyd));   // a * cx, a * cy: exact
+  wx.e = __dadd_rn(wx.e, qx.e);
+  wy.e = __dadd_rn(wy.e, qy.e);
+  t.m[5] = cross_f64(d2y, wx, d2x, wy) / det;
+  return t;
+}
+
+// target_centres(): a coordinate that buctd_gaussian_target's (int)(v / stride + 0.5f) maps to int(j / stride + 0.5)
+__device__ __forceinline__ float target_centre(double v, double stride) {
+  double q = __dadd_rn(v / stride, 0.5);
+  q = fmin(fmax(q, -9.0e18), 9.0e18);                      // astype(int) of a finite double, kept inside int64
+  long long mu = (long long)q;                             // truncates toward zero
+  if (mu < 0) mu -= 1;
+  return (float)__dmul_rn((double)mu, stride);
+}
+
+__device__ __forceinline__ int floor_div10(long long v) {
+  long long q = v / 10;
+  if (v % 10 != 0 && v < 0) q -= 1;
+  return (int)q;
+}
+
+__device__ __forceinline__ int trunc_int(double v) {       // astype(int), kept inside int32 (the table's fields)
+  return (int)fmin(fmax(trunc(v), -1.0e9), 1.0e9);
+}
+
+struct GeomPoint { double x, y, z, v0, v1, v2; };
+// fliplr_joints + the crop affine for lane j of one [K][3] pose
+__device__ __forceinline__ GeomPoint geom_point(const double* pose, const double* vis, int j, int K, bool flip,
+                                                const int* pair, double W, const double* m, bool through) {
+  int src = j;
+  if (flip) {
+    const int q = pair[j];
+    if (q >= 0 && q < K) src = q;
+  }
+  GeomPoint g;
+  g.x = pose[src * 3]; g.y = pose[src * 3 + 1]; g.z = pose[src * 3 + 2];
+  g.v0 = vis[src * 3]; g.v1 = vis[src * 3 + 1]; g.v2 = vis[src * 3 + 2];
+  if (flip) {
+    g.x = __dmul_rn(__dsub_rn(__dsub_rn(W, g.x), 1.0), g.v0);
+    g.y = __dmul_rn(g.y, g.v1);
+    g.z = __dmul_rn(g.z, g.v2);
+  }
+  if (through && g.v0 > 0.0) {
+    const double tx = __dadd_rn(__dadd_rn(__dmul_rn(m[0], g.x), __dmul_rn(m[1], g.y)), m[2]);
+    const double ty = __dadd_rn(__dadd_rn(__dmul_rn(m[3], g.x), __dmul_rn(m[4], g.y)), m[5]);
+    g.x = tx;
+    g.y = ty;
+  }
+  return g;
+}
+
+__global__ __launch_bounds__(256) void sample_geometry_kernel(buctd_sample_geom_args p) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), j = threadIdx.x & 63;
+  if (b >= p.B) return;                                   // whole wavefronts leave: the shuffles below see 64 lanes
+  const bool on = j < p.K;
+  const long i = (long)b * p.K + j;
+  const int flags = p.flags[b];
+  const bool has_cond = p.cond != nullptr;
+  const bool flip = (flags & BUCTD_GEOM_FLIP) != 0;
+  buctd_warp_item* it = p.items + b;
+  const double W = (double)it->W, H = (double)it->H;
+  // 1. box: from the condition pose under use_bu_bbox, else the record's
+  float cx = p.center[2 * b], cy = p.center[2 * b + 1], s0 = p.scale[2 * b], s1 = p.scale[2 * b + 1];
+  bool has_box = (flags & BUCTD_GEOM_HAS_BBOX) != 0;
+  double bx = 0.0, by = 0.0, bw = 0.0, bh = 0.0;
+  if (has_box) { bx = p.bbox[4 * b]; by = p.bbox[4 * b + 1]; bw = p.bbox[4 * b + 2]; bh = p.bbox[4 * b + 3]; }
+  int bad = 0;
+  if (has_cond && (flags & BUCTD_GEOM_USE_BU_BBOX)) {     // wave-uniform
+    const double ex = on ? p.cond[i * 3] : 0.0, ey = on ? p.cond[i * 3 + 1] : 0.0;
+    const bool nx = on && ex != 0.0, ny = on && ey != 0.0;
+    const bool empty = __ballot(nx) == 0 || __ballot(ny) == 0;
+    const double xsum = wave_sum_f64(ex);
+    const double y_first = p.cond[(long)b * p.K * 3 + 1];
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const double xlo = wave_min_f64(nx ? ex : inf), xhi = wave_max_f64(nx ? ex : -inf);
+    const double ylo = wave_min_f64(ny ? ey : inf), yhi = wave_max_f64(ny ? ey : -inf);
+    if (empty) {
+      bad |= 1;
+    } else if (xsum != 0.0 && y_first != 0.0) {
+      // box_from_keypoints
+      const double x0 = fmin(fmax(__dsub_rn(xlo, p.margin), 0.0), W), x1 = fmin(fmax(__dadd_rn(xhi, p.margin), 0.0), W);
+      const double y0 = fmin(fmax(__dsub_rn(ylo, p.margin), 0.0), H), y1 = fmin(fmax(__dadd_rn(yhi, p.margin), 0.0), H);
+      double w = __dsub_rn(x1, x0), h = __dsub_rn(y1, y0);
+      has_box = true;
+      bx = x0; by = y0; bw = w; bh = h;
+      // xywh2cs
+      cx = (float)__dadd_rn(x0, __dmul_rn(w, 0.5));
+      cy = (float)__dadd_rn(y0, __dmul_rn(h, 0.5));
+      const double ah = __dmul_rn(p.aspect_ratio, h);
+      if (w > ah) h = w / p.aspect_ratio;
+      else if (w < ah) w = __dmul_rn(h, p.aspect_ratio);
+      s0 = (float)(w / 200.0);
+      s1 = (float)(h / 200.0);
+      if (cx != -1.f) {
+        s0 = __fmul_rn(s0, (float)p.scale_thre);
+        s1 = __fmul_rn(s1, (float)p.scale_thre);
+      }
+    }
+  }
+  // 2. half-body override
+  if (flags & BUCTD_GEOM_HALF_BODY) {
+    cx = p.half_body[4 * b]; cy = p.half_body[4 * b + 1]; s0 = p.half_body[4 * b + 2]; s1 = p.half_body[4 * b + 3];
+  }
+  // 3. scale draw: float32 * float64 scalar is float64 in numpy
+  const double mul = p.draws[4 * b], sn = p.draws[4 * b + 1], cs = p.draws[4 * b + 2];
+  const double sc0 = __dmul_rn((double)s0, mul), sc1 = __dmul_rn((double)s1, mul);
+  // 4. flip of the centre, in float32
+  if (flip) cx = __fsub_rn(__fsub_rn((float)it->W, cx), 1.0f);
+  // 5. crop affine
+  const RotAffine t = crop_affine_rot(cx, cy, sc0, sn, cs, p.crop_w, p.crop_h);
+  if (!bad && !t.ok) bad |= 2;
+  if (j == 0) p.status[b] = bad;
+  // 6. joints, condition, target centres
+  if (on) {
+    GeomPoint g = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (!bad) g = geom_point(p.joints + (long)b * p.K * 3, p.joints_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m, true);
+    p.out_joints[i * 3] = g.x; p.out_joints[i * 3 + 1] = g.y; p.out_joints[i * 3 + 2] = g.z;
+    p.out_joints_vis[i * 3] = g.v0; p.out_joints_vis[i * 3 + 1] = g.v1; p.out_joints_vis[i * 3 + 2] = g.v2;
+    p.target_xy[i * 3] = bad ? 0.f : target_centre(g.x, p.stride_x);
+    p.target_xy[i * 3 + 1] = bad ? 0.f : target_centre(g.y, p.stride_y);
+    p.target_xy[i * 3 + 2] = 0.f;
+    p.target_vis[i] = (float)g.v0;
+    if (has_cond) {
+      GeomPoint c = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (!bad) c = geom_point(p.cond + (long)b * p.K * 3, p.cond_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m, true);
+      p.out_cond[i * 3] = c.x; p.out_cond[i * 3 + 1] = c.y; p.out_cond[i * 3 + 2] = c.z;
+      p.out_cond_vis[i * 3] = c.v0; p.out_cond_vis[i * 3 + 1] = c.v1; p.out_cond_vis[i * 3 + 2] = c.v2;
+      p.cond_trunc[i * 2] = (float)trunc(c.x);
+      p.cond_trunc[i * 2 + 1] = (float)trunc(c.y);
+    }
+  }
+  if (j != 0) return;
+  // 8. meta
+  p.out_center[2 * b] = bad ? 0.f : cx; p.out_center[2 * b + 1] = bad ? 0.f : cy;
+  p.out_scale[2 * b] = bad ? 0.0 : sc0; p.out_scale[2 * b + 1] = bad ? 0.0 : sc1;
+  p.out_rotation[b] = p.draws[4 * b + 3];
+  if (bad) return;
+  // 7. keep-rectangle
+  int rx = 0, ry = 0, rw = 0, rh = 0;
+  if (p.keep_rect && has_box) {
+    int x = trunc_int(bx), y = trunc_int(by), w = trunc_int(bw), h = trunc_int(bh);
+    if (p.bbox_aug) {
+      const int xd = floor_div10((long long)w * p.bbox_draws[2 * b]), yd = floor_div10((long long)h * p.bbox_draws[2 * b + 1]);
+      x = x - xd > 0 ? x - xd : 0;
+      y = y - yd > 0 ? y - yd : 0;
+      w = w + 2 * xd;
+      h = h + 2 * yd;
+    }
+    rx = max(x, 0); ry = max(y, 0);
+    rw = x + w - rx; rh = y + h - ry;
+  }
+  it->flip = flip ? 1 : 0;
+  it->rx = rx; it->ry = ry; it->rw = rw; it->rh = rh;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) it->m[k] = t.m[k];
+}
+
+extern "C" int buctd_sample_geometry(const buctd_sample_geom_args* a, void* stream) {
+  BUCTD_CHECK_ARG(a && a->joints && a->joints_vis && a->center && a->scale && a->bbox && a->half_body && a->draws &&
+                      a->bbox_draws && a->flags && a->pair && a->items && a->out_joints && a->out_joints_vis &&
+                      a->target_xy && a->target_vis && a->out_center && a->out_scale && a->out_rotation && a->status,
+                  "buctd_sample_geometry: NULL argument (only the condition's five may be NULL)");
+  const bool all = a->cond && a->cond_vis && a->out_cond && a->out_cond_vis && a->cond_trunc;
+  const bool none = !a->cond && !a->cond_vis && !a->out_cond && !a->out_cond_vis && !a->cond_trunc;
+  BUCTD_CHECK_ARG(all || none, "buctd_sample_geometry: cond, cond_vis, out_cond, out_cond_vis and cond_trunc go together");
+  BUCTD_CHECK_ARG(a->B > 0 && a->B < (1 << 20) && a->K > 0 && a->K <= 32, "buctd_sample_geometry: B > 0, 0 < K <= 32");
+  BUCTD_CHECK_ARG(a->crop_w > 0 && a->crop_h > 0 && a->aspect_ratio > 0.0 && a->stride_x > 0.0 && a->stride_y > 0.0,
+                  "buctd_sample_geometry: sizes, strides and the aspect ratio must be positive");
+  hipLaunchKernelGGL(sample_geometry_kernel, dim3(ceil_div(a->B, 4)), dim3(256), 0, (hipStream_t)stream, *a);
+  BUCTD_CHECK_LAUNCH("buctd_sample_geometry");
+  return BUCTD_OK;
+}

@@ -3,7 +3,8 @@
 DeviceSamplePipeline does what the DataLoader workers of the reference do per sample in
 lib/dataset/JointsDataset.py:134-361 - box -> (half-body / scale / rotation / flip augmentation) -> affine crop ->
 ToTensor/Normalize -> key points into crop coordinates -> Gaussian target + condition heat-map - for a whole batch:
-the scalar geometry (a few dozen float64 operations per person, the same expressions as the reference) stays on the host,
+the scalar geometry (a few dozen float64 operations per person, the same expressions as the reference) stays on the host
+(or, with geometry_on_device=True, is one buctd_sample_geometry launch per batch),
 every per-pixel step is one batched HIP kernel writing straight into the NCHW network input, the target and the
 target weights.  Decoded images are uint8 HWC tensors already resident on the device (JPEG decoding is host I/O).
 
@@ -25,12 +26,16 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._C import RefineArgs, check, lib, ptr, stream_ptr
+from .._C import RefineArgs, SampleGeomArgs, check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
 from ..utils.transforms import _swap_table, affine_transform, fliplr_joints, get_affine_transform
 from .pose_synthesis import synthesize_pose_batch
 
 _M64 = (1 << 64) - 1
+MAX_DEVICE_JOINTS = 32         # buctd_sample_geometry, buctd_refine_step, buctd_cond_geometry: one lane per joint
+GEOM_HAS_BBOX, GEOM_USE_BU_BBOX, GEOM_HALF_BODY, GEOM_FLIP = 1, 2, 4, 8      # BUCTD_GEOM_* of include/buctd_hip.h
+NO_BOX = ("sample(s) {bad} of the batch: use_bu_bbox with a condition pose without a non-zero x or y coordinate, or a "
+          "box without extent (status {status}): there is no box to crop")
 NO_CONDITION = ("Training with empirical sampling is not possible without providing 'cond_kpts'; "
                 "please train with generative sampling (DATASET.SYNTHESIS_POSE=True)")
 
@@ -38,6 +43,13 @@ NO_CONDITION = ("Training with empirical sampling is not possible without provid
 class _WarpItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("flip", C.c_int), ("rx", C.c_int),
                 ("ry", C.c_int), ("rw", C.c_int), ("rh", C.c_int), ("m", C.c_double * 6)]
+
+
+# the same struct for numpy: a whole table is filled column by column
+WARP_ITEM = np.dtype({"names": [f[0] for f in _WarpItem._fields_],
+                      "formats": [np.uint64] + [np.int32] * 7 + [(np.float64, 6)],
+                      "offsets": [getattr(_WarpItem, f[0]).offset for f in _WarpItem._fields_],
+                      "itemsize": C.sizeof(_WarpItem)})
 
 
 def xywh2cs(x, y, w, h, aspect_ratio, scale_thre, pixel_std=200):
@@ -59,6 +71,22 @@ def box_from_keypoints(kp, margin, img_w, img_h):
     xmin, ymin = np.clip(xs.min() - margin, 0, img_w), np.clip(ys.min() - margin, 0, img_h)
     xmax, ymax = np.clip(xs.max() + margin, 0, img_w), np.clip(ys.max() + margin, 0, img_h)
     return [xmin, ymin, xmax - xmin, ymax - ymin]
+
+
+def keep_rectangle(bbox, bbox_draws=None):
+    """The rectangle of DATASET.NEW_AUGMENTATION (JointsDataset.py:263-279): source pixels outside the person box are
+    zeroed before the warp.  bbox: x, y, w, h, truncated like np.array(bbox).astype(int); bbox_draws: the two
+    randint(0, 20) of DATASET.BBOX_AUGMENTATION (lines 267-273) or None.  Returns (rx, ry, rw, rh) of buctd_warp_item, cut
+    at the origin as oracle.sample.warp_affine_u8 keeps it (rx = max(x, 0), rw = x + w - rx; the reference's negative
+    slice indices wrap around instead: out of scope).  buctd_sample_geometry restates these lines."""
+    x, y, w, h = (int(v) for v in np.array(bbox).astype(int))
+    if bbox_draws is not None:
+        x_delta, y_delta = w * int(bbox_draws[0]) // 10, h * int(bbox_draws[1]) // 10
+        x = int(x - x_delta) if x - x_delta > 0 else 0
+        y = int(y - y_delta) if y - y_delta > 0 else 0
+        w, h = int(w + 2 * x_delta), int(h + 2 * y_delta)
+    rx, ry = max(x, 0), max(y, 0)
+    return rx, ry, x + w - rx, y + h - ry
 
 
 def synthesis_area(cond):
@@ -104,6 +132,28 @@ def trunc_condition(cond):
     return np.ascontiguousarray(np.trunc(np.asarray(cond, dtype=np.float64)[:, :, :2]).astype(np.float32))
 
 
+def _layout(sections):
+    """[(name, numpy dtype, shape)] -> ({name: (byte offset, dtype, shape)}, total bytes); widest items first, so every
+    section is aligned to its item size."""
+    at, off = {}, 0
+    for name, dt, shape in sorted(sections, key=lambda t: -np.dtype(t[1]).itemsize):
+        at[name] = (off, np.dtype(dt), tuple(shape))
+        off += int(np.prod(shape)) * np.dtype(dt).itemsize
+    return at, off
+
+
+def _views(buf, at):
+    """Typed views of the sections of a uint8 tensor (device) or numpy array (host)."""
+    out = {}
+    for name, (off, dt, shape) in at.items():
+        raw = buf[off:off + int(np.prod(shape)) * dt.itemsize]
+        if torch.is_tensor(raw):
+            out[name] = raw.view(getattr(torch, dt.name)).view(shape)
+        else:
+            out[name] = raw.view(dt).reshape(shape)
+    return out
+
+
 def batch_seed(seed, call):
     """64-bit synthesis seed of call number `call` of a pipeline seeded with `seed` (splitmix64 finaliser: seeds of
     consecutive calls share no counter sequence of the generator in csrc/synth.hip)."""
@@ -130,12 +180,30 @@ class DeviceSamplePipeline:
     The variant of the synthesis is cfg.DATASET.DATASET's: 'coco', 'crowdpose', or the generic one for any other name
     (fish, marmosets, multimouse, a custom data set; pose_synthesis.py:798-816).
 
+    geometry_on_device=True (train pipelines, NUM_JOINTS <= 32): the scalar geometry leaves the host as well.  __call__
+    makes the augmentation draws with the same generators in the same order as the host path (draw(); aug = a list of
+    draw() results replays them), uploads the records and the draws as one packed buffer and launches
+    buctd_sample_geometry: box (the record's, or under use_bu_bbox the one around the condition pose - the synthesized
+    pose never leaves the device, there is no host fallback), half-body override (decided and boxed on the host), scale
+    draw, flip, crop affine in closed form (utils.transforms.crop_affine_rot_closed_form), joints and condition in crop
+    coordinates, target centres, keep-rectangle.  The crop, target and condition kernels read what it wrote.  On this
+    path meta['joints'], ['joints_vis'], ['cond_joints'], ['cond_joints_vis'], ['center'], ['scale'] (float64: see
+    apply_draw), ['rotation'] (float64) are DEVICE tensors, meta['table'] is the buctd_warp_item table and
+    meta['status'] the kernel's int32 status per sample; nothing is copied back and the call does not wait for the
+    device.  A sample without a box (use_bu_bbox with a condition that has no non-zero x or no non-zero y; the host path's
+    synthesis_area raises for such a condition) gets status != 0 and an all-zero sample instead of an exception:
+    check(meta) reads the status back and raises the ValueError.  Default False: the host path, bit for bit.
+
+    Keep-rectangle (both paths): with is_train and DATASET.NEW_AUGMENTATION a sample that has a box - rec['bbox'], or under
+    use_bu_bbox the box around its condition - is cropped from an image zeroed outside that box (JointsDataset.py:263-279),
+    widened by the DATASET.BBOX_AUGMENTATION draws; records without 'bbox' are cropped as before.
+
     joints_weight ([K] or [K, 1], the data set class's self.joints_weight): with cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT
     every target_weight is multiplied by it on the device (JointsDataset.py:450-451); without the flag, or with None,
     it is not looked at."""
 
     def __init__(self, cfg, flip_pairs=(), upper_body_ids=(), kpt_colors=None, mean=(0.485, 0.456, 0.406),
-                 std=(0.229, 0.224, 0.225), is_train=False, seed=0, joints_weight=None):
+                 std=(0.229, 0.224, 0.225), is_train=False, seed=0, joints_weight=None, geometry_on_device=False):
         self.cfg = cfg
         self.is_train = is_train
         self.num_joints = cfg.MODEL.NUM_JOINTS
@@ -153,6 +221,8 @@ class DeviceSamplePipeline:
         self.num_joints_half_body = getattr(ds, "NUM_JOINTS_HALF_BODY", 8)
         self.prob_half_body = getattr(ds, "PROB_HALF_BODY", 0.0)
         self.bu_bbox_margin = getattr(ds, "BU_BBOX_MARGIN", 25)
+        self.new_augmentation = bool(getattr(ds, "NEW_AUGMENTATION", False))
+        self.bbox_augmentation = bool(getattr(ds, "BBOX_AUGMENTATION", False))
         self.scale_thre = getattr(cfg.TEST, "SCALE_THRE", 1.25)
         self.flip_pairs = [list(p) for p in flip_pairs]
         self.upper_body_ids = set(upper_body_ids)
@@ -173,6 +243,14 @@ class DeviceSamplePipeline:
                 raise ValueError(f"joints_weight has shape {jw.shape}, MODEL.NUM_JOINTS is {self.num_joints}")
             self.joints_weight = np.ascontiguousarray(jw.reshape(1, self.num_joints, 1))
         self._weight_dev = {}
+        self.geometry_on_device = bool(geometry_on_device)
+        if self.geometry_on_device:
+            if not is_train:
+                raise ValueError("DeviceSamplePipeline(geometry_on_device=True) is the train path (is_train=True): an eval "
+                                 "batch has no draws, and IterativeRefiner(on_device=True) keeps its geometry on the device")
+            if self.num_joints > MAX_DEVICE_JOINTS:
+                raise ValueError(f"DeviceSamplePipeline(geometry_on_device=True) handles at most {MAX_DEVICE_JOINTS} "
+                                 f"joints (MODEL.NUM_JOINTS is {self.num_joints})")
 
     # ---- host-side scalar geometry (reference expressions, float64) -----------------------------------------
     def half_body_transform(self, joints, joints_vis):
@@ -195,20 +273,42 @@ class DeviceSamplePipeline:
             w = h * self.aspect_ratio
         return center, np.array([w * 1.0 / 200, h * 1.0 / 200], dtype=np.float32) * 1.5
 
-    def draw_augmentation(self, rec, center, scale):
-        """The random part of JointsDataset.py:233-251 (same draws in the same order): returns center, scale, rot, flip."""
-        rot, flip = 0, False
+    def draw(self, rec):
+        """The random draws of one record, JointsDataset.py:236-269 (same generators, same order): dict(half_body =
+        (center, scale) of the half-body box or None, scale_mul = the clipped scale multiplier (None in eval mode: the
+        scale keeps its dtype), rot, flip, bbox_aug = the two randint(0, 20) of DATASET.BBOX_AUGMENTATION or None - drawn
+        after the flip, whether the record has a box or not).  geometry(rec, aug=<this dict>) replays it."""
+        d = dict(half_body=None, scale_mul=None, rot=0, flip=False, bbox_aug=None)
         if not self.is_train:
-            return center, scale, rot, flip
+            return d
         if np.sum(rec["joints_3d_vis"][:, 0]) > self.num_joints_half_body and self.np_rng.rand() < self.prob_half_body:
             c_hb, s_hb = self.half_body_transform(rec["joints_3d"], rec["joints_3d_vis"])
             if c_hb is not None and s_hb is not None:
-                center, scale = c_hb, s_hb
+                d["half_body"] = (c_hb, s_hb)
         sf, rf = self.scale_factor, self.rotation_factor
-        scale = scale * np.clip(self.np_rng.randn() * sf + 1, 1 - sf, 1 + sf)
-        rot = np.clip(self.np_rng.randn() * rf, -rf * 2, rf * 2) if self.py_rng.random() <= 0.6 else 0
-        flip = self.flip and self.py_rng.random() <= 0.5
-        return center, scale, rot, flip
+        d["scale_mul"] = np.clip(self.np_rng.randn() * sf + 1, 1 - sf, 1 + sf)
+        d["rot"] = np.clip(self.np_rng.randn() * rf, -rf * 2, rf * 2) if self.py_rng.random() <= 0.6 else 0
+        d["flip"] = self.flip and self.py_rng.random() <= 0.5
+        if self.new_augmentation and self.bbox_augmentation:
+            d["bbox_aug"] = (self.py_rng.randint(0, 20), self.py_rng.randint(0, 20))
+        return d
+
+    @staticmethod
+    def apply_draw(d, center, scale):
+        """center, scale after the half-body override and the scale draw of d = draw(rec).  float32 scale * the float64
+        numpy scalar of the draw is a FLOAT64 array (numpy >= 2, NEP 50): in train mode get_affine_transform and
+        meta['scale'] see a float64 scale, and buctd_sample_geometry follows that (tests/test_sample_geometry.py pins it)."""
+        if d["half_body"] is not None:
+            center, scale = d["half_body"]
+        if d["scale_mul"] is not None:
+            scale = scale * d["scale_mul"]
+        return center, scale
+
+    def draw_augmentation(self, rec, center, scale):
+        """The random part of JointsDataset.py:233-251 (same draws in the same order): returns center, scale, rot, flip."""
+        d = self.draw(rec)
+        center, scale = self.apply_draw(d, center, scale)
+        return center, scale, d["rot"], d["flip"]
 
     def condition(self, rec):
         """(cond_joints, cond_joints_vis, has_cond) of a record as float64 copies.  A conditional train pipeline gives a
@@ -234,8 +334,12 @@ class DeviceSamplePipeline:
         """Everything of a sample that is scalar: returns dict(trans, center, scale, rot, flip, joints, joints_vis,
         cond_joints, cond_joints_vis) with the key points already in crop coordinates.  aug = (center, scale, rot, flip)
         replaces the random draws (parity tests); center is the value BEFORE the flip mirrors it, like in the reference.
+        aug = a draw() result replays those draws instead: box, half-body override, scale multiplier, rotation, flip and
+        the BBOX_AUGMENTATION integers, as buctd_sample_geometry takes them.
         cond = (cond_joints, cond_joints_vis) replaces the record's condition (a synthesized pose); cond = False leaves
-        the condition out (it is transformed on the device): cond_joints / cond_joints_vis come back as zeros."""
+        the condition out (it is transformed on the device): cond_joints / cond_joints_vis come back as zeros.
+        keep_rect (only with is_train and DATASET.NEW_AUGMENTATION, for a sample that has a box - the record's 'bbox', or
+        under use_bu_bbox the condition's): keep_rectangle() of it, which warp_table() hands to the crop kernel."""
         img = rec["image"]
         ih, iw = int(img.shape[0]), int(img.shape[1])
         joints = np.array(rec["joints_3d"], dtype=np.float64).copy()
@@ -247,15 +351,23 @@ class DeviceSamplePipeline:
         else:
             cj, cv, has_cond = np.array(cond[0], dtype=np.float64).copy(), np.array(cond[1], dtype=np.float64).copy(), True
         if rec.get("use_bu_bbox", False) and has_cond and cj[:, 0].sum() != 0 and cj[0, 1].sum() != 0:
-            x, y, w, h = box_from_keypoints(cj, self.bu_bbox_margin, iw, ih)
-            center, scale = xywh2cs(x, y, w, h, self.aspect_ratio, self.scale_thre)
+            bbox = box_from_keypoints(cj, self.bu_bbox_margin, iw, ih)
+            center, scale = xywh2cs(*bbox, self.aspect_ratio, self.scale_thre)
         else:
             center = np.array(rec["center"], dtype=np.float32).copy()
             scale = np.array(rec["scale"], dtype=np.float32).copy()
-        if aug is None:
-            center, scale, rot, flip = self.draw_augmentation(rec, center, scale)
+            bbox = rec.get("bbox")
+        bbox_aug = None
+        if aug is None or isinstance(aug, dict):
+            d = self.draw(rec) if aug is None else aug
+            center, scale = self.apply_draw(d, center, scale)
+            center = np.array(center, np.float32).copy()
+            rot, flip, bbox_aug = d["rot"], d["flip"], d["bbox_aug"]
         else:
             center, scale, rot, flip = np.array(aug[0], np.float32).copy(), np.array(aug[1], np.float32), aug[2], aug[3]
+        keep_rect = None
+        if self.is_train and self.new_augmentation and bbox is not None:
+            keep_rect = keep_rectangle(bbox, bbox_aug)
         if flip:
             joints, joints_vis = fliplr_joints(joints, joints_vis, iw, self.flip_pairs)
             center[0] = iw - center[0] - 1
@@ -268,7 +380,7 @@ class DeviceSamplePipeline:
             if has_cond and cv[i, 0] > 0.0:
                 cj[i, 0:2] = affine_transform(cj[i, 0:2], trans)
         return dict(trans=trans, center=center, scale=scale, rot=rot, flip=bool(flip), joints=joints,
-                    joints_vis=joints_vis, cond_joints=cj, cond_joints_vis=cv)
+                    joints_vis=joints_vis, cond_joints=cj, cond_joints_vis=cv, keep_rect=keep_rect)
 
     # ---- batched device work -----------------------------------------------------------------------------------
     def warp_table(self, images, geos):
@@ -287,28 +399,35 @@ class DeviceSamplePipeline:
                 items[b].m[k] = float(v)
         return torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(images[0].device)
 
+    def pair_table(self, dev):
+        """int32 [K] on the device: the flip partner of every joint, -1 for a joint without one (uploaded once)."""
+        pair = self._pair_dev.get(dev)
+        if pair is None:
+            K = self.num_joints
+            swap = _swap_table(K, self.flip_pairs)
+            pair = torch.from_numpy(np.where(swap == np.arange(K), -1, swap).astype(np.int32)).to(dev)
+            self._pair_dev[dev] = pair
+        return pair
+
     def cond_geometry(self, synth, cond_vis, table):
         """Flip + crop affine of device-resident condition poses (buctd_cond_geometry).  synth, cond_vis: float64 device
         tensors [B, K, 3]; table: warp_table().  Returns cond_joints, cond_joints_vis (float64) and the truncated
         coordinates float32 [B, K, 2] that render(cond_trunc=...) takes - all on the device."""
         dev = synth.device
         B, K = int(synth.shape[0]), int(synth.shape[1])
-        pair = self._pair_dev.get(dev)
-        if pair is None:
-            swap = _swap_table(K, self.flip_pairs)
-            pair = torch.from_numpy(np.where(swap == np.arange(K), -1, swap).astype(np.int32)).to(dev)
-            self._pair_dev[dev] = pair
+        pair = self.pair_table(dev)
         cj, cv = torch.empty_like(synth), torch.empty_like(cond_vis)
         cjt = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
         check(lib().buctd_cond_geometry(ptr(synth), ptr(cond_vis), ptr(table), ptr(pair), B, K, ptr(cj), ptr(cv), ptr(cjt),
                                         stream_ptr()), "cond_geometry")
         return cj, cv, cjt
 
-    def render(self, images, geos, want_crop=False, table=None, cond_trunc=None):
+    def render(self, images, geos, want_crop=False, table=None, cond_trunc=None, targets=None):
         """images: uint8 HWC device tensors; geos: geometry() results.  Returns input [B, 3(+3), H, W], target
         [B, K, h, w], target_weight [B, K, 1] (+ the uint8 crops) on the device.  table: warp_table(images, geos) if the
         caller built it already; cond_trunc: the condition coordinates as cond_geometry() returns them, instead of
-        geos[.]['cond_joints']."""
+        geos[.]['cond_joints']; targets: (target centres float32 [B, K, 3], visibilities float32 [B, K]) on the device as
+        buctd_sample_geometry wrote them, instead of geos[.]['joints'] / ['joints_vis'] (geos is not read then)."""
         dev = images[0].device
         B, K = len(images), self.num_joints
         W, H = int(self.image_size[0]), int(self.image_size[1])
@@ -326,11 +445,12 @@ class DeviceSamplePipeline:
         # well, so it is handed a v that maps back to the same mu: mu * stride for mu >= 0 and (mu - 1) * stride for mu < 0
         # (v / stride + 0.5 = mu - 0.5 truncates to mu; mu * stride would give mu + 0.5 -> mu + 1 for negative centres:
         # visible joints left of / above the crop would get a shifted Gaussian and a shifted target_weight cut-off)
-        stride = self.image_size / self.heatmap_size
-        jt = target_centres(np.stack([g["joints"] for g in geos]), stride)
-        vis = np.stack([g["joints_vis"][:, 0] for g in geos]).astype(np.float32)
-        target, weight = ops.gaussian_target(torch.from_numpy(jt).to(dev), torch.from_numpy(vis).to(dev),
-                                             self.heatmap_size, self.image_size, self.sigma)
+        if targets is None:
+            stride = self.image_size / self.heatmap_size
+            jt = target_centres(np.stack([g["joints"] for g in geos]), stride)
+            vis = np.stack([g["joints_vis"][:, 0] for g in geos]).astype(np.float32)
+            targets = torch.from_numpy(jt).to(dev), torch.from_numpy(vis).to(dev)
+        target, weight = ops.gaussian_target(targets[0], targets[1], self.heatmap_size, self.image_size, self.sigma)
         if self.joints_weight is not None:
             # np.multiply(target_weight, self.joints_weight) of JointsDataset.py:450-451, the batch at once
             jw = self._weight_dev.get((dev, B))
@@ -395,6 +515,153 @@ class DeviceSamplePipeline:
         self.render_condition(x, cond_trunc, colors)
         return x
 
+    # ---- scalar geometry on the device (geometry_on_device=True) ------------------------------------------------
+    def draw_table(self, records, aug=None):
+        """The draws of a batch as the columns buctd_sample_geometry reads: draw() per record, in record order (the same
+        generator calls as the host path makes), or aug = a list of draw() results.  Returns numpy arrays: half_body
+        float32 [B, 4] (center, scale of the override), draws float64 [B, 4] (scale multiplier, sin and cos of the rotation
+        - evaluated here, in float64, by the calls get_dir makes - and the rotation in degrees), bbox_draws int32 [B, 2],
+        flags int32 [B] (GEOM_HALF_BODY, GEOM_FLIP)."""
+        B = len(records)
+        draws = [self.draw(r) for r in records] if aug is None else list(aug)
+        if len(draws) != B or not all(isinstance(d, dict) for d in draws):
+            raise ValueError("geometry_on_device: aug is a list of draw() results, one per record (center and scale of a "
+                             "(center, scale, rot, flip) tuple would replace the box the kernel forms)")
+        rot = [d["rot"] for d in draws]
+        hb = np.zeros((B, 4), dtype=np.float32)
+        has_hb = np.array([d["half_body"] is not None for d in draws], dtype=bool)
+        if has_hb.any():
+            hb[has_hb] = np.array([np.concatenate(d["half_body"]) for d in draws if d["half_body"] is not None], np.float32)
+        dr = np.empty((B, 4), dtype=np.float64)
+        dr[:, 0] = [d["scale_mul"] for d in draws]
+        dr[:, 1] = [np.sin(np.pi * r / 180) for r in rot]
+        dr[:, 2] = [np.cos(np.pi * r / 180) for r in rot]
+        dr[:, 3] = rot
+        bd = np.array([d["bbox_aug"] if d["bbox_aug"] is not None else (0, 0) for d in draws], dtype=np.int32).reshape(B, 2)
+        flags = has_hb * GEOM_HALF_BODY + np.array([bool(d["flip"]) for d in draws], dtype=bool) * GEOM_FLIP
+        return dict(half_body=hb, draws=dr, bbox_draws=bd, flags=flags.astype(np.int32))
+
+    def device_geometry(self, records, table, cond=None, cond_vis=None):
+        """One upload and one buctd_sample_geometry launch for a batch.  table: draw_table(); cond: the condition poses
+        [B, K, 3] in image coordinates - a float64 device tensor (buctd_synthesize_pose's output) or a host array - and
+        cond_vis their visibilities (host array), both None without a condition.  Returns device tensors: items (the
+        table of buctd_warp_affine_norm), joints, joints_vis, cond_joints, cond_joints_vis (float64 [B, K, 3]), cond_trunc
+        (float32 [B, K, 2]), target_xy, target_vis (the inputs of buctd_gaussian_target), center (float32 [B, 2]), scale
+        (float64 [B, 2]: see apply_draw), rotation (float64 [B]) and status (int32 [B])."""
+        images = [r["image"] for r in records]
+        for img in images:
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not img.is_cuda:
+                raise ValueError("images must be contiguous uint8 [H, W, 3] device tensors")
+        dev = images[0].device
+        B, K = len(records), self.num_joints
+        f32, f64, i32 = np.float32, np.float64, np.int32
+        has_cond = cond is not None
+        cond_on_device = has_cond and torch.is_tensor(cond)
+        sections = [("joints", f64, (B, K, 3)), ("joints_vis", f64, (B, K, 3)), ("bbox", f64, (B, 4)), ("draws", f64, (B, 4)),
+                    ("items", np.uint64, (B, WARP_ITEM.itemsize // 8)), ("center", f32, (B, 2)), ("scale", f32, (B, 2)),
+                    ("half_body", f32, (B, 4)), ("flags", i32, (B,)), ("bbox_draws", i32, (B, 2))]
+        if has_cond:
+            sections.append(("cond_vis", f64, (B, K, 3)))
+            if not cond_on_device:
+                sections.append(("cond", f64, (B, K, 3)))
+        at_in, n_in = _layout(sections)
+        host = np.zeros(n_in, dtype=np.uint8)
+        hv = _views(host, at_in)
+        hv["joints"][:] = np.stack([np.asarray(r["joints_3d"], dtype=f64).reshape(K, 3) for r in records])
+        hv["joints_vis"][:] = np.stack([np.asarray(r["joints_3d_vis"], dtype=f64).reshape(K, 3) for r in records])
+        hv["center"][:] = np.stack([np.asarray(r["center"], dtype=f32).reshape(2) for r in records])
+        hv["scale"][:] = np.stack([np.asarray(r["scale"], dtype=f32).reshape(2) for r in records])
+        has_bbox = np.array(["bbox" in r for r in records], dtype=bool)
+        if has_bbox.any():
+            hv["bbox"][has_bbox] = np.array([r["bbox"] for r in records if "bbox" in r], dtype=f64).reshape(-1, 4)
+        use_bu = np.array([bool(r.get("use_bu_bbox", False)) for r in records], dtype=bool)
+        hv["flags"][:] = table["flags"] + has_bbox * GEOM_HAS_BBOX + use_bu * GEOM_USE_BU_BBOX
+        for key in ("draws", "half_body", "bbox_draws"):
+            hv[key][:] = table[key]
+        if has_cond:
+            hv["cond_vis"][:] = np.asarray(cond_vis, dtype=f64).reshape(B, K, 3)
+            if not cond_on_device:
+                hv["cond"][:] = np.asarray(cond, dtype=f64).reshape(B, K, 3)
+        items = hv["items"].reshape(-1).view(WARP_ITEM)
+        items["src"] = [img.data_ptr() for img in images]
+        items["H"] = [img.shape[0] for img in images]
+        items["W"] = [img.shape[1] for img in images]
+        sv = _views(torch.from_numpy(host).to(dev), at_in)
+        outs = [("joints", f64, (B, K, 3)), ("joints_vis", f64, (B, K, 3)), ("scale", f64, (B, 2)), ("rotation", f64, (B,)),
+                ("target_xy", f32, (B, K, 3)), ("target_vis", f32, (B, K)), ("center", f32, (B, 2)), ("status", i32, (B,))]
+        if has_cond:
+            outs += [("cond_joints", f64, (B, K, 3)), ("cond_joints_vis", f64, (B, K, 3)), ("cond_trunc", f32, (B, K, 2))]
+        at_out, n_out = _layout(outs)
+        out = _views(torch.empty(n_out, dtype=torch.uint8, device=dev), at_out)
+        a = SampleGeomArgs()
+        a.joints, a.joints_vis, a.center, a.scale, a.bbox = (ptr(sv[k]) for k in ("joints", "joints_vis", "center", "scale", "bbox"))
+        a.half_body, a.draws, a.bbox_draws, a.flags = (ptr(sv[k]) for k in ("half_body", "draws", "bbox_draws", "flags"))
+        a.pair, a.items = ptr(self.pair_table(dev)), ptr(sv["items"])
+        if has_cond:
+            if cond_on_device and (cond.dtype != torch.float64 or tuple(cond.shape) != (B, K, 3) or not cond.is_contiguous()):
+                raise ValueError("device_geometry: cond must be a contiguous float64 [B, K, 3] tensor")
+            a.cond, a.cond_vis = ptr(cond if cond_on_device else sv["cond"]), ptr(sv["cond_vis"])
+            a.out_cond, a.out_cond_vis, a.cond_trunc = ptr(out["cond_joints"]), ptr(out["cond_joints_vis"]), ptr(out["cond_trunc"])
+        a.out_joints, a.out_joints_vis, a.target_xy, a.target_vis = (ptr(out[k]) for k in ("joints", "joints_vis", "target_xy", "target_vis"))
+        a.out_center, a.out_scale, a.out_rotation, a.status = (ptr(out[k]) for k in ("center", "scale", "rotation", "status"))
+        a.B, a.K, a.crop_w, a.crop_h = B, K, int(self.image_size[0]), int(self.image_size[1])
+        a.keep_rect, a.bbox_aug = int(self.is_train and self.new_augmentation), int(self.bbox_augmentation)
+        a.margin, a.aspect_ratio, a.scale_thre = float(self.bu_bbox_margin), float(self.aspect_ratio), float(self.scale_thre)
+        stride = self.image_size / self.heatmap_size
+        a.stride_x, a.stride_y = float(stride[0]), float(stride[1])
+        check(lib().buctd_sample_geometry(C.byref(a), stream_ptr()), "sample_geometry")
+        out["items"] = sv["items"]
+        return out
+
+    def check(self, meta):
+        """Reads meta['status'] of a geometry_on_device batch back (one copy, one wait) and raises the host path's
+        ValueError for a sample without a box; batches of the host path have no status and pass."""
+        status = meta.get("status")
+        if status is None:
+            return
+        st = status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size:
+            raise ValueError("pose synthesis: a condition without a non-zero x or y coordinate has no area - " +
+                             NO_BOX.format(bad=bad.tolist(), status=st[bad].tolist()))
+
+    def call_on_device(self, records, aug=None, seed=None):
+        """__call__ with geometry_on_device=True: the draws on the host, everything after them on the device."""
+        images = [r["image"] for r in records]
+        table = self.draw_table(records, aug)
+        extra, cond, cond_vis = {}, None, None
+        if self.synthesizes:
+            if seed is None:
+                seed = batch_seed(self.seed, self.synth_calls)
+                self.synth_calls += 1
+            J, E, V, near, area = self.synthesis_inputs(records)
+            cond = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
+                                         device=images[0].device)
+            cond_vis = V
+            extra["synth_joints"] = cond
+        else:
+            conds = [self.condition(r) for r in records]
+            if all(c[2] for c in conds):
+                cond, cond_vis = np.stack([c[0] for c in conds]), np.stack([c[1] for c in conds])
+            elif any(c[2] for c in conds):
+                raise ValueError("geometry_on_device: either every record of a batch carries 'cond_joints' or none does")
+        g = self.device_geometry(records, table, cond, cond_vis)
+        x, target, weight = self.render(images, None, table=g["items"], cond_trunc=g.get("cond_trunc"),
+                                        targets=(g["target_xy"], g["target_vis"]))
+        zeros = None if cond is not None else torch.zeros_like(g["joints"])
+        meta = {
+            "image": [r.get("image_file", "") for r in records],
+            "joints": g["joints"], "joints_vis": g["joints_vis"],
+            "cond_joints": g["cond_joints"] if zeros is None else zeros,
+            "cond_joints_vis": g["cond_joints_vis"] if zeros is None else zeros,
+            "center": g["center"], "scale": g["scale"], "rotation": g["rotation"],
+            "score": torch.tensor([float(r.get("score", 1)) for r in records]),
+            "annotation_id": torch.tensor([int(r.get("annotation_id", -1)) for r in records]),
+            "status": g["status"], "table": g["items"],
+        }
+        meta.update(extra)
+        return x, target, weight, meta
+
     def synthesis_inputs(self, records):
         """Host side of JointsDataset.py:165-167 and 204-212 for a batch: ground-truth joints [B, K, 3], the conditions
         they are perturbed around and their visibilities, the neighbours [B, M, K, 3] (or None) and the areas [B]."""
@@ -411,6 +678,8 @@ class DeviceSamplePipeline:
         for conditional models, 'cond_joints' / 'cond_joints_vis' (+ 'score', 'annotation_id', 'use_bu_bbox'; under
         generative sampling 'near_joints', see the class docstring).  seed: of the pose synthesis of this batch.
         Returns (input, target, target_weight, meta) like a collated DataLoader batch of the reference."""
+        if self.geometry_on_device:
+            return self.call_on_device(records, aug, seed)
         images = [r["image"] for r in records]
         extra = {}
         if self.synthesizes:
@@ -549,27 +818,8 @@ class IterativeRefiner:
         a.in_vis_thre, a.scale_thre = float(self.in_vis_thre), float(pipe.scale_thre)
         check(lib().buctd_refine_step(C.byref(a), stream_ptr()), "refine_step")
 
-    @staticmethod
-    def _layout(sections):
-        """[(name, numpy dtype, shape)] -> ({name: (byte offset, dtype, shape)}, total bytes); widest items first, so every
-        section is aligned to its item size."""
-        at, off = {}, 0
-        for name, dt, shape in sorted(sections, key=lambda t: -np.dtype(t[1]).itemsize):
-            at[name] = (off, np.dtype(dt), tuple(shape))
-            off += int(np.prod(shape)) * np.dtype(dt).itemsize
-        return at, off
-
-    @staticmethod
-    def _views(buf, at):
-        """Typed views of the sections of a uint8 tensor (device) or numpy array (host)."""
-        out = {}
-        for name, (off, dt, shape) in at.items():
-            raw = buf[off:off + int(np.prod(shape)) * dt.itemsize]
-            if torch.is_tensor(raw):
-                out[name] = raw.view(getattr(torch, dt.name)).view(shape)
-            else:
-                out[name] = raw.view(dt).reshape(shape)
-        return out
+    _layout = staticmethod(_layout)
+    _views = staticmethod(_views)
 
     def run_on_device(self, records, passes=3):
         """run() with on_device=True: one upload before the first pass, one copy back after the last."""

@@ -123,6 +123,84 @@ def crop_affine_closed_form(center, scale, output_size, inv=0):
     return t
 
 
+def _two_sum(a, b):
+    """a + b = s + e exactly (Knuth), float64."""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _split(a):
+    """a = h + l with 26-bit halves (Veltkamp)."""
+    c = 134217729.0 * a
+    h = c - (c - a)
+    return h, a - h
+
+
+def _two_prod(a, b):
+    """a * b = p + e exactly (Dekker: no fused multiply-add), float64."""
+    p = a * b
+    ah, al = _split(a)
+    bh, bl = _split(b)
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _cross(a, u, b, v):
+    """a * (u[0] + u[1]) - b * (v[0] + v[1]) with the cancellation of the two leading products done exactly."""
+    p1, e1 = _two_prod(a, u[0])
+    p2, e2 = _two_prod(b, v[0])
+    s, es = _two_sum(p1, -p2)
+    return s + ((es + (e1 - e2)) + (a * u[1] - b * v[1]))
+
+
+def crop_affine_rot_closed_form(center, scale, sn, cs, output_size):
+    """get_affine_transform(center, scale, rot, output_size) for any rotation, without the solve; sn, cs = sin and cos of
+    pi * rot / 180 in float64.  center is float32; scale keeps its dtype (float32 records, float64 after the train path's
+    scale draw: numpy multiplies a float32 array by a float64 scalar in float64), as `scale * 200.0` does there.
+
+    The box triangle P0, P1, P2 is the one _triangle / get_3rd_point build, with their float32 roundings; the crop
+    triangle is (a, b), (a, b - a), (0, b - a) with a, b = half the crop size, exact in float32.  The 2x2 part A solves
+    A (P1 - P0) = (0, -a) and A (P2 - P1) = (-a, 0):
+
+        A = [[a * d1y, -a * d1x], [-a * d2y, a * d2x]] / det,   d1 = P1 - P0, d2 = P2 - P1, det = d1x * d2y - d2x * d1y
+
+    (d2 is d1 turned by a right angle up to the float32 roundings, so the two products of det have the same sign and
+    nothing cancels).  The translation (a, b) - A P0 cancels: evaluated from the rounded A its error is |dA| |P0|, thousands
+    of ulp of a small translation.  It is therefore written over the same denominator,
+
+        tx = a * (d1x * (d2y + cy) - d1y * (d2x + cx)) / det
+        ty = (d2y * (b * d1x + a * cx) - d2x * (b * d1y + a * cy)) / det
+
+    with the two differences of products taken exactly (_two_sum / _two_prod, which need no fused multiply-add).
+    Everything after the float32 triangle is float64, one rounding per operation.  buctd_sample_geometry
+    (csrc/sample.hip, crop_affine_rot) restates these lines.  tests/test_sample_geometry.py measures this form and the
+    solve against the exact rational solution."""
+    cx, cy = np.float32(center[0]), np.float32(center[1])
+    box = np.asarray(scale).reshape(-1)[0] * 200.0                       # only box[0] is used
+    y = box * -0.5
+    ax, ay = -(y * np.float64(sn)), y * np.float64(cs)                   # get_dir([0, y], rot): 0 * c - y * s, 0 * s + y * c
+    p1x, p1y = np.float32(np.float64(cx) + ax), np.float32(np.float64(cy) + ay)   # pts[1] = origin + arm, stored as float32
+    dx, dy = cx - p1x, cy - p1y                                          # get_3rd_point: float32 differences
+    p2x, p2y = p1x - dy, p1y + dx
+    cx, cy = np.float64(cx), np.float64(cy)
+    d1x, d1y = np.float64(p1x) - cx, np.float64(p1y) - cy
+    d2x, d2y = np.float64(p2x) - np.float64(p1x), np.float64(p2y) - np.float64(p1y)
+    det = d1x * d2y - d2x * d1y
+    if det == 0.0:
+        raise np.linalg.LinAlgError("crop_affine_rot_closed_form: the box has no extent")
+    a, b = np.float64(output_size[0]) * 0.5, np.float64(output_size[1]) * 0.5
+    t = np.zeros((2, 3), dtype=np.float64)
+    t[0, 0], t[0, 1] = (a * d1y) / det, -(a * d1x) / det
+    t[1, 0], t[1, 1] = -(a * d2y) / det, (a * d2x) / det
+    t[0, 2] = (a * _cross(d1x, _two_sum(d2y, cy), d1y, _two_sum(d2x, cx))) / det
+    qx, fx = _two_prod(b, d1x)
+    qy, fy = _two_prod(b, d1y)
+    wx, gx = _two_sum(qx, a * cx)                                        # a * cx, a * cy: exact (a float32 times a half-integer)
+    wy, gy = _two_sum(qy, a * cy)
+    t[1, 2] = _cross(d2y, (wx, gx + fx), d2x, (wy, gy + fy)) / det
+    return t
+
+
 def affine_transform(pt, t):
     return t[:, :2] @ np.array([pt[0], pt[1]], dtype=np.float64) + t[:, 2]
 

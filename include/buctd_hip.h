@@ -767,6 +767,68 @@ typedef struct {
   double margin, aspect_ratio, in_vis_thre, scale_thre;
 } buctd_refine_args;
 int buctd_refine_step(const buctd_refine_args* a, void* stream);
+/* Scalar geometry of a TRAIN batch on the device (JointsDataset.py:217-295, as DeviceSamplePipeline.geometry restates
+ * them on the host): from the records, the augmentation draws and (for generative sampling) the pose
+ * buctd_synthesize_pose left on the device to the table buctd_warp_affine_norm reads and the inputs of
+ * buctd_gaussian_target and buctd_cond_render_into.  Per sample, in the host's order and with the host's roundings
+ * (float64 products and sums are never fused):
+ *   box        flags & USE_BU_BBOX, a condition, its x sum != 0 and its joint 0 has y != 0: dataset.pipeline
+ *              box_from_keypoints (non-zero coordinates -+ margin, clipped to [0, W] x [0, H] of items[b]) and xywh2cs
+ *              with their float32 roundings; otherwise center / scale / bbox of the record.  (The x sum is a butterfly
+ *              sum: it can differ from numpy's in the last bit, which matters only where the x cancel to rounding.)
+ *   half body  flags & HALF_BODY: center, scale = half_body[b] (decided and boxed on the host);
+ *   scale      float32 scale widened to float64, times draws[b][0] (numpy: float32 array * float64 scalar is float64);
+ *   flip       flags & FLIP: center x = float32(float32(W - cx) - 1); fliplr_joints on the ground truth and the
+ *              condition (x = W - x - 1, pair exchange, joints * joints_vis);
+ *   m          get_affine_transform(center, scale, rot, crop size) in the closed form of
+ *              utils.transforms.crop_affine_rot_closed_form with sin / cos = draws[b][1], draws[b][2];
+ *   joints     ground truth and condition through m where vis[., 0] > 0; cond_trunc = trunc() of the condition;
+ *              target_xy = dataset.pipeline.target_centres, target_vis = float32(vis[., 0]);
+ *   rectangle  keep_rect set and the sample has a box (the record's, flags & HAS_BBOX, or the one formed above):
+ *              x, y, w, h = trunc(bbox), with bbox_aug set widened by bbox_draws as JointsDataset.py:267-273 do, then
+ *              cut at the origin (rx = max(x, 0), rw = x + w - rx: what oracle.sample.warp_affine_u8 keeps; the
+ *              reference's negative slice indices wrap around instead - out of scope) into items[b].rx .. rh, zeros
+ *              otherwise.  The kernel applies it to the mirrored image with the unmirrored box, like the reference.
+ * status (int32 [B], written): bit 0 - USE_BU_BBOX and a condition without a non-zero x or without a non-zero y,
+ * bit 1 - the box has no extent (the host's solve is singular); items[b] of such a sample stays as it is and its other
+ * outputs are zeros.  One wavefront per sample, lanes over joints: K <= 32.  One launch, no allocation, no
+ * synchronisation. */
+#define BUCTD_GEOM_HAS_BBOX 1
+#define BUCTD_GEOM_USE_BU_BBOX 2
+#define BUCTD_GEOM_HALF_BODY 4
+#define BUCTD_GEOM_FLIP 8
+typedef struct {
+  const double* joints;       /* [B][K][3] ground truth, image coordinates */
+  const double* joints_vis;   /* [B][K][3] */
+  const double* cond;         /* [B][K][3] condition pose, NULL (with cond_vis): non-conditional */
+  const double* cond_vis;     /* [B][K][3] */
+  const float* center;        /* [B][2] of the record */
+  const float* scale;         /* [B][2] of the record */
+  const double* bbox;         /* [B][4] x, y, w, h of the record (read with BUCTD_GEOM_HAS_BBOX) */
+  const float* half_body;     /* [B][4] center, scale of the override (read with BUCTD_GEOM_HALF_BODY) */
+  const double* draws;        /* [B][4] scale multiplier, sin, cos of the rotation, the rotation in degrees */
+  const int32_t* bbox_draws;  /* [B][2] the two randint(0, 20) of BBOX_AUGMENTATION */
+  const int32_t* flags;       /* [B] BUCTD_GEOM_* */
+  const int32_t* pair;        /* [K] flip partner, -1: none */
+  buctd_warp_item* items;     /* [B]: H, W read; flip, rx .. rh, m written */
+  double* out_joints;         /* [B][K][3] crop coordinates */
+  double* out_joints_vis;     /* [B][K][3] */
+  double* out_cond;           /* [B][K][3], NULL with cond */
+  double* out_cond_vis;       /* [B][K][3], NULL with cond */
+  float* cond_trunc;          /* [B][K][2], NULL with cond */
+  float* target_xy;           /* [B][K][3] the `joints` argument of buctd_gaussian_target */
+  float* target_vis;          /* [B][K] */
+  float* out_center;          /* [B][2] */
+  double* out_scale;          /* [B][2] */
+  double* out_rotation;       /* [B] */
+  int32_t* status;            /* [B] */
+  int B, K;
+  int crop_w, crop_h;
+  int keep_rect, bbox_aug;
+  double margin, aspect_ratio, scale_thre;
+  double stride_x, stride_y;  /* crop size / heat-map size */
+} buctd_sample_geom_args;
+int buctd_sample_geometry(const buctd_sample_geom_args* a, void* stream);
 
 /* Generative pose synthesis(dataset/pose_synthesis.py:6-817, called from JointsDataset.py:202-215): for every person
  * and joint one of the error types jitter / miss / inversion / swap / good is drawn and a key point proposed

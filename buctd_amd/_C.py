@@ -232,6 +232,8 @@ SIGNATURES = {
     "buctd_warp_affine_norm": (_I, [_P, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "buctd_cond_render_into": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _SZ, _P]),
     "buctd_cond_geometry": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "buctd_cond_mirror": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "buctd_mirror_rows": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P]),
     "buctd_refine_step": (_I, [C.POINTER(RefineArgs), _P]),
     "buctd_sample_geometry": (_I, [C.POINTER(SampleGeomArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),

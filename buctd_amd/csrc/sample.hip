@@ -154,6 +154,116 @@ extern "C" int buctd_cond_geometry(const double* synth, const double* cond_vis, 
   return BUCTD_OK;
 }
 
+// The mirrored half of a flip-test input (reference lib/core/function.py:213-225, lib/utils/transforms.py:33-75).
+//
+// cond_mirror_kernel: the condition coordinates the mirrored crop is rendered from - fliplr_joints on the crop
+// coordinates (x' = (W - x) - 1 with both differences rounded on their own, rows and visibilities taken from the partner,
+// joints times their visibility), then the renderer's np.array(kpts).astype(int) as floats, the (float)trunc() of
+// cond_geometry_kernel and refine_step_kernel.  One thread per (sample, joint).  It reads the coordinates BEFORE any
+// truncation: trunc(W - 1 - x) is not W - 1 - trunc(x) for a non-integer x.
+struct CondMirrorParams {
+  const double* joints;          // [B][K][js], js = 2 or 3
+  const double* vis;             // [B][K][3], NULL: all ones
+  const int* pair;               // [K], -1 = no partner
+  int B, K, js, width;
+  float* out;                    // [B][K][2]
+};
+
+__global__ __launch_bounds__(256) void cond_mirror_kernel(CondMirrorParams p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.B * p.K) return;
+  const int b = i / p.K, j = i - b * p.K;
+  int src = j;
+  const int q = p.pair[j];
+  if (q >= 0 && q < p.K) src = q;
+  const long s = (long)b * p.K + src;
+  double x = __dsub_rn(__dsub_rn((double)p.width, p.joints[s * p.js]), 1.0);
+  double y = p.joints[s * p.js + 1];
+  if (p.vis) {
+    x = __dmul_rn(x, p.vis[s * 3]);
+    y = __dmul_rn(y, p.vis[s * 3 + 1]);
+  }
+  p.out[(long)i * 2] = (float)trunc(x);
+  p.out[(long)i * 2 + 1] = (float)trunc(y);
+}
+
+extern "C" int buctd_cond_mirror(const double* cond_joints, int joint_stride, const double* cond_vis,
+                                 const int* pair_device, int B, int K, int width, float* out, void* stream) {
+  BUCTD_CHECK_ARG(cond_joints && pair_device && out && (joint_stride == 2 || joint_stride == 3) && B > 0 && K > 0 &&
+                      K <= 32 && B < (1 << 20) && width > 0,
+                  "buctd_cond_mirror: bad argument (K <= 32, joint_stride 2 or 3)");
+  CondMirrorParams p;
+  p.joints = cond_joints; p.vis = cond_vis; p.pair = pair_device; p.B = B; p.K = K; p.js = joint_stride; p.width = width;
+  p.out = out;
+  hipLaunchKernelGGL(cond_mirror_kernel, dim3(ceil_div((long)B * K, 256)), dim3(256), 0, (hipStream_t)stream, p);
+  BUCTD_CHECK_LAUNCH("buctd_cond_mirror");
+  return BUCTD_OK;
+}
+
+// mirror_rows_kernel: out[b][c0 + c][y][x] = in[b][c0 + perm[c]][y][W - 1 - x].  Grid: x over a row, y over the C * H
+// rows of a sample (4 per block, one wavefront each), z = sample - one 32-bit division per thread, none per pixel.  A
+// thread owns V consecutive output pixels and reads the V source pixels that mirror them as one load: consecutive lanes
+// write ascending addresses and read descending ones, so a wavefront still touches one dense 64 * V * 4-byte segment of a
+// source row.  V = 4 (16-byte loads and stores) where W, both batch strides and both pointers allow it, else V = 1: any W.
+struct MirrorRowsParams {
+  const float* in;
+  float* out;
+  const int* perm;               // [C], NULL: identity; an entry outside [0, C) keeps its channel
+  long in_bs, out_bs;            // batch strides in floats
+  int c0, C, H, W;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void mirror_rows_kernel(MirrorRowsParams p) {
+  const int wv = p.W / V, rows = p.C * p.H;
+  const float* in = p.in + (long)blockIdx.z * p.in_bs;
+  float* out = p.out + (long)blockIdx.z * p.out_bs;
+  for (int row = blockIdx.y * 4 + threadIdx.y; row < rows; row += gridDim.y * 4) {
+    const int c = row / p.H, y = row - c * p.H;
+    int cs = c;
+    if (p.perm) {
+      const int q = p.perm[c];
+      if (q >= 0 && q < p.C) cs = q;
+    }
+    const float* s = in + ((long)(p.c0 + cs) * p.H + y) * p.W;
+    float* d = out + ((long)(p.c0 + c) * p.H + y) * p.W;
+    for (int xv = blockIdx.x * 64 + threadIdx.x; xv < wv; xv += gridDim.x * 64) {
+      const int x = xv * V;                       // source pixels [W - V - x, W - x): inside the row for x <= W - V
+      if (V == 4) {
+        const float4 v = *reinterpret_cast<const float4*>(s + (p.W - 4 - x));
+        *reinterpret_cast<float4*>(d + x) = make_float4(v.w, v.z, v.y, v.x);
+      } else {
+        d[x] = s[p.W - 1 - x];
+      }
+    }
+  }
+}
+
+extern "C" int buctd_mirror_rows(const float* in, long in_batch_stride, float* out, long out_batch_stride,
+                                 const int32_t* perm, int B, int channel0, int channels, int H, int W, void* stream) {
+  BUCTD_CHECK_ARG(in && out && B > 0 && B <= 65535 && channel0 >= 0 && channels > 0 && H > 0 && W > 0 &&
+                      (long)(channel0 + channels) * H < (1L << 31),
+                  "buctd_mirror_rows: bad argument (B <= 65535)");
+  const long image = (long)(channel0 + channels) * H * W;
+  BUCTD_CHECK_ARG(in_batch_stride >= image && out_batch_stride >= image,
+                  "buctd_mirror_rows: batch stride smaller than the channels [0, channel0 + channels)");
+  // what is read and what is written may be two row ranges of one tensor, never the same floats
+  const float* in_end = in + (B - 1) * in_batch_stride + image;
+  const float* out_end = out + (B - 1) * out_batch_stride + image;
+  BUCTD_CHECK_ARG(in_end <= out || out_end <= in, "buctd_mirror_rows: source and destination overlap");
+  MirrorRowsParams p;
+  p.in = in; p.out = out; p.perm = perm; p.in_bs = in_batch_stride; p.out_bs = out_batch_stride;
+  p.c0 = channel0; p.C = channels; p.H = H; p.W = W;
+  const bool wide = W % 4 == 0 && in_batch_stride % 4 == 0 && out_batch_stride % 4 == 0 &&
+                    ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
+  const long rows = (long)channels * H;
+  dim3 grid((unsigned)min((long)ceil_div(wide ? W / 4 : W, 64), 64L), (unsigned)min((rows + 3) / 4, 65535L), (unsigned)B);
+  if (wide) hipLaunchKernelGGL(mirror_rows_kernel<4>, grid, dim3(64, 4), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(mirror_rows_kernel<1>, grid, dim3(64, 4), 0, (hipStream_t)stream, p);
+  BUCTD_CHECK_LAUNCH("buctd_mirror_rows");
+  return BUCTD_OK;
+}
+
 // One pass boundary of the iterative refinement (dataset/pipeline.py IterativeRefiner; reference dataloader.py:454-508,
 // 596-612): what get_final_preds, rescore, next_records and geometry() do per person on the host between the decode of
 // one pass and the crop of the next.  One wavefront per person, lanes over joints (K <= 32); the box and the score are

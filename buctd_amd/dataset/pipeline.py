@@ -28,7 +28,8 @@ import torch
 from .. import ops
 from .._C import RefineArgs, SampleGeomArgs, check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
-from ..utils.transforms import _swap_table, affine_transform, fliplr_joints, get_affine_transform
+from ..utils.transforms import (_swap_table, affine_transform, flip_hm, flip_merge_device, flip_perm, fliplr_joints,
+                                get_affine_transform, mirror_condition)
 from .pose_synthesis import synthesize_pose_batch
 
 _M64 = (1 << 64) - 1
@@ -236,6 +237,7 @@ class DeviceSamplePipeline:
         self.seed = int(seed)
         self.synth_calls = 0
         self._pair_dev = {}
+        self._perm_dev, self._colors_dev = {}, {}                          # the flip test's tables, uploaded once
         self.joints_weight = None
         if joints_weight is not None and bool(getattr(getattr(cfg, "LOSS", None), "USE_DIFFERENT_JOINTS_WEIGHT", False)):
             jw = np.asarray(joints_weight, dtype=np.float32)
@@ -409,6 +411,14 @@ class DeviceSamplePipeline:
             self._pair_dev[dev] = pair
         return pair
 
+    def flip_perm(self, dev):
+        """int32 [K] on the device: the channel permutation of ops.flipback_avg (utils.transforms.flip_perm, uploaded
+        once)."""
+        perm = self._perm_dev.get(dev)
+        if perm is None:
+            perm = self._perm_dev[dev] = flip_perm(self.num_joints, self.flip_pairs, dev)
+        return perm
+
     def cond_geometry(self, synth, cond_vis, table):
         """Flip + crop affine of device-resident condition poses (buctd_cond_geometry).  synth, cond_vis: float64 device
         tensors [B, K, 3]; table: warp_table().  Returns cond_joints, cond_joints_vis (float64) and the truncated
@@ -498,21 +508,97 @@ class DeviceSamplePipeline:
                                                    C.c_void_p(x[:, 3 + c:].data_ptr()), x.stride(0), ptr(ws),
                                                    ws.numel(), stream_ptr()), "cond_render_into")
 
-    def warp_and_condition(self, table, cond_trunc, colors=None):
+    def cond_mirror(self, cond_joints, cond_vis=None, out=None):
+        """The mirrored, truncated condition coordinates of a batch (buctd_cond_mirror; utils.transforms.mirror_condition
+        on the host).  cond_joints: float64 device tensor [B, K, 2 or 3], crop coordinates before any truncation;
+        cond_vis: float64 [B, K, 3] or None for all ones.  Returns float32 [B, K, 2] (out, if given)."""
+        B, K, js = (int(v) for v in cond_joints.shape)
+        dev = cond_joints.device
+        if cond_joints.dtype != torch.float64 or js not in (2, 3) or not cond_joints.is_contiguous():
+            raise ValueError("cond_mirror: cond_joints must be a contiguous float64 [B, K, 2 or 3] tensor")
+        if cond_vis is not None and (cond_vis.dtype != torch.float64 or tuple(cond_vis.shape) != (B, K, 3)
+                                     or not cond_vis.is_contiguous() or cond_vis.device != dev):
+            raise ValueError("cond_mirror: cond_vis must be a contiguous float64 [B, K, 3] tensor on cond_joints' device")
+        if K != self.num_joints:
+            raise ValueError(f"cond_mirror: cond_joints has {K} joints, MODEL.NUM_JOINTS is {self.num_joints}")
+        if out is None:
+            out = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, K, 2) or not out.is_contiguous() or out.device != dev:
+            raise ValueError("cond_mirror: out must be a contiguous float32 [B, K, 2] tensor on cond_joints' device")
+        check(lib().buctd_cond_mirror(ptr(cond_joints), js, ptr(cond_vis), ptr(self.pair_table(dev)), B, K,
+                                      int(self.image_size[0]), ptr(out), stream_ptr()), "cond_mirror")
+        return out
+
+    @staticmethod
+    def mirror_rows(src, dst, channel0, count, perm=None):
+        """dst[b, channel0 + c, y, x] = src[b, channel0 + perm[c], y, W - 1 - x] for c in [0, count) (buctd_mirror_rows).
+        src, dst: float32 NCHW device tensors (or batch slices of one tensor, not overlapping) with dense images; perm:
+        int32 [count] on the device, an entry outside [0, count) - the -1 of pair_table() - keeps its channel; None:
+        identity."""
+        B, _, H, W = (int(v) for v in src.shape)
+        for t in (src, dst):
+            if t.dtype != torch.float32 or t.dim() != 4 or t.stride()[1:] != (H * W, W, 1):
+                raise ValueError("mirror_rows: float32 NCHW tensors with dense channels")
+        if tuple(dst.shape[2:]) != (H, W) or int(dst.shape[0]) != B or channel0 < 0 or count < 1 or \
+                channel0 + count > min(int(src.shape[1]), int(dst.shape[1])):
+            raise ValueError("mirror_rows: src and dst differ in shape, or the channel range leaves them")
+        if perm is not None and (perm.dtype != torch.int32 or tuple(perm.shape) != (count,) or not perm.is_contiguous()
+                                 or perm.device != src.device):
+            raise ValueError("mirror_rows: perm must be a contiguous int32 [count] tensor on src's device")
+        if dst.device != src.device or not src.is_cuda:
+            raise ValueError("mirror_rows: src and dst must be on one ROCm device")
+        check(lib().buctd_mirror_rows(C.c_void_p(src.data_ptr()), src.stride(0), C.c_void_p(dst.data_ptr()), dst.stride(0),
+                                      ptr(perm), B, int(channel0), int(count), H, W, stream_ptr()), "mirror_rows")
+        return dst
+
+    def mirror_colors(self, dev):
+        """The colour table the mirrored half of a 3-channel condition is rendered with (transforms.flip_hm renders it
+        colored for a mono condition as well): uploaded once per device."""
+        colors = self._colors_dev.get(dev)
+        if colors is None:
+            if self.kpt_colors is None:
+                raise ValueError("the flip test re-renders a 3-channel condition colored: the pipeline needs kpt_colors")
+            colors = torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:self.num_joints])).to(dev)
+            self._colors_dev[dev] = colors
+        return colors
+
+    def warp_and_condition(self, table, cond_trunc, colors=None, mirrored=None):
         """Network input [B, 3 + Cc, H, W] from a device-resident warp_table() and truncated condition coordinates
         (float32 [B, K, 2], device): render() without the Gaussian targets and without any host array - the two kernels an
-        inference pass needs.  Nothing is uploaded when colors (condition_colors()) is handed in."""
+        inference pass needs.  Nothing is uploaded when colors (condition_colors()) is handed in.
+
+        mirrored = (cond_joints, cond_joints_vis or None): the paired input of the flip test, [2B, 3 + Cc, H, W].  Rows
+        [0, B) are the input above, written by the same launches; rows [B, 2B) are what core.function._mirrored_input makes
+        of them: the image channels mirrored (buctd_mirror_rows), a stacked condition mirrored with partner channels
+        exchanged, a 3-channel condition - colored or mono - rendered colored from the mirrored coordinates
+        (buctd_cond_mirror of cond_joints: float64 [B, K, 2 or 3], the crop coordinates before trunc())."""
         if not self.conditional:
             raise ValueError("warp_and_condition renders a condition: MODEL.CONDITIONAL_TOPDOWN is off")
         dev = table.device
         B, K = int(cond_trunc.shape[0]), self.num_joints
         W, H = int(self.image_size[0]), int(self.image_size[1])
-        x = torch.empty((B, 3 + (K if self.stacked else 3), H, W), dtype=torch.float32, device=dev)
+        rows = B if mirrored is None else 2 * B
+        if mirrored is not None and (mirrored[0].dim() != 3 or int(mirrored[0].shape[0]) != B or mirrored[0].device != dev):
+            raise ValueError("warp_and_condition: mirrored[0] must be [B, K, 2 or 3] with the B of cond_trunc, on its device")
+        x = torch.empty((rows, 3 + (K if self.stacked else 3), H, W), dtype=torch.float32, device=dev)
         mean = (C.c_float * 3)(*self.mean.tolist())
         std = (C.c_float * 3)(*self.std.tolist())
         check(lib().buctd_warp_affine_norm(ptr(table), B, H, W, mean, std, ptr(x), x.stride(0), None, stream_ptr()),
               "warp_affine_norm")
-        self.render_condition(x, cond_trunc, colors)
+        if mirrored is None:
+            self.render_condition(x, cond_trunc, colors)
+            return x
+        first, second = x[:B], x[B:]
+        self.render_condition(first, cond_trunc, colors)
+        self.mirror_rows(first, second, 0, 3)
+        if self.stacked:
+            self.mirror_rows(first, second, 3, K, self.pair_table(dev))
+        else:
+            cjm = self.cond_mirror(mirrored[0], mirrored[1])
+            ws = ops.workspace(lib().buctd_cond_render_workspace(B, 3, H, W), dev)
+            check(lib().buctd_cond_render_into(ptr(cjm), 2, ptr(self.mirror_colors(dev)), B, K, 3, H, W, 0,
+                                               C.c_void_p(second[:, 3:].data_ptr()), x.stride(0), ptr(ws), ws.numel(),
+                                               stream_ptr()), "cond_render_into")
         return x
 
     # ---- scalar geometry on the device (geometry_on_device=True) ------------------------------------------------
@@ -729,15 +815,27 @@ class IterativeRefiner:
     conditions of all passes stay on the device (buctd_refine_step between the decode kernel of one pass and the crop of
     the next) and run() waits for the device once, after the last pass.  Same return value; a person whose predictions
     have no non-zero x or y raises the host path's ValueError, after the last pass instead of in the middle.  Needs an
-    eval pipeline (no augmentation draws), a conditional config and NUM_JOINTS <= 32."""
+    eval pipeline (no augmentation draws), a conditional config and NUM_JOINTS <= 32.
+
+    flip_test=True: every pass is the flip test of validate() (reference function.py:213-236, which each of the three CLI
+    runs goes through with TEST.FLIP_TEST True): one forward over [crops | mirrored crops], the two heat-maps merged with
+    flip_merge_device, then decoded.  shift_heatmap: the one-pixel shift of the mirrored half in that merge; None takes
+    cfg.TEST.SHIFT_HEATMAP.  The keyword is explicit and off by default - cfg.TEST.FLIP_TEST is NOT read, callers of
+    earlier versions keep their results bit for bit; flip_test=cfg.TEST.FLIP_TEST is the setting that equals the
+    reference chain.  On the device chain the mirrored half is built on the device as well (buctd_mirror_rows,
+    buctd_cond_mirror): still one upload before the loop and one copy back after it, and the model - ForwardGraph and
+    Bf16Inference included - sees 2B rows."""
 
     MAX_DEVICE_JOINTS = 32     # buctd_refine_step: one lane per joint, as buctd_cond_geometry
 
-    def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False, on_device=False):
+    def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False, on_device=False, flip_test=False,
+                 shift_heatmap=None):
         self.cfg, self.model, self.pipe = cfg, model, pipeline
         self.use_dark = bool(use_dark)
         self.in_vis_thre = cfg.TEST.IN_VIS_THRE if in_vis_thre is None else in_vis_thre
         self.on_device = bool(on_device)
+        self.flip_test = bool(flip_test)
+        self.shift_heatmap = bool(getattr(cfg.TEST, "SHIFT_HEATMAP", False) if shift_heatmap is None else shift_heatmap)
         if self.on_device:
             if pipeline.is_train:
                 raise ValueError("IterativeRefiner(on_device=True) needs a pipeline built with is_train=False: the "
@@ -776,6 +874,25 @@ class IterativeRefiner:
             out.append(nr)
         return out
 
+    def mirrored_input(self, x, geos):
+        """core.function._mirrored_input for the host chain: the pipeline stands in for the data set (image_size,
+        flip_pairs, kpt_colors), the geometry's cond_joints / cond_joints_vis for the batch's meta.  A 3-channel condition
+        is rendered from utils.transforms.mirror_condition, which truncates the mirrored coordinates in float64 like the
+        reference's .astype(int); transforms.flip_hm rounds them to float32 first, and from the second pass on a person
+        whose box has stopped moving has crop coordinates an ulp from an integer (24.999999999999996 is 24 there, 25 in
+        float32 - DESIGN.md section 12).  A stacked condition goes through flip_hm: no coordinates."""
+        pipe = self.pipe
+        if not pipe.conditional:
+            return x.flip(3)
+        cj = np.stack([g["cond_joints"] for g in geos])
+        cv = np.stack([g["cond_joints_vis"] for g in geos])
+        if pipe.stacked:
+            cond = flip_hm(x[:, 3:], pipe, torch.from_numpy(cj), torch.from_numpy(cv))
+        else:
+            pts = torch.from_numpy(mirror_condition(cj, cv, int(pipe.image_size[0]), pipe.flip_pairs)).to(x.device)
+            cond = ops.cond_render(pts, pipe.mirror_colors(x.device), int(pipe.image_size[1]), int(pipe.image_size[0]))
+        return torch.cat((x[:, :3].flip(3), cond), dim=1)
+
     @torch.no_grad()
     def run(self, records, passes=3):
         """Returns per pass: dict(preds [B, K, 3] image coordinates + max-val, score, box_score, keypoint_score)."""
@@ -786,8 +903,15 @@ class IterativeRefiner:
         for _ in range(passes):
             geos = [self.pipe.geometry(r) for r in records]
             x, _, _ = self.pipe.render([r["image"] for r in records], geos)
-            out = self.model(x)
-            out = out[-1] if isinstance(out, list) else out
+            if self.flip_test:
+                # validate()'s paired forward: [crops | mirrored crops], merged before the decode
+                out = self.model(torch.cat((x, self.mirrored_input(x, geos)), dim=0))
+                out = out[-1] if isinstance(out, list) else out
+                n = x.shape[0]
+                out = flip_merge_device(out[:n], out[n:], self.pipe.flip_pairs, self.shift_heatmap)
+            else:
+                out = self.model(x)
+                out = out[-1] if isinstance(out, list) else out
             center = np.stack([g["center"] for g in geos])
             scale = np.stack([g["scale"] for g in geos])
             coords, maxvals = get_final_preds(self.cfg, out, center, scale, use_dark=self.use_dark)
@@ -832,14 +956,22 @@ class IterativeRefiner:
         geos = [pipe.geometry(r) for r in records]
         table = pipe.warp_table(images, geos)
         f32, f64 = np.float32, np.float64
-        at_in, n_in = self._layout([("box_score", f64, (B,)), ("center", f32, (B, 2)), ("scale", f32, (B, 2)),
-                                    ("cond_trunc", f32, (B, K, 2))])
+        flip = self.flip_test
+        sections = [("box_score", f64, (B,)), ("center", f32, (B, 2)), ("scale", f32, (B, 2)), ("cond_trunc", f32, (B, K, 2))]
+        if flip:
+            # the condition before trunc() - pass 0's from the host geometry, with its visibilities; buctd_refine_step
+            # overwrites cond_joints with the next pass's, whose visibilities are all ones
+            sections += [("cond_joints", f64, (B, K, 2)), ("cond_vis", f64, (B, K, 3))]
+        at_in, n_in = self._layout(sections)
         host = np.zeros(n_in, dtype=np.uint8)
         hv = self._views(host, at_in)
         hv["box_score"][:] = [float(r.get("score", 1)) for r in records]
         hv["center"][:] = np.stack([g["center"] for g in geos])
         hv["scale"][:] = np.stack([g["scale"] for g in geos])
         hv["cond_trunc"][:] = trunc_condition(np.stack([g["cond_joints"] for g in geos]))
+        if flip:
+            hv["cond_joints"][:] = np.stack([g["cond_joints"][:, :2] for g in geos])
+            hv["cond_vis"][:] = np.stack([g["cond_joints_vis"] for g in geos])
         sv = self._views(torch.from_numpy(host).to(dev), at_in)
         state = (sv["center"], sv["scale"], sv["box_score"], sv["cond_trunc"])
         at_out, n_out = self._layout([("score", f64, (passes, B)), ("box_score", f64, (passes, B)),
@@ -850,15 +982,23 @@ class IterativeRefiner:
         out = self._views(result, at_out)
         colors = pipe.condition_colors(dev)
         refine = bool(cfg.TEST.POST_PROCESS)
+        perm = pipe.flip_perm(dev) if flip else None
         for p in range(passes):
-            x = pipe.warp_and_condition(table, sv["cond_trunc"], colors)
+            if flip:
+                x = pipe.warp_and_condition(table, sv["cond_trunc"], colors,
+                                            mirrored=(sv["cond_joints"], sv["cond_vis"] if p == 0 else None))
+            else:
+                x = pipe.warp_and_condition(table, sv["cond_trunc"], colors)
             hm = self.model(x)
             hm = (hm[-1] if isinstance(hm, list) else hm).contiguous()
+            if flip:
+                hm = ops.flipback_avg(hm[:B], hm[B:], perm, self.shift_heatmap)
             if self.use_dark:
                 res = ops.dark_decode(hm)
             else:
                 res = ops.argmax_decode(hm, refine=refine)
-            self.refine_step((res[0], res[1], res[3] if (self.use_dark or refine) else None), state, table, out, p, passes)
+            self.refine_step((res[0], res[1], res[3] if (self.use_dark or refine) else None), state, table, out, p, passes,
+                             cond_joints=sv["cond_joints"] if flip else None)
         got = self._views(result.cpu().numpy(), at_out)
         bad = np.nonzero(got["status"])[0]
         if bad.size:

@@ -42,6 +42,20 @@ def fliplr_joints(joints, joints_vis, width, matched_parts):
     return joints * joints_vis, joints_vis
 
 
+def mirror_condition(cond_joints, cond_joints_vis, width, matched_parts):
+    """The condition coordinates of the mirrored half of a flip-test input, as the renderer takes them: fliplr_joints per
+    sample on copies (x' = (width - x) - 1 in float64, partners exchanged, joints times their visibility), then
+    np.array(kpts).astype(int) as floats (dataset.pipeline.trunc_condition).  cond_joints [B, K, >=2], cond_joints_vis
+    [B, K, 3] or None for all ones -> float32 [B, K, 2].  trunc(width - 1 - x) is not width - 1 - trunc(x) for a
+    non-integer x: this takes the untruncated crop coordinates.  The CPU statement of buctd_cond_mirror."""
+    kp = np.array(cond_joints, dtype=np.float64)
+    vis = np.ones(kp.shape[:2] + (3,)) if cond_joints_vis is None else np.array(cond_joints_vis, dtype=np.float64)
+    if kp.shape[2] == 2:
+        vis = vis[:, :, :2].copy()
+    mirrored = np.stack([fliplr_joints(kp[b], vis[b], width, matched_parts)[0] for b in range(kp.shape[0])])
+    return np.ascontiguousarray(np.trunc(mirrored[:, :, :2]).astype(np.float32))
+
+
 def flip_hm(heatmap, dataset, cond_joints, cond_joints_vis):
     """Condition flip for the flip test (reference 33-58): a 3-channel condition is re-rendered (colored) from the
     mirrored key points - on the GPU here; a stacked one is mirrored with left/right channels exchanged."""

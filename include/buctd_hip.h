@@ -721,6 +721,22 @@ int buctd_cond_render_into(const float* joints, int js, const float* colors, int
 int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd_warp_item* items_device,
                         const int* pair_device, int B, int K, double* out_joints, double* out_vis, float* out_trunc,
                         void* stream);
+/* The mirrored half of a flip-test input (reference lib/core/function.py:213-225), built on the device.
+ * buctd_cond_mirror: the condition coordinates the mirrored crop is rendered from.  Per (sample, joint): fliplr_joints
+ * (lib/utils/transforms.py:61-75) on crop coordinates - x' = (width - x) - 1 in float64, never fused; row and visibility
+ * taken from pair[j] (-1: no partner); x' and y times the visibility's columns 0 and 1 (an invisible joint becomes
+ * (0, 0)) - then trunc() toward zero and the conversion to float32 that buctd_cond_geometry and buctd_refine_step apply.
+ * cond_joints float64 [B][K][joint_stride], joint_stride 2 (buctd_refine_args.cond_joints) or 3 - the coordinates BEFORE
+ * truncation: trunc(width - 1 - x) is not width - 1 - trunc(x).  cond_vis float64 [B][K][3] or NULL = all ones.
+ * out float32 [B][K][2], the `joints` argument of buctd_cond_render_into with js = 2.  K <= 32.
+ * buctd_mirror_rows: out[b][channel0 + c][y][x] = in[b][channel0 + perm[c]][y][W - 1 - x] for c in [0, channels) over
+ * float32 NCHW with dense images and batch strides in floats.  perm int32 [channels] on the device, an entry outside
+ * [0, channels) keeps its channel (so the pair table with its -1 serves); NULL = identity.  in and out may be row ranges
+ * of one tensor (rows [B, 2B) from rows [0, B)) but must not overlap.  Any W. */
+int buctd_cond_mirror(const double* cond_joints, int joint_stride, const double* cond_vis, const int* pair_device, int B,
+                      int K, int width, float* out, void* stream);
+int buctd_mirror_rows(const float* in, long in_batch_stride, float* out, long out_batch_stride, const int32_t* perm,
+                      int B, int channel0, int channels, int H, int W, void* stream);
 /* One pass boundary of the iterative refinement (dataset.pipeline.IterativeRefiner; reference: three tools/test.py runs
  * chained through the results json, lib/dataset/dataloader.py:454-508 and 596-612): from the decode outputs of pass
  * `pass` to the crop affine and the condition of pass `pass` + 1 without leaving the device.  Per person, in the host's

@@ -88,12 +88,49 @@ extern "C" int buctd_warp_affine_norm(const buctd_warp_item* items_device, int B
   return BUCTD_OK;
 }
 
+// np.array(kpts).astype(int) of JointsDataset.py:521 as float32: a [., 2] row of the render kernel's `joints`
+__device__ __forceinline__ void store_trunc(float* dst, double x, double y) {
+  dst[0] = (float)trunc(x);
+  dst[1] = (float)trunc(y);
+}
+
+// fliplr_joints (utils/transforms.py:61-75) + the crop affine for joint j of one [K][js] pose, js = 2 or 3 (without a
+// third column z is 0), the one statement of both on the device.  flip: x = (W - x) - 1, row and visibility taken from
+// the partner, joints * joints_vis (so a "missed" joint (0, 0) comes back as (W - 1, 0) times its visibility, like in the
+// reference); then through m (NULL: no affine) where vis[., 0] > 0.  vis NULL: all ones - the products with 1.0 stay,
+// which is bit-identical to not multiplying for every value that is not a NaN.  Every float64 product and sum is rounded
+// on its own (__dmul_rn / __dadd_rn / __dsub_rn: never contracted into an fma).
+struct GeomPoint { double x, y, z, v0, v1, v2; };
+__device__ __forceinline__ GeomPoint geom_point(const double* pose, int js, const double* vis, int j, int K, bool flip,
+                                                const int* pair, double W, const double* m) {
+  int src = j;
+  if (flip) {
+    const int q = pair[j];
+    if (q >= 0 && q < K) src = q;
+  }
+  GeomPoint g = {pose[src * js], pose[src * js + 1], js > 2 ? pose[src * js + 2] : 0.0, 1.0, 1.0, 1.0};
+  if (vis) { g.v0 = vis[src * 3]; g.v1 = vis[src * 3 + 1]; g.v2 = vis[src * 3 + 2]; }
+  if (flip) {
+    g.x = __dmul_rn(__dsub_rn(__dsub_rn(W, g.x), 1.0), g.v0);
+    g.y = __dmul_rn(g.y, g.v1);
+    g.z = __dmul_rn(g.z, g.v2);
+  }
+  if (m && g.v0 > 0.0) {
+    const double tx = __dadd_rn(__dadd_rn(__dmul_rn(m[0], g.x), __dmul_rn(m[1], g.y)), m[2]);
+    const double ty = __dadd_rn(__dadd_rn(__dmul_rn(m[3], g.x), __dmul_rn(m[4], g.y)), m[5]);
+    g.x = tx;
+    g.y = ty;
+  }
+  return g;
+}
+__device__ __forceinline__ void store_point(double* joints, double* vis, const GeomPoint& g) {
+  joints[0] = g.x; joints[1] = g.y; joints[2] = g.z;
+  vis[0] = g.v0; vis[1] = g.v1; vis[2] = g.v2;
+}
+
 // Condition key points of a generative-sampling train batch (JointsDataset.py:257-259, 293-295): what
 // DeviceSamplePipeline.geometry does to cond_joints on the host, for poses that buctd_synthesize_pose left on the
-// device.  One thread per (sample, joint).  flip: fliplr_joints (utils/transforms.py:61-75) - x = W - x - 1, the
-// left/right exchange of joints and visibilities, joints * joints_vis (so a "missed" joint (0, 0) comes back as
-// (W - 1, 0) times its visibility, like in the reference); then the crop affine where vis[., 0] > 0.  Every float64
-// product and sum is rounded on its own (__dmul_rn / __dadd_rn / __dsub_rn: never contracted into an fma).
+// device.  One thread per (sample, joint): geom_point with the sample's flip and crop affine.
 struct CondGeomParams {
   const double* synth;           // [B][K][3]
   const double* vis;             // [B][K][3]
@@ -110,34 +147,10 @@ __global__ __launch_bounds__(256) void cond_geometry_kernel(CondGeomParams p) {
   if (i >= p.B * p.K) return;
   const int b = i / p.K, j = i - b * p.K;
   const buctd_warp_item* it = p.items + b;
-  const int flip = it->flip;
-  int src = j;
-  if (flip) {
-    const int q = p.pair[j];
-    if (q >= 0 && q < p.K) src = q;
-  }
-  const double* s = p.synth + ((long)b * p.K + src) * 3;
-  const double* v = p.vis + ((long)b * p.K + src) * 3;
-  double x = s[0], y = s[1], z = s[2];
-  const double v0 = v[0], v1 = v[1], v2 = v[2];
-  if (flip) {
-    x = __dsub_rn(__dsub_rn((double)it->W, x), 1.0);
-    x = __dmul_rn(x, v0);
-    y = __dmul_rn(y, v1);
-    z = __dmul_rn(z, v2);
-  }
-  if (v0 > 0.0) {
-    const double tx = __dadd_rn(__dadd_rn(__dmul_rn(it->m[0], x), __dmul_rn(it->m[1], y)), it->m[2]);
-    const double ty = __dadd_rn(__dadd_rn(__dmul_rn(it->m[3], x), __dmul_rn(it->m[4], y)), it->m[5]);
-    x = tx;
-    y = ty;
-  }
-  double* oj = p.out_joints + (long)i * 3;
-  double* ov = p.out_vis + (long)i * 3;
-  oj[0] = x; oj[1] = y; oj[2] = z;
-  ov[0] = v0; ov[1] = v1; ov[2] = v2;
-  p.out_trunc[(long)i * 2] = (float)trunc(x);        // np.array(kpts).astype(int) of JointsDataset.py:521, as float32
-  p.out_trunc[(long)i * 2 + 1] = (float)trunc(y);
+  const long pose = (long)b * p.K * 3;
+  const GeomPoint g = geom_point(p.synth + pose, 3, p.vis + pose, j, p.K, it->flip != 0, p.pair, (double)it->W, it->m);
+  store_point(p.out_joints + (long)i * 3, p.out_vis + (long)i * 3, g);
+  store_trunc(p.out_trunc + (long)i * 2, g.x, g.y);
 }
 
 extern "C" int buctd_cond_geometry(const double* synth, const double* cond_vis, const buctd_warp_item* items_device,
@@ -156,11 +169,9 @@ extern "C" int buctd_cond_geometry(const double* synth, const double* cond_vis, 
 
 // The mirrored half of a flip-test input (reference lib/core/function.py:213-225, lib/utils/transforms.py:33-75).
 //
-// cond_mirror_kernel: the condition coordinates the mirrored crop is rendered from - fliplr_joints on the crop
-// coordinates (x' = (W - x) - 1 with both differences rounded on their own, rows and visibilities taken from the partner,
-// joints times their visibility), then the renderer's np.array(kpts).astype(int) as floats, the (float)trunc() of
-// cond_geometry_kernel and refine_step_kernel.  One thread per (sample, joint).  It reads the coordinates BEFORE any
-// truncation: trunc(W - 1 - x) is not W - 1 - trunc(x) for a non-integer x.
+// cond_mirror_kernel: the condition coordinates the mirrored crop is rendered from - geom_point on the crop coordinates
+// with the flip always on and no affine, then store_trunc.  One thread per (sample, joint).  It reads the coordinates
+// BEFORE any truncation: trunc(W - 1 - x) is not W - 1 - trunc(x) for a non-integer x.
 struct CondMirrorParams {
   const double* joints;          // [B][K][js], js = 2 or 3
   const double* vis;             // [B][K][3], NULL: all ones
@@ -173,18 +184,9 @@ __global__ __launch_bounds__(256) void cond_mirror_kernel(CondMirrorParams p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.B * p.K) return;
   const int b = i / p.K, j = i - b * p.K;
-  int src = j;
-  const int q = p.pair[j];
-  if (q >= 0 && q < p.K) src = q;
-  const long s = (long)b * p.K + src;
-  double x = __dsub_rn(__dsub_rn((double)p.width, p.joints[s * p.js]), 1.0);
-  double y = p.joints[s * p.js + 1];
-  if (p.vis) {
-    x = __dmul_rn(x, p.vis[s * 3]);
-    y = __dmul_rn(y, p.vis[s * 3 + 1]);
-  }
-  p.out[(long)i * 2] = (float)trunc(x);
-  p.out[(long)i * 2 + 1] = (float)trunc(y);
+  const GeomPoint g = geom_point(p.joints + (long)b * p.K * p.js, p.js, p.vis ? p.vis + (long)b * p.K * 3 : nullptr, j, p.K,
+                                 true, p.pair, (double)p.width, nullptr);
+  store_trunc(p.out + (long)i * 2, g.x, g.y);
 }
 
 extern "C" int buctd_cond_mirror(const double* cond_joints, int joint_stride, const double* cond_vis,
@@ -267,7 +269,7 @@ extern "C" int buctd_mirror_rows(const float* in, long in_batch_stride, float* o
 // One pass boundary of the iterative refinement (dataset/pipeline.py IterativeRefiner; reference dataloader.py:454-508,
 // 596-612): what get_final_preds, rescore, next_records and geometry() do per person on the host between the decode of
 // one pass and the crop of the next.  One wavefront per person, lanes over joints (K <= 32); the box and the score are
-// butterfly reductions in float64.  Every float64 product and sum is rounded on its own, like in cond_geometry_kernel.
+// butterfly reductions in float64.  Every float64 product and sum is rounded on its own, like in geom_point.
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o, 64));
@@ -282,6 +284,46 @@ __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// dataset/pipeline.py box_from_keypoints for the wavefront's person: (x, y) is the lane's joint, on whether the lane holds
+// one.  The non-zero x and the non-zero y each on their own, -+ margin, clipped to the image.  empty: no non-zero x or no
+// non-zero y (the host's min() of an empty array raises); the box means nothing then.
+struct KeypointBox {
+  bool empty;
+  double x0, y0, w, h;
+};
+__device__ __forceinline__ KeypointBox keypoint_box(double x, double y, bool on, double margin, double W, double H) {
+  const bool nx = on && x != 0.0, ny = on && y != 0.0;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  const double xlo = wave_min_f64(nx ? x : inf), xhi = wave_max_f64(nx ? x : -inf);
+  const double ylo = wave_min_f64(ny ? y : inf), yhi = wave_max_f64(ny ? y : -inf);
+  KeypointBox r;
+  r.empty = __ballot(nx) == 0 || __ballot(ny) == 0;
+  r.x0 = fmin(fmax(__dsub_rn(xlo, margin), 0.0), W);
+  r.y0 = fmin(fmax(__dsub_rn(ylo, margin), 0.0), H);
+  r.w = __dsub_rn(fmin(fmax(__dadd_rn(xhi, margin), 0.0), W), r.x0);
+  r.h = __dsub_rn(fmin(fmax(__dadd_rn(yhi, margin), 0.0), H), r.y0);
+  return r;
+}
+
+// dataset/pipeline.py xywh2cs: float32 centre and scale of a box with the network's aspect ratio
+struct CenterScale { float cx, cy, s0, s1; };
+__device__ __forceinline__ CenterScale xywh2cs(const KeypointBox& box, double aspect_ratio, double scale_thre) {
+  double w = box.w, h = box.h;
+  CenterScale r;
+  r.cx = (float)__dadd_rn(box.x0, __dmul_rn(w, 0.5));
+  r.cy = (float)__dadd_rn(box.y0, __dmul_rn(h, 0.5));
+  const double ah = __dmul_rn(aspect_ratio, h);
+  if (w > ah) h = __ddiv_rn(w, aspect_ratio);
+  else if (w < ah) w = __dmul_rn(h, aspect_ratio);
+  r.s0 = (float)__ddiv_rn(w, 200.0);
+  r.s1 = (float)__ddiv_rn(h, 200.0);
+  if (r.cx != -1.f) {
+    r.s0 = __fmul_rn(r.s0, (float)scale_thre);
+    r.s1 = __fmul_rn(r.s1, (float)scale_thre);
+  }
+  return r;
 }
 
 // utils/transforms.py crop_affine_closed_form, line by line: x' = sx * x + tx, y' = sy * y + ty.
@@ -341,29 +383,12 @@ __global__ __launch_bounds__(256) void refine_step_kernel(buctd_refine_args p) {
   const double sum = wave_sum_f64(counted ? (double)mv : 0.0);
   const double kpt_score = n > 0 ? sum / (double)n : 0.0;
   const double score = __dmul_rn(kpt_score, box_score);
-  // box_from_keypoints: the non-zero x and the non-zero y, each on its own
-  const bool nx = on && px != 0.f, ny = on && py != 0.f;
-  const bool empty = __ballot(nx) == 0 || __ballot(ny) == 0;
-  const double inf = __longlong_as_double(0x7ff0000000000000LL);
-  const double xlo = wave_min_f64(nx ? (double)px : inf), xhi = wave_max_f64(nx ? (double)px : -inf);
-  const double ylo = wave_min_f64(ny ? (double)py : inf), yhi = wave_max_f64(ny ? (double)py : -inf);
+  // the box around the predictions and the next pass's centre and scale
   const buctd_warp_item* it = p.items + b;
-  const double W = (double)it->W, H = (double)it->H;
-  const double x0 = fmin(fmax(__dsub_rn(xlo, p.margin), 0.0), W), x1 = fmin(fmax(__dadd_rn(xhi, p.margin), 0.0), W);
-  const double y0 = fmin(fmax(__dsub_rn(ylo, p.margin), 0.0), H), y1 = fmin(fmax(__dadd_rn(yhi, p.margin), 0.0), H);
-  double w = __dsub_rn(x1, x0), h = __dsub_rn(y1, y0);
-  // xywh2cs
-  const float ncx = (float)__dadd_rn(x0, __dmul_rn(w, 0.5)), ncy = (float)__dadd_rn(y0, __dmul_rn(h, 0.5));
-  const double ah = __dmul_rn(p.aspect_ratio, h);
-  if (w > ah) h = w / p.aspect_ratio;
-  else if (w < ah) w = __dmul_rn(h, p.aspect_ratio);
-  float ns0 = (float)(w / 200.0), ns1 = (float)(h / 200.0);
-  if (ncx != -1.f) {
-    ns0 = ns0 * (float)p.scale_thre;
-    ns1 = ns1 * (float)p.scale_thre;
-  }
-  const CropAffine fwd = crop_affine(ncx, ncy, ns0, p.crop_w, p.crop_h, false);
-  const int bad = (empty ? 1 : 0) | (!empty && !fwd.ok ? 2 : 0);
+  const KeypointBox box = keypoint_box((double)px, (double)py, on, p.margin, (double)it->W, (double)it->H);
+  const CenterScale next = xywh2cs(box, p.aspect_ratio, p.scale_thre);
+  const CropAffine fwd = crop_affine(next.cx, next.cy, next.s0, p.crop_w, p.crop_h, false);
+  const int bad = (box.empty ? 1 : 0) | (!box.empty && !fwd.ok ? 2 : 0);
   if (j == 0) {
     p.hist_score[row] = score;
     p.hist_box_score[row] = box_score;
@@ -375,8 +400,8 @@ __global__ __launch_bounds__(256) void refine_step_kernel(buctd_refine_args p) {
   }
   if (bad) return;
   if (j == 0) {
-    p.center[2 * b] = ncx; p.center[2 * b + 1] = ncy;
-    p.scale[2 * b] = ns0; p.scale[2 * b + 1] = ns1;
+    p.center[2 * b] = next.cx; p.center[2 * b + 1] = next.cy;
+    p.scale[2 * b] = next.s0; p.scale[2 * b + 1] = next.s1;
     double* m = p.items[b].m;
     m[0] = fwd.sx; m[1] = 0.0; m[2] = fwd.tx;
     m[3] = 0.0; m[4] = fwd.sy; m[5] = fwd.ty;
@@ -389,8 +414,7 @@ __global__ __launch_bounds__(256) void refine_step_kernel(buctd_refine_args p) {
       p.cond_joints[2 * i] = qx;
       p.cond_joints[2 * i + 1] = qy;
     }
-    p.cond_trunc[2 * i] = (float)trunc(qx);
-    p.cond_trunc[2 * i + 1] = (float)trunc(qy);
+    store_trunc(p.cond_trunc + 2 * i, qx, qy);
   }
 }
 
@@ -496,32 +520,6 @@ __device__ __forceinline__ int trunc_int(double v) {       // astype(int), kept 
   return (int)fmin(fmax(trunc(v), -1.0e9), 1.0e9);
 }
 
-struct GeomPoint { double x, y, z, v0, v1, v2; };
-// fliplr_joints + the crop affine for lane j of one [K][3] pose
-__device__ __forceinline__ GeomPoint geom_point(const double* pose, const double* vis, int j, int K, bool flip,
-                                                const int* pair, double W, const double* m, bool through) {
-  int src = j;
-  if (flip) {
-    const int q = pair[j];
-    if (q >= 0 && q < K) src = q;
-  }
-  GeomPoint g;
-  g.x = pose[src * 3]; g.y = pose[src * 3 + 1]; g.z = pose[src * 3 + 2];
-  g.v0 = vis[src * 3]; g.v1 = vis[src * 3 + 1]; g.v2 = vis[src * 3 + 2];
-  if (flip) {
-    g.x = __dmul_rn(__dsub_rn(__dsub_rn(W, g.x), 1.0), g.v0);
-    g.y = __dmul_rn(g.y, g.v1);
-    g.z = __dmul_rn(g.z, g.v2);
-  }
-  if (through && g.v0 > 0.0) {
-    const double tx = __dadd_rn(__dadd_rn(__dmul_rn(m[0], g.x), __dmul_rn(m[1], g.y)), m[2]);
-    const double ty = __dadd_rn(__dadd_rn(__dmul_rn(m[3], g.x), __dmul_rn(m[4], g.y)), m[5]);
-    g.x = tx;
-    g.y = ty;
-  }
-  return g;
-}
-
 __global__ __launch_bounds__(256) void sample_geometry_kernel(buctd_sample_geom_args p) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), j = threadIdx.x & 63;
   if (b >= p.B) return;                                   // whole wavefronts leave: the shuffles below see 64 lanes
@@ -540,34 +538,16 @@ __global__ __launch_bounds__(256) void sample_geometry_kernel(buctd_sample_geom_
   int bad = 0;
   if (has_cond && (flags & BUCTD_GEOM_USE_BU_BBOX)) {     // wave-uniform
     const double ex = on ? p.cond[i * 3] : 0.0, ey = on ? p.cond[i * 3 + 1] : 0.0;
-    const bool nx = on && ex != 0.0, ny = on && ey != 0.0;
-    const bool empty = __ballot(nx) == 0 || __ballot(ny) == 0;
+    const KeypointBox box = keypoint_box(ex, ey, on, p.margin, W, H);
     const double xsum = wave_sum_f64(ex);
     const double y_first = p.cond[(long)b * p.K * 3 + 1];
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
-    const double xlo = wave_min_f64(nx ? ex : inf), xhi = wave_max_f64(nx ? ex : -inf);
-    const double ylo = wave_min_f64(ny ? ey : inf), yhi = wave_max_f64(ny ? ey : -inf);
-    if (empty) {
+    if (box.empty) {
       bad |= 1;
-    } else if (xsum != 0.0 && y_first != 0.0) {
-      // box_from_keypoints
-      const double x0 = fmin(fmax(__dsub_rn(xlo, p.margin), 0.0), W), x1 = fmin(fmax(__dadd_rn(xhi, p.margin), 0.0), W);
-      const double y0 = fmin(fmax(__dsub_rn(ylo, p.margin), 0.0), H), y1 = fmin(fmax(__dadd_rn(yhi, p.margin), 0.0), H);
-      double w = __dsub_rn(x1, x0), h = __dsub_rn(y1, y0);
+    } else if (xsum != 0.0 && y_first != 0.0) {               // the host's test (geometry()), reference quirk included
+      const CenterScale c = xywh2cs(box, p.aspect_ratio, p.scale_thre);
       has_box = true;
-      bx = x0; by = y0; bw = w; bh = h;
-      // xywh2cs
-      cx = (float)__dadd_rn(x0, __dmul_rn(w, 0.5));
-      cy = (float)__dadd_rn(y0, __dmul_rn(h, 0.5));
-      const double ah = __dmul_rn(p.aspect_ratio, h);
-      if (w > ah) h = w / p.aspect_ratio;
-      else if (w < ah) w = __dmul_rn(h, p.aspect_ratio);
-      s0 = (float)(w / 200.0);
-      s1 = (float)(h / 200.0);
-      if (cx != -1.f) {
-        s0 = __fmul_rn(s0, (float)p.scale_thre);
-        s1 = __fmul_rn(s1, (float)p.scale_thre);
-      }
+      bx = box.x0; by = box.y0; bw = box.w; bh = box.h;
+      cx = c.cx; cy = c.cy; s0 = c.s0; s1 = c.s1;
     }
   }
   // 2. half-body override
@@ -586,20 +566,17 @@ __global__ __launch_bounds__(256) void sample_geometry_kernel(buctd_sample_geom_
   // 6. joints, condition, target centres
   if (on) {
     GeomPoint g = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (!bad) g = geom_point(p.joints + (long)b * p.K * 3, p.joints_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m, true);
-    p.out_joints[i * 3] = g.x; p.out_joints[i * 3 + 1] = g.y; p.out_joints[i * 3 + 2] = g.z;
-    p.out_joints_vis[i * 3] = g.v0; p.out_joints_vis[i * 3 + 1] = g.v1; p.out_joints_vis[i * 3 + 2] = g.v2;
+    if (!bad) g = geom_point(p.joints + (long)b * p.K * 3, 3, p.joints_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m);
+    store_point(p.out_joints + i * 3, p.out_joints_vis + i * 3, g);
     p.target_xy[i * 3] = bad ? 0.f : target_centre(g.x, p.stride_x);
     p.target_xy[i * 3 + 1] = bad ? 0.f : target_centre(g.y, p.stride_y);
     p.target_xy[i * 3 + 2] = 0.f;
     p.target_vis[i] = (float)g.v0;
     if (has_cond) {
       GeomPoint c = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      if (!bad) c = geom_point(p.cond + (long)b * p.K * 3, p.cond_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m, true);
-      p.out_cond[i * 3] = c.x; p.out_cond[i * 3 + 1] = c.y; p.out_cond[i * 3 + 2] = c.z;
-      p.out_cond_vis[i * 3] = c.v0; p.out_cond_vis[i * 3 + 1] = c.v1; p.out_cond_vis[i * 3 + 2] = c.v2;
-      p.cond_trunc[i * 2] = (float)trunc(c.x);
-      p.cond_trunc[i * 2 + 1] = (float)trunc(c.y);
+      if (!bad) c = geom_point(p.cond + (long)b * p.K * 3, 3, p.cond_vis + (long)b * p.K * 3, j, p.K, flip, p.pair, W, t.m);
+      store_point(p.out_cond + i * 3, p.out_cond_vis + i * 3, c);
+      store_trunc(p.cond_trunc + i * 2, c.x, c.y);
     }
   }
   if (j != 0) return;

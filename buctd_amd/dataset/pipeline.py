@@ -28,12 +28,12 @@ import torch
 from .. import ops
 from .._C import RefineArgs, SampleGeomArgs, check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
-from ..utils.transforms import (_swap_table, affine_transform, flip_hm, flip_merge_device, flip_perm, fliplr_joints,
-                                get_affine_transform, mirror_condition)
+from ..utils.transforms import (_swap_table, affine_transform, flip_hm, flip_perm, fliplr_joints, get_affine_transform,
+                                mirror_condition)
 from .pose_synthesis import synthesize_pose_batch
 
 _M64 = (1 << 64) - 1
-MAX_DEVICE_JOINTS = 32         # buctd_sample_geometry, buctd_refine_step, buctd_cond_geometry: one lane per joint
+MAX_DEVICE_JOINTS = 32         # buctd_sample_geometry, buctd_refine_step, buctd_cond_geometry, buctd_cond_mirror
 GEOM_HAS_BBOX, GEOM_USE_BU_BBOX, GEOM_HALF_BODY, GEOM_FLIP = 1, 2, 4, 8      # BUCTD_GEOM_* of include/buctd_hip.h
 NO_BOX = ("sample(s) {bad} of the batch: use_bu_bbox with a condition pose without a non-zero x or y coordinate, or a "
           "box without extent (status {status}): there is no box to crop")
@@ -51,6 +51,35 @@ WARP_ITEM = np.dtype({"names": [f[0] for f in _WarpItem._fields_],
                       "formats": [np.uint64] + [np.int32] * 7 + [(np.float64, 6)],
                       "offsets": [getattr(_WarpItem, f[0]).offset for f in _WarpItem._fields_],
                       "itemsize": C.sizeof(_WarpItem)})
+
+
+def fill_warp_items(items, src, sizes, geos=None):
+    """items: zeroed WARP_ITEM array [B], filled column by column.  src: the images' device addresses; sizes: their
+    (H, W); geos: geometry() results - flip, keep-rectangle and crop affine - or None where buctd_sample_geometry writes
+    those columns itself."""
+    items["src"] = src
+    items["H"], items["W"] = np.asarray(sizes, dtype=np.int32).reshape(-1, 2).T
+    if geos is not None:
+        items["flip"] = [int(g["flip"]) for g in geos]
+        rects = [g.get("keep_rect") for g in geos]
+        items["rx"], items["ry"], items["rw"], items["rh"] = np.array(
+            [(0, 0, 0, 0) if r is None else tuple(int(v) for v in r) for r in rects], dtype=np.int32).reshape(-1, 4).T
+        items["m"] = [np.asarray(g["trans"], dtype=np.float64).reshape(6) for g in geos]
+    return items
+
+
+def _check_images(images):
+    for img in images:
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not img.is_cuda:
+            raise ValueError("images must be contiguous uint8 [H, W, 3] device tensors")
+
+
+def warp_items(images, geos=None, items=None):
+    """fill_warp_items for device images, into `items` (a zeroed WARP_ITEM array) or a new table."""
+    _check_images(images)
+    if items is None:
+        items = np.zeros(len(images), dtype=WARP_ITEM)
+    return fill_warp_items(items, [img.data_ptr() for img in images], [img.shape[:2] for img in images], geos)
 
 
 def xywh2cs(x, y, w, h, aspect_ratio, scale_thre, pixel_std=200):
@@ -153,6 +182,14 @@ def _views(buf, at):
         else:
             out[name] = raw.view(dt).reshape(shape)
     return out
+
+
+def history_layout(passes, B, K):
+    """The sections of IterativeRefiner's history buffer, what buctd_refine_step writes per pass: for _layout()."""
+    f32, f64 = np.float32, np.float64
+    return [("score", f64, (passes, B)), ("box_score", f64, (passes, B)), ("keypoint_score", f64, (passes, B)),
+            ("preds", f32, (passes, B, K, 3)), ("center", f32, (passes, B, 2)), ("scale", f32, (passes, B, 2)),
+            ("status", np.int32, (B,))]
 
 
 def batch_seed(seed, call):
@@ -388,18 +425,7 @@ class DeviceSamplePipeline:
     def warp_table(self, images, geos):
         """The per-sample table of the device kernels (buctd_warp_item: source image, flip, keep-rectangle, crop affine)
         as a uint8 device tensor."""
-        B = len(images)
-        items = (_WarpItem * B)()
-        for b, (img, g) in enumerate(zip(images, geos)):
-            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not img.is_cuda:
-                raise ValueError("images must be contiguous uint8 [H, W, 3] device tensors")
-            items[b].src, items[b].H, items[b].W = img.data_ptr(), int(img.shape[0]), int(img.shape[1])
-            items[b].flip = int(g["flip"])
-            rect = g.get("keep_rect")
-            items[b].rx, items[b].ry, items[b].rw, items[b].rh = (int(v) for v in rect) if rect is not None else (0, 0, 0, 0)
-            for k, v in enumerate(np.asarray(g["trans"], dtype=np.float64).reshape(6)):
-                items[b].m[k] = float(v)
-        return torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(images[0].device)
+        return torch.from_numpy(warp_items(images, geos).view(np.uint8)).to(images[0].device)
 
     def pair_table(self, dev):
         """int32 [K] on the device: the flip partner of every joint, -1 for a joint without one (uploaded once)."""
@@ -446,10 +472,7 @@ class DeviceSamplePipeline:
         if table is None:
             table = self.warp_table(images, geos)
         crop = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if want_crop else None
-        mean = (C.c_float * 3)(*self.mean.tolist())
-        std = (C.c_float * 3)(*self.std.tolist())
-        check(lib().buctd_warp_affine_norm(ptr(table), B, H, W, mean, std, ptr(x), x.stride(0), ptr(crop), stream_ptr()),
-              "warp_affine_norm")
+        self._warp(table, B, x, crop)
         # Gaussian targets: the heat-map centre mu = int(j / stride + 0.5) is evaluated here in float64 exactly like the
         # reference (JointsDataset.py:417-418).  The kernel recomputes (int)(v / stride + 0.5f), truncating toward zero as
         # well, so it is handed a v that maps back to the same mu: mu * stride for mu >= 0 and (mu - 1) * stride for mu < 0
@@ -475,20 +498,38 @@ class DeviceSamplePipeline:
             self.render_condition(x, cjt)
         return (x, target, weight, crop) if want_crop else (x, target, weight)
 
-    def condition_colors(self, dev):
-        """The colour table of a colored condition on the device (None for mono / stacked): a fresh upload per call."""
-        if not self.colored:
-            return None
-        return torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:self.num_joints])).to(dev)
+    def _warp(self, table, B, x, crop=None):
+        """The crops of table's first B items into channels [0, 3) of x (+ the uint8 crops): buctd_warp_affine_norm."""
+        mean = (C.c_float * 3)(*self.mean.tolist())
+        std = (C.c_float * 3)(*self.std.tolist())
+        check(lib().buctd_warp_affine_norm(ptr(table), B, int(x.shape[2]), int(x.shape[3]), mean, std, ptr(x), x.stride(0),
+                                           ptr(crop), stream_ptr()), "warp_affine_norm")
 
-    def render_condition(self, x, cjt, colors=None):
+    def mirror_colors(self, dev):
+        """The colour table on the device, uploaded once per device: what the mirrored half of a 3-channel condition is
+        rendered with (transforms.flip_hm renders it colored for a mono condition as well)."""
+        colors = self._colors_dev.get(dev)
+        if colors is None:
+            if self.kpt_colors is None:
+                raise ValueError("the flip test re-renders a 3-channel condition colored: the pipeline needs kpt_colors")
+            colors = torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:self.num_joints])).to(dev)
+            self._colors_dev[dev] = colors
+        return colors
+
+    def condition_colors(self, dev):
+        """mirror_colors() for a colored condition, None for mono / stacked."""
+        return self.mirror_colors(dev) if self.colored else None
+
+    def render_condition(self, x, cjt, colors=None, colored=None):
         """Condition heat-map of truncated crop coordinates cjt (float32 [B, K, 2], device) into channels [3, 3 + Cc) of the
-        network input x.  colors: condition_colors() if the caller uploaded it already."""
+        network input x.  colors: condition_colors() if the caller has it already; colored=True renders a mono
+        pipeline's 3-channel condition colored as well (the mirrored half of a flip-test input)."""
         dev = x.device
         B, K = int(x.shape[0]), self.num_joints
         W, H = int(self.image_size[0]), int(self.image_size[1])
-        if colors is None:
-            colors = self.condition_colors(dev)
+        colored = self.colored if colored is None else colored
+        if colors is None and colored:
+            colors = self.mirror_colors(dev)
         ws = ops.workspace(lib().buctd_cond_render_workspace(B * K if self.stacked else B, 3, H, W), dev)
         if self.stacked:
             # get_stacked_condition (JointsDataset.py:471-498): every joint is its own single-impulse image, blurred
@@ -497,7 +538,7 @@ class DeviceSamplePipeline:
             check(lib().buctd_cond_render_into(ptr(cjt), 2, None, B * K, 1, 1, H, W, 0, ptr(tmp), tmp.stride(0), ptr(ws),
                                                ws.numel(), stream_ptr()), "cond_render_into")
             x[:, 3:] = tmp.view(B, K, H, W)
-        elif self.colored:
+        elif colored:
             check(lib().buctd_cond_render_into(ptr(cjt), 2, ptr(colors), B, K, 3, H, W, 0,
                                                C.c_void_p(x[:, 3:].data_ptr()), x.stride(0), ptr(ws), ws.numel(),
                                                stream_ptr()), "cond_render_into")
@@ -551,17 +592,6 @@ class DeviceSamplePipeline:
                                       ptr(perm), B, int(channel0), int(count), H, W, stream_ptr()), "mirror_rows")
         return dst
 
-    def mirror_colors(self, dev):
-        """The colour table the mirrored half of a 3-channel condition is rendered with (transforms.flip_hm renders it
-        colored for a mono condition as well): uploaded once per device."""
-        colors = self._colors_dev.get(dev)
-        if colors is None:
-            if self.kpt_colors is None:
-                raise ValueError("the flip test re-renders a 3-channel condition colored: the pipeline needs kpt_colors")
-            colors = torch.from_numpy(np.ascontiguousarray(self.kpt_colors[:self.num_joints])).to(dev)
-            self._colors_dev[dev] = colors
-        return colors
-
     def warp_and_condition(self, table, cond_trunc, colors=None, mirrored=None):
         """Network input [B, 3 + Cc, H, W] from a device-resident warp_table() and truncated condition coordinates
         (float32 [B, K, 2], device): render() without the Gaussian targets and without any host array - the two kernels an
@@ -581,24 +611,16 @@ class DeviceSamplePipeline:
         if mirrored is not None and (mirrored[0].dim() != 3 or int(mirrored[0].shape[0]) != B or mirrored[0].device != dev):
             raise ValueError("warp_and_condition: mirrored[0] must be [B, K, 2 or 3] with the B of cond_trunc, on its device")
         x = torch.empty((rows, 3 + (K if self.stacked else 3), H, W), dtype=torch.float32, device=dev)
-        mean = (C.c_float * 3)(*self.mean.tolist())
-        std = (C.c_float * 3)(*self.std.tolist())
-        check(lib().buctd_warp_affine_norm(ptr(table), B, H, W, mean, std, ptr(x), x.stride(0), None, stream_ptr()),
-              "warp_affine_norm")
-        if mirrored is None:
-            self.render_condition(x, cond_trunc, colors)
-            return x
+        self._warp(table, B, x)
         first, second = x[:B], x[B:]
         self.render_condition(first, cond_trunc, colors)
-        self.mirror_rows(first, second, 0, 3)
-        if self.stacked:
-            self.mirror_rows(first, second, 3, K, self.pair_table(dev))
-        else:
-            cjm = self.cond_mirror(mirrored[0], mirrored[1])
-            ws = ops.workspace(lib().buctd_cond_render_workspace(B, 3, H, W), dev)
-            check(lib().buctd_cond_render_into(ptr(cjm), 2, ptr(self.mirror_colors(dev)), B, K, 3, H, W, 0,
-                                               C.c_void_p(second[:, 3:].data_ptr()), x.stride(0), ptr(ws), ws.numel(),
-                                               stream_ptr()), "cond_render_into")
+        if mirrored is not None:
+            self.mirror_rows(first, second, 0, 3)
+            if self.stacked:
+                self.mirror_rows(first, second, 3, K, self.pair_table(dev))
+            else:
+                cjm = self.cond_mirror(mirrored[0], mirrored[1])
+                self.render_condition(second, cjm, self.mirror_colors(dev), colored=True)
         return x
 
     # ---- scalar geometry on the device (geometry_on_device=True) ------------------------------------------------
@@ -635,9 +657,7 @@ class DeviceSamplePipeline:
         (float32 [B, K, 2]), target_xy, target_vis (the inputs of buctd_gaussian_target), center (float32 [B, 2]), scale
         (float64 [B, 2]: see apply_draw), rotation (float64 [B]) and status (int32 [B])."""
         images = [r["image"] for r in records]
-        for img in images:
-            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not img.is_cuda:
-                raise ValueError("images must be contiguous uint8 [H, W, 3] device tensors")
+        _check_images(images)
         dev = images[0].device
         B, K = len(records), self.num_joints
         f32, f64, i32 = np.float32, np.float64, np.int32
@@ -668,10 +688,7 @@ class DeviceSamplePipeline:
             hv["cond_vis"][:] = np.asarray(cond_vis, dtype=f64).reshape(B, K, 3)
             if not cond_on_device:
                 hv["cond"][:] = np.asarray(cond, dtype=f64).reshape(B, K, 3)
-        items = hv["items"].reshape(-1).view(WARP_ITEM)
-        items["src"] = [img.data_ptr() for img in images]
-        items["H"] = [img.shape[0] for img in images]
-        items["W"] = [img.shape[1] for img in images]
+        warp_items(images, items=hv["items"].reshape(-1).view(WARP_ITEM))
         sv = _views(torch.from_numpy(host).to(dev), at_in)
         outs = [("joints", f64, (B, K, 3)), ("joints_vis", f64, (B, K, 3)), ("scale", f64, (B, 2)), ("rotation", f64, (B,)),
                 ("target_xy", f32, (B, K, 3)), ("target_vis", f32, (B, K)), ("center", f32, (B, 2)), ("status", i32, (B,))]
@@ -711,43 +728,6 @@ class DeviceSamplePipeline:
             raise ValueError("pose synthesis: a condition without a non-zero x or y coordinate has no area - " +
                              NO_BOX.format(bad=bad.tolist(), status=st[bad].tolist()))
 
-    def call_on_device(self, records, aug=None, seed=None):
-        """__call__ with geometry_on_device=True: the draws on the host, everything after them on the device."""
-        images = [r["image"] for r in records]
-        table = self.draw_table(records, aug)
-        extra, cond, cond_vis = {}, None, None
-        if self.synthesizes:
-            if seed is None:
-                seed = batch_seed(self.seed, self.synth_calls)
-                self.synth_calls += 1
-            J, E, V, near, area = self.synthesis_inputs(records)
-            cond = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
-                                         device=images[0].device)
-            cond_vis = V
-            extra["synth_joints"] = cond
-        else:
-            conds = [self.condition(r) for r in records]
-            if all(c[2] for c in conds):
-                cond, cond_vis = np.stack([c[0] for c in conds]), np.stack([c[1] for c in conds])
-            elif any(c[2] for c in conds):
-                raise ValueError("geometry_on_device: either every record of a batch carries 'cond_joints' or none does")
-        g = self.device_geometry(records, table, cond, cond_vis)
-        x, target, weight = self.render(images, None, table=g["items"], cond_trunc=g.get("cond_trunc"),
-                                        targets=(g["target_xy"], g["target_vis"]))
-        zeros = None if cond is not None else torch.zeros_like(g["joints"])
-        meta = {
-            "image": [r.get("image_file", "") for r in records],
-            "joints": g["joints"], "joints_vis": g["joints_vis"],
-            "cond_joints": g["cond_joints"] if zeros is None else zeros,
-            "cond_joints_vis": g["cond_joints_vis"] if zeros is None else zeros,
-            "center": g["center"], "scale": g["scale"], "rotation": g["rotation"],
-            "score": torch.tensor([float(r.get("score", 1)) for r in records]),
-            "annotation_id": torch.tensor([int(r.get("annotation_id", -1)) for r in records]),
-            "status": g["status"], "table": g["items"],
-        }
-        meta.update(extra)
-        return x, target, weight, meta
-
     def synthesis_inputs(self, records):
         """Host side of JointsDataset.py:165-167 and 204-212 for a batch: ground-truth joints [B, K, 3], the conditions
         they are perturbed around and their visibilities, the neighbours [B, M, K, 3] (or None) and the areas [B]."""
@@ -759,50 +739,73 @@ class DeviceSamplePipeline:
         near = pad_near_joints([r.get("near_joints", ()) for r in records], K)
         return J, E, V, near, synthesis_area(E)
 
+    def _synthesize(self, records, seed):
+        """One buctd_synthesize_pose launch for the batch: the synthesized poses (float64 [B, K, 3] on the device, image
+        coordinates) and the conditions' visibilities (host).  seed None: the next of the pipeline's own seeds."""
+        if seed is None:
+            seed = batch_seed(self.seed, self.synth_calls)
+            self.synth_calls += 1
+        J, E, V, near, area = self.synthesis_inputs(records)
+        synth = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
+                                      device=records[0]["image"].device)
+        return synth, V
+
+    @staticmethod
+    def _meta(records, **tensors):
+        """meta of a batch: the records' own entries around the geometry's tensors."""
+        meta = {"image": [r.get("image_file", "") for r in records]}
+        meta.update(tensors)
+        meta["score"] = torch.tensor([float(r.get("score", 1)) for r in records])
+        meta["annotation_id"] = torch.tensor([int(r.get("annotation_id", -1)) for r in records])
+        return meta
+
     def __call__(self, records, aug=None, seed=None):
         """records: dicts with 'image' (uint8 HWC device tensor), 'joints_3d', 'joints_3d_vis', 'center', 'scale' and,
         for conditional models, 'cond_joints' / 'cond_joints_vis' (+ 'score', 'annotation_id', 'use_bu_bbox'; under
         generative sampling 'near_joints', see the class docstring).  seed: of the pose synthesis of this batch.
         Returns (input, target, target_weight, meta) like a collated DataLoader batch of the reference."""
-        if self.geometry_on_device:
-            return self.call_on_device(records, aug, seed)
         images = [r["image"] for r in records]
-        extra = {}
+        extra, synth, V = {}, None, None
         if self.synthesizes:
-            if seed is None:
-                seed = batch_seed(self.seed, self.synth_calls)
-                self.synth_calls += 1
-            J, E, V, near, area = self.synthesis_inputs(records)
-            synth = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
-                                          device=images[0].device)
+            synth, V = self._synthesize(records, seed)
             extra["synth_joints"] = synth
-            if any(r.get("use_bu_bbox", False) for r in records):
-                # the crop box itself comes from the synthesized pose (JointsDataset.py:218-228): host geometry
-                host = synth.cpu().numpy()
-                geos = [self.geometry(r, None if aug is None else aug[i], cond=(host[i], V[i]))
-                        for i, r in enumerate(records)]
-                x, target, weight = self.render(images, geos)
-            else:
-                geos = [self.geometry(r, None if aug is None else aug[i], cond=False) for i, r in enumerate(records)]
-                table = self.warp_table(images, geos)
-                cj, cv, cjt = self.cond_geometry(synth, torch.from_numpy(V).to(synth.device), table)
-                x, target, weight = self.render(images, geos, table=table, cond_trunc=cjt)
-                extra["cond_joints"], extra["cond_joints_vis"] = cj, cv
-        else:
-            geos = [self.geometry(r, None if aug is None else aug[i]) for i, r in enumerate(records)]
+        if self.geometry_on_device:                      # the draws on the host, everything after them on the device
+            cond, cond_vis = synth, V
+            if synth is None:
+                conds = [self.condition(r) for r in records]
+                if all(c[2] for c in conds):
+                    cond, cond_vis = np.stack([c[0] for c in conds]), np.stack([c[1] for c in conds])
+                elif any(c[2] for c in conds):
+                    raise ValueError("geometry_on_device: either every record of a batch carries 'cond_joints' or none does")
+            g = self.device_geometry(records, self.draw_table(records, aug), cond, cond_vis)
+            x, target, weight = self.render(images, None, table=g["items"], cond_trunc=g.get("cond_trunc"),
+                                            targets=(g["target_xy"], g["target_vis"]))
+            zeros = None if cond is not None else torch.zeros_like(g["joints"])
+            meta = self._meta(records, joints=g["joints"], joints_vis=g["joints_vis"],
+                              cond_joints=g["cond_joints"] if zeros is None else zeros,
+                              cond_joints_vis=g["cond_joints_vis"] if zeros is None else zeros,
+                              center=g["center"], scale=g["scale"], rotation=g["rotation"])
+            meta.update(status=g["status"], table=g["items"], **extra)
+            return x, target, weight, meta
+        augs = [None] * len(records) if aug is None else aug
+        if synth is None:
+            geos = [self.geometry(r, a) for r, a in zip(records, augs)]
             x, target, weight = self.render(images, geos)
-        meta = {
-            "image": [r.get("image_file", "") for r in records],
-            "joints": torch.from_numpy(np.stack([g["joints"] for g in geos])),
-            "joints_vis": torch.from_numpy(np.stack([g["joints_vis"] for g in geos])),
-            "cond_joints": torch.from_numpy(np.stack([g["cond_joints"] for g in geos])),
-            "cond_joints_vis": torch.from_numpy(np.stack([g["cond_joints_vis"] for g in geos])),
-            "center": torch.from_numpy(np.stack([g["center"] for g in geos])),
-            "scale": torch.from_numpy(np.stack([g["scale"] for g in geos])),
-            "rotation": torch.tensor([float(g["rot"]) for g in geos]),
-            "score": torch.tensor([float(r.get("score", 1)) for r in records]),
-            "annotation_id": torch.tensor([int(r.get("annotation_id", -1)) for r in records]),
-        }
+        elif any(r.get("use_bu_bbox", False) for r in records):
+            # the crop box itself comes from the synthesized pose (JointsDataset.py:218-228): host geometry
+            host = synth.cpu().numpy()
+            geos = [self.geometry(r, a, cond=(host[i], V[i])) for i, (r, a) in enumerate(zip(records, augs))]
+            x, target, weight = self.render(images, geos)
+        else:
+            geos = [self.geometry(r, a, cond=False) for r, a in zip(records, augs)]
+            table = self.warp_table(images, geos)
+            cj, cv, cjt = self.cond_geometry(synth, torch.from_numpy(V).to(synth.device), table)
+            x, target, weight = self.render(images, geos, table=table, cond_trunc=cjt)
+            extra["cond_joints"], extra["cond_joints_vis"] = cj, cv
+        stack = lambda key: torch.from_numpy(np.stack([g[key] for g in geos]))
+        meta = self._meta(records, joints=stack("joints"), joints_vis=stack("joints_vis"), cond_joints=stack("cond_joints"),
+                          cond_joints_vis=stack("cond_joints_vis"), center=stack("center"), scale=stack("scale"),
+                          rotation=torch.tensor([float(g["rot"]) for g in geos]))
         meta.update(extra)
         return x, target, weight, meta
 
@@ -819,14 +822,12 @@ class IterativeRefiner:
 
     flip_test=True: every pass is the flip test of validate() (reference function.py:213-236, which each of the three CLI
     runs goes through with TEST.FLIP_TEST True): one forward over [crops | mirrored crops], the two heat-maps merged with
-    flip_merge_device, then decoded.  shift_heatmap: the one-pixel shift of the mirrored half in that merge; None takes
+    ops.flipback_avg, then decoded.  shift_heatmap: the one-pixel shift of the mirrored half in that merge; None takes
     cfg.TEST.SHIFT_HEATMAP.  The keyword is explicit and off by default - cfg.TEST.FLIP_TEST is NOT read, callers of
     earlier versions keep their results bit for bit; flip_test=cfg.TEST.FLIP_TEST is the setting that equals the
     reference chain.  On the device chain the mirrored half is built on the device as well (buctd_mirror_rows,
     buctd_cond_mirror): still one upload before the loop and one copy back after it, and the model - ForwardGraph and
     Bf16Inference included - sees 2B rows."""
-
-    MAX_DEVICE_JOINTS = 32     # buctd_refine_step: one lane per joint, as buctd_cond_geometry
 
     def __init__(self, cfg, model, pipeline, in_vis_thre=None, use_dark=False, on_device=False, flip_test=False,
                  shift_heatmap=None):
@@ -843,8 +844,8 @@ class IterativeRefiner:
             if not pipeline.conditional:
                 raise ValueError("IterativeRefiner(on_device=True) needs a conditional config "
                                  "(MODEL.CONDITIONAL_TOPDOWN): without a condition there is nothing to refine")
-            if pipeline.num_joints > self.MAX_DEVICE_JOINTS:
-                raise ValueError(f"IterativeRefiner(on_device=True) handles at most {self.MAX_DEVICE_JOINTS} joints "
+            if pipeline.num_joints > MAX_DEVICE_JOINTS:
+                raise ValueError(f"IterativeRefiner(on_device=True) handles at most {MAX_DEVICE_JOINTS} joints "
                                  f"(MODEL.NUM_JOINTS is {pipeline.num_joints})")
 
     @staticmethod
@@ -893,6 +894,15 @@ class IterativeRefiner:
             cond = ops.cond_render(pts, pipe.mirror_colors(x.device), int(pipe.image_size[1]), int(pipe.image_size[0]))
         return torch.cat((x[:, :3].flip(3), cond), dim=1)
 
+    def _forward(self, x, B):
+        """The heat-maps of one pass: the model's last output for B persons.  With flip_test x is validate()'s paired
+        input [crops | mirrored crops] and the two halves are merged (buctd_flipback_avg) before the decode."""
+        hm = self.model(x)
+        hm = (hm[-1] if isinstance(hm, list) else hm).contiguous()
+        if self.flip_test:
+            hm = ops.flipback_avg(hm[:B], hm[B:], self.pipe.flip_perm(hm.device), self.shift_heatmap)
+        return hm
+
     @torch.no_grad()
     def run(self, records, passes=3):
         """Returns per pass: dict(preds [B, K, 3] image coordinates + max-val, score, box_score, keypoint_score)."""
@@ -903,15 +913,7 @@ class IterativeRefiner:
         for _ in range(passes):
             geos = [self.pipe.geometry(r) for r in records]
             x, _, _ = self.pipe.render([r["image"] for r in records], geos)
-            if self.flip_test:
-                # validate()'s paired forward: [crops | mirrored crops], merged before the decode
-                out = self.model(torch.cat((x, self.mirrored_input(x, geos)), dim=0))
-                out = out[-1] if isinstance(out, list) else out
-                n = x.shape[0]
-                out = flip_merge_device(out[:n], out[n:], self.pipe.flip_pairs, self.shift_heatmap)
-            else:
-                out = self.model(x)
-                out = out[-1] if isinstance(out, list) else out
+            out = self._forward(torch.cat((x, self.mirrored_input(x, geos)), dim=0) if self.flip_test else x, len(records))
             center = np.stack([g["center"] for g in geos])
             scale = np.stack([g["scale"] for g in geos])
             coords, maxvals = get_final_preds(self.cfg, out, center, scale, use_dark=self.use_dark)
@@ -926,7 +928,7 @@ class IterativeRefiner:
     def refine_step(self, decoded, state, table, out, p, passes, cond_joints=None):
         """One buctd_refine_step launch: decoded = (coords [B, K, 2], maxvals [B, K, 1], offsets [B, K, 2] or None) of pass
         p; state = (center, scale, box_score, cond_trunc) device tensors, overwritten with those of pass p + 1; table:
-        warp_table(), its matrices overwritten; out: the history sections of _layout()."""
+        warp_table(), its matrices overwritten; out: the views of history_layout()'s sections."""
         pipe = self.pipe
         coords, maxvals, offset = decoded
         a = RefineArgs()
@@ -941,9 +943,6 @@ class IterativeRefiner:
         a.margin, a.aspect_ratio = float(pipe.bu_bbox_margin), float(pipe.aspect_ratio)
         a.in_vis_thre, a.scale_thre = float(self.in_vis_thre), float(pipe.scale_thre)
         check(lib().buctd_refine_step(C.byref(a), stream_ptr()), "refine_step")
-
-    _layout = staticmethod(_layout)
-    _views = staticmethod(_views)
 
     def run_on_device(self, records, passes=3):
         """run() with on_device=True: one upload before the first pass, one copy back after the last."""
@@ -962,9 +961,9 @@ class IterativeRefiner:
             # the condition before trunc() - pass 0's from the host geometry, with its visibilities; buctd_refine_step
             # overwrites cond_joints with the next pass's, whose visibilities are all ones
             sections += [("cond_joints", f64, (B, K, 2)), ("cond_vis", f64, (B, K, 3))]
-        at_in, n_in = self._layout(sections)
+        at_in, n_in = _layout(sections)
         host = np.zeros(n_in, dtype=np.uint8)
-        hv = self._views(host, at_in)
+        hv = _views(host, at_in)
         hv["box_score"][:] = [float(r.get("score", 1)) for r in records]
         hv["center"][:] = np.stack([g["center"] for g in geos])
         hv["scale"][:] = np.stack([g["scale"] for g in geos])
@@ -972,34 +971,27 @@ class IterativeRefiner:
         if flip:
             hv["cond_joints"][:] = np.stack([g["cond_joints"][:, :2] for g in geos])
             hv["cond_vis"][:] = np.stack([g["cond_joints_vis"] for g in geos])
-        sv = self._views(torch.from_numpy(host).to(dev), at_in)
+        sv = _views(torch.from_numpy(host).to(dev), at_in)
         state = (sv["center"], sv["scale"], sv["box_score"], sv["cond_trunc"])
-        at_out, n_out = self._layout([("score", f64, (passes, B)), ("box_score", f64, (passes, B)),
-                                      ("keypoint_score", f64, (passes, B)), ("preds", f32, (passes, B, K, 3)),
-                                      ("center", f32, (passes, B, 2)), ("scale", f32, (passes, B, 2)),
-                                      ("status", np.int32, (B,))])
+        at_out, n_out = _layout(history_layout(passes, B, K))
         result = torch.zeros(n_out, dtype=torch.uint8, device=dev)
-        out = self._views(result, at_out)
+        out = _views(result, at_out)
         colors = pipe.condition_colors(dev)
         refine = bool(cfg.TEST.POST_PROCESS)
-        perm = pipe.flip_perm(dev) if flip else None
         for p in range(passes):
             if flip:
                 x = pipe.warp_and_condition(table, sv["cond_trunc"], colors,
                                             mirrored=(sv["cond_joints"], sv["cond_vis"] if p == 0 else None))
             else:
                 x = pipe.warp_and_condition(table, sv["cond_trunc"], colors)
-            hm = self.model(x)
-            hm = (hm[-1] if isinstance(hm, list) else hm).contiguous()
-            if flip:
-                hm = ops.flipback_avg(hm[:B], hm[B:], perm, self.shift_heatmap)
+            hm = self._forward(x, B)
             if self.use_dark:
                 res = ops.dark_decode(hm)
             else:
                 res = ops.argmax_decode(hm, refine=refine)
             self.refine_step((res[0], res[1], res[3] if (self.use_dark or refine) else None), state, table, out, p, passes,
                              cond_joints=sv["cond_joints"] if flip else None)
-        got = self._views(result.cpu().numpy(), at_out)
+        got = _views(result.cpu().numpy(), at_out)
         bad = np.nonzero(got["status"])[0]
         if bad.size:
             raise ValueError(f"iterative refinement: person(s) {bad.tolist()} of the batch have predictions without a "

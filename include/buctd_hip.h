@@ -714,7 +714,8 @@ int buctd_cond_render_into(const float* joints, int js, const float* colors, int
  * without leaving the device (JointsDataset.py:257-259 and 293-295, as DeviceSamplePipeline.geometry does them on the
  * host): per (sample, joint), with items[b].flip set, fliplr_joints - x = W - x - 1 (W = items[b].W), joints and
  * visibilities exchanged with pair[j] (-1: no partner), joints * visibilities - then (x, y) through items[b].m where
- * the (flipped) visibility's first column is > 0.  synth (straight from buctd_synthesize_pose, image coordinates) and
+ * the (flipped) visibility's first column is > 0 (geom_point of sample.hip, which buctd_cond_mirror and
+ * buctd_sample_geometry call as well).  synth (straight from buctd_synthesize_pose, image coordinates) and
  * cond_vis are float64 [B][K][3]; items_device is the table buctd_warp_affine_norm takes (only flip, W and m are read);
  * pair_device int [K].  out_joints / out_vis float64 [B][K][3]; out_trunc float32 [B][K][2] = trunc(x), trunc(y),
  * the `joints` argument of buctd_cond_render_into with js = 2.  float64 products and sums are never fused.  K <= 32. */
@@ -747,9 +748,11 @@ int buctd_mirror_rows(const float* in, long in_batch_stride, float* out, long ou
  *   scores     keypoint_score = mean of the maxvals > float32(in_vis_thre), 0 when none is; score = keypoint_score *
  *              box_score, summed in float64 (IterativeRefiner.rescore);
  *   box        min / max of the non-zero x and of the non-zero y of the float32 preds, -+ margin, clipped to [0, W] and
- *              [0, H] with W, H = items[b].W, items[b].H (dataset.pipeline.box_from_keypoints);
- *   center, scale   dataset.pipeline.xywh2cs: float32(x + w * 0.5), float32(w / 200) * float32(scale_thre), the aspect
- *              branches and the center[0] != -1 test;
+ *              [0, H] with W, H = items[b].W, items[b].H (dataset.pipeline.box_from_keypoints: keypoint_box of sample.hip,
+ *              shared with buctd_sample_geometry);
+ *   center, scale   dataset.pipeline.xywh2cs (xywh2cs of sample.hip, shared likewise):
+ *              float32(x + w * 0.5), float32(w / 200) * float32(scale_thre), the aspect branches and the
+ *              center[0] != -1 test;
  *   items[b].m get_affine_transform(center, scale, 0, crop size) in the closed form of
  *              utils.transforms.crop_affine_closed_form; src, H, W, flip and the rectangle are not written;
  *   cond_trunc trunc() of the preds through the new m (all visibilities 1: IterativeRefiner.next_records), float32

@@ -17,7 +17,7 @@ PASSES, PASS = 2, 1          # the call writes row 1 of two history rows; row 0 
 def _launch(case, dev, K):
     """One buctd_refine_step call on the case's inputs.  Returns the kernel's outputs as numpy arrays and the warp table
     before and after (as _WarpItem arrays)."""
-    from buctd_amd.dataset.pipeline import IterativeRefiner, _WarpItem, trunc_condition
+    from buctd_amd.dataset.pipeline import IterativeRefiner, _WarpItem, _layout, _views, history_layout
     from buctd_amd.utils.transforms import get_affine_transform
     pipe = pipe_for(K)
     refiner = IterativeRefiner(cfg_for(K), None, pipe, on_device=True)
@@ -28,16 +28,13 @@ def _launch(case, dev, K):
     before = (_WarpItem * B).from_buffer_copy(table.cpu().numpy().tobytes())
     up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     state = (up(case["center"]), up(case["scale"]), up(case["box_score"]), torch.full((B, K, 2), -7.0, device=dev))
-    at, n = refiner._layout([("score", np.float64, (PASSES, B)), ("box_score", np.float64, (PASSES, B)),
-                             ("keypoint_score", np.float64, (PASSES, B)), ("preds", np.float32, (PASSES, B, K, 3)),
-                             ("center", np.float32, (PASSES, B, 2)), ("scale", np.float32, (PASSES, B, 2)),
-                             ("status", np.int32, (B,))])
+    at, n = _layout(history_layout(PASSES, B, K))
     result = torch.zeros(n, dtype=torch.uint8, device=dev)
     cond64 = torch.full((B, K, 2), -7.0, dtype=torch.float64, device=dev)
     refiner.refine_step((up(case["coords"]), up(case["maxvals"]), up(case["offset"])), state, table,
-                        refiner._views(result, at), PASS, PASSES, cond_joints=cond64)
+                        _views(result, at), PASS, PASSES, cond_joints=cond64)
     torch.cuda.synchronize()
-    got = refiner._views(result.cpu().numpy(), at)
+    got = _views(result.cpu().numpy(), at)
     got.update(new_center=state[0].cpu().numpy(), new_scale=state[1].cpu().numpy(), new_box_score=state[2].cpu().numpy(),
                cond_trunc=state[3].cpu().numpy(), cond=cond64.cpu().numpy())
     after = (_WarpItem * B).from_buffer_copy(table.cpu().numpy().tobytes())

@@ -40,6 +40,27 @@ def test_warp_restatement_hand_derived_vectors():
     assert np.array_equal(out[:, 19], img[0, :])
 
 
+def test_warp_items_column_fill_equals_the_field_by_field_struct():
+    """fill_warp_items writes a WARP_ITEM table column by column; its bytes, padding included, are those of a
+    (_WarpItem * B) array filled field by field per record.  Records: flipped with a keep-rectangle, neither, a
+    keep-rectangle only."""
+    from buctd_amd.dataset.pipeline import WARP_ITEM, _WarpItem, fill_warp_items
+    rng = np.random.RandomState(3)
+    src, sizes = [0x7F0012345000, 0x7F00ABCDE040, 0x7FFE12340000], [(480, 640), (333, 501), (1, 7)]
+    geos = [dict(flip=True, keep_rect=(3, 0, 120, 451), trans=rng.randn(2, 3)), dict(flip=False, trans=rng.randn(2, 3)),
+            dict(flip=False, keep_rect=(17, 29, 5, 1), trans=rng.randn(6))]
+    items = (_WarpItem * 3)()
+    for b, g in enumerate(geos):
+        items[b].src, items[b].H, items[b].W = src[b], sizes[b][0], sizes[b][1]
+        items[b].flip = int(g["flip"])
+        rect = g.get("keep_rect")
+        items[b].rx, items[b].ry, items[b].rw, items[b].rh = (int(v) for v in rect) if rect is not None else (0, 0, 0, 0)
+        for k, v in enumerate(np.asarray(g["trans"], dtype=np.float64).reshape(6)):
+            items[b].m[k] = float(v)
+    filled = fill_warp_items(np.zeros(3, dtype=WARP_ITEM), src, sizes, geos)
+    assert bytes(filled) == bytes(items)
+
+
 def _cfg(colored=True):
     from oracle import cfg as ocfg
     c = ocfg.hrnet_cfg(16, 14, (64, 96), "pose_hrnet_coam", use_attention=True, colored=colored,

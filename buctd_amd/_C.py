@@ -237,9 +237,6 @@ SIGNATURES = {
     "buctd_refine_step": (_I, [C.POINTER(RefineArgs), _P]),
     "buctd_sample_geometry": (_I, [C.POINTER(SampleGeomArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
-    "buctd_mha_fwd_supported": (_I, [_I, _I]),
-    "buctd_mha_fwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P]),
-    "buctd_mha_fwd_bf16x6": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P]),
     "buctd_gconv_x6_supported": (_I, [_I] * 7),
     "buctd_gconv_x6_prep_bytes": (_SZ, [_I, _I, _I, _I]),
     "buctd_gconv_x6_prep": (_I, [_I, _I, _I, _P, _I, _P, _P]),
@@ -250,13 +247,7 @@ SIGNATURES = {
     "buctd_gconv_x6_fwd": (_I, [_I] * 6 + [_P] * 6 + [_I, _P, _P, _P, _P]),
     "buctd_gconv_x6_dgrad": (_I, [_I] * 6 + [_P] * 4 + [_P]),
     "buctd_mha_fwd_bf16x6_workspace": (_SZ, [_I, _I, _I]),
-    "buctd_mha_fwd_bf16x6_ws": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P, _SZ, _P]),
-    "buctd_mha_train_supported": (_I, [_I, _I]),
-    "buctd_mha_fwd_train": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _U64, _P, _P, _P]),
-    "buctd_mha_bwd_workspace": (_SZ, [_I, _I]),
-    "buctd_mha_bwd": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _U64, _P, _P, _I, _P, _I, _P, _SZ, _P]),
-    "buctd_mha_fwd_train_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P]),
-    "buctd_mha_bwd_dseed": (_I, [_I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
+    "buctd_mha_heads_fwd_bf16x6_ws": (_I, [C.POINTER(MhaArgs), _P, _SZ, _P]),
     "buctd_mha_heads_fwd_supported": (_I, [_I, _I, _I]),
     "buctd_mha_heads_fwd": (_I, [C.POINTER(MhaArgs), _P]),
     "buctd_mha_heads_fwd_bf16x6": (_I, [C.POINTER(MhaArgs), _P]),

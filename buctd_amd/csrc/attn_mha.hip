@@ -14,6 +14,7 @@
 // HBM bytes per image and layer: Q, K, V read once per 128-query tile from L2 (K, V: 2.75 MB stay L2-resident), O written
 // once: the kernel is bound by the fp32 MFMA rate (4 T^2 d FLOP at 157 TFLOP/s peak).
 #include "common.h"
+#include "split_bf16.h"
 #include "../../include/buctd_hip.h"
 
 #define MHA_BQ 128
@@ -180,17 +181,12 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_kernel(MhaFwdArgs arg) {
 //     16-byte row reads for the A operand of S^T; the V fragments in the enumeration above come out of the same layout
 //     through two ds_read_b64_tr_b16 transpose reads each);
 //   * Q is split once into registers (B operand of S^T), pre-multiplied by scale * log2(e): soft-max in the exp2 domain.
-typedef __bf16 mbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mbf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short mu16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ mbf16x8 mha_tr_pair(const unsigned char* p, const unsigned char* q) {
-  typedef __attribute__((address_space(3))) mbf16x4 lds_bf16x4;
-  const mbf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p);
-  const mbf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)q);
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ void mha_split8(const float (&x)[8], mbf16x8 (&pc)[3]) {
+// The transpose read, the six-MFMA product and the row stride are the shared ones of split_bf16.h.
+//
+// The pieces of a value come from the element-wise residual chain here (and in split_row4, mha_kv_split_kernel and the
+// soft-max slots of mha_fwd_x6q_kernel), not from split8<3> of split_bf16.h: the same values, other instructions inside the
+// tuned inner loops - swapping it is a performance change that wants its own measurement.
+__device__ __forceinline__ void mha_split8(const float (&x)[8], bf16x8 (&pc)[3]) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     float r = x[e];
@@ -202,21 +198,13 @@ __device__ __forceinline__ void mha_split8(const float (&x)[8], mbf16x8 (&pc)[3]
     }
   }
 }
-__device__ __forceinline__ void mha_mma6(f32x4& acc, const mbf16x8 (&a)[3], const mbf16x8 (&b)[3]) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
-}
 
 template <int DF, bool TAIL>
 __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
   const int T = arg.T, ldq = arg.ldq, ldk = arg.ldk, ldv = arg.ldv;
   const float scale = arg.scale;
   float* __restrict__ lse = arg.lse;
-  constexpr int D = DF * 16, LO = D * 2, RS = D * 6 + (((D * 6) % 64 == 32) ? 0 : 32), NK = (D + 31) / 32;
+  constexpr int D = DF * 16, LO = SplitRow<D, 3>::LO, RS = SplitRow<D, 3>::RS, NK = (D + 31) / 32;
   constexpr int C4 = D / 4, PL = (MHA_BK * C4 + 511) / 512;
   extern __shared__ __attribute__((aligned(16))) unsigned char smx[];
   unsigned char* kt = smx;                    // [64 keys][RS]
@@ -231,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
   const float* vb = arg.v + ((long)b * T) * ldv + head * D;
 
   // B operand of S^T: lane (query i16, group g) holds Q[q0 + i16][32 kk + 8 g .. +8] (zeros past d), pre-scaled
-  mbf16x8 qq[NK][3];
+  bf16x8 qq[NK][3];
   const float s2 = scale * 1.44269504088896340736f;
 #pragma unroll
   for (int kk = 0; kk < NK; ++kk) {
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
     }
   };
   auto split_row4 = [&](unsigned char* row, int c, f32x4 val) {
-    mu16x4 pc[3];
+    u16x4 pc[3];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float r = val[j];
@@ -285,7 +273,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
       }
     }
 #pragma unroll
-    for (int qp = 0; qp < 3; ++qp) *reinterpret_cast<mu16x4*>(row + qp * LO + 2 * c) = pc[qp];
+    for (int qp = 0; qp < 3; ++qp) *reinterpret_cast<u16x4*>(row + qp * LO + 2 * c) = pc[qp];
   };
   auto store_kv = [&]() {
 #pragma unroll
@@ -313,16 +301,16 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
       const unsigned char* krow = kt + (16 * f + i16) * RS;
 #pragma unroll
       for (int kk = 0; kk < NK; ++kk) {
-        mbf16x8 aa[3];
+        bf16x8 aa[3];
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) {
-          aa[qp] = *reinterpret_cast<const mbf16x8*>(krow + koff[kk] + qp * LO);
+          aa[qp] = *reinterpret_cast<const bf16x8*>(krow + koff[kk] + qp * LO);
           if (32 * kk + 8 * g >= D) {            // zero-padded tail of the channel contraction
 #pragma unroll
             for (int e = 0; e < 8; ++e) aa[qp][e] = (__bf16)0.f;
           }
         }
-        mha_mma6(st[f], aa, qq[kk]);
+        mfma_split<3>(st[f], aa, qq[kk]);
       }
     }
     // online soft-max of query i16 (its 64 logits of this tile sit in the four lanes i16 + 16 g)
@@ -356,15 +344,15 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
           pv[4 * fb + rg] = e2;
           lrun += e2;
         }
-      mbf16x8 pp[3];
+      bf16x8 pp[3];
       mha_split8(pv, pp);
       const unsigned char* vbase = vt + 32 * h * RS + tr_off;
 #pragma unroll
       for (int n = 0; n < DF; ++n) {
-        mbf16x8 bb[3];
+        bf16x8 bb[3];
 #pragma unroll
-        for (int qp = 0; qp < 3; ++qp) bb[qp] = mha_tr_pair(vbase + n * 32 + qp * LO, vbase + n * 32 + qp * LO + 16 * RS);
-        mha_mma6(o[n], pp, bb);
+        for (int qp = 0; qp < 3; ++qp) bb[qp] = tr_pair(vbase + n * 32 + qp * LO, vbase + n * 32 + qp * LO + 16 * RS);
+        mfma_split<3>(o[n], pp, bb);
       }
     }
   }
@@ -389,10 +377,11 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6_kernel(MhaFwdArgs arg) {
 // (VALU), multiply (MFMA)" rhythm in which the two pipes take turns.  Here mha_kv_split_kernel writes the tiles once per
 // layer in exactly the LDS layout ([key][d h | d m | d l | pad], RS bytes per key, 6 B per element) and the attention kernel
 // moves them HBM/L2 -> LDS with the DMA path (global_load_lds_dwordx4: no registers, no VALU, no ds_write):
-//   * K(j + 1) travels while O += P V(j) runs, V(j + 1) while S^T = K(j + 1) Q^T runs - one buffer each, two barriers per
-//     tile as before, but nothing is waited for;
-//   * workgroups of one image are dealt to ONE XCD (blockIdx -> (image, query tile) below), so its K/V image (4.3 MB at
-//     T = 3072, d = 112) is fetched into that XCD's L2 once instead of once per XCD.
+//   * a K tile travels while O += P V runs, a V tile while S^T = K Q^T runs - one buffer each, two barriers per tile as
+//     before, but nothing is waited for (the schedule is written out at the loop of mha_fwd_x6q_kernel);
+//   * workgroups of one image are dealt to ONE XCD (blockIdx -> (image, query tile) in mha_fwd_x6q_kernel: consecutive
+//     workgroup ids go round the 8 XCDs, XCD x gets the images = x mod 8), so its K/V image (4.3 MB at T = 3072, d = 112) is
+//     fetched into that XCD's L2 once instead of once per XCD.
 __global__ __launch_bounds__(256) void mha_kv_split_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                            long rows, int d, int ldk, int ldv, int rs,
                                                            unsigned char* __restrict__ k6, unsigned char* __restrict__ v6) {
@@ -405,7 +394,7 @@ __global__ __launch_bounds__(256) void mha_kv_split_kernel(const float* __restri
     const long row = idx / c4n;
     const int c = (int)(idx - row * c4n) * 4;
     const f32x4 val = *reinterpret_cast<const f32x4*>(src + row * ld + c);
-    mu16x4 pc[3];
+    u16x4 pc[3];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float r = val[j];
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(256) void mha_kv_split_kernel(const float* __restri
     }
     unsigned char* o = dst + row * rs + 2 * c;
 #pragma unroll
-    for (int qp = 0; qp < 3; ++qp) *reinterpret_cast<mu16x4*>(o + qp * 2 * d) = pc[qp];
+    for (int qp = 0; qp < 3; ++qp) *reinterpret_cast<u16x4*>(o + qp * 2 * d) = pc[qp];
   }
 }
 
@@ -429,161 +418,8 @@ __device__ __forceinline__ void mha_dma(const unsigned char* src_lane, unsigned 
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src_lane), "s"(lds_addr) : "memory");
 }
 
-template <int DF>
-__global__ __launch_bounds__(512, 1) void mha_fwd_x6p_kernel(const float* __restrict__ q,
-                                                             const unsigned char* __restrict__ k6,
-                                                             const unsigned char* __restrict__ v6, int B, int T, int ldq,
-                                                             float scale, float* __restrict__ out,
-                                                             float* __restrict__ lse) {
-  constexpr int D = DF * 16, LO = D * 2, RS = D * 6 + (((D * 6) % 64 == 32) ? 0 : 32), NK = (D + 31) / 32;
-  constexpr int TILE = MHA_BK * RS, NINS = TILE / 1024, NI = (NINS + 7) / 8;
-  static_assert(TILE % 1024 == 0, "a 64-key tile is a whole number of 1 KB wave copies");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smx[];
-  unsigned char* kt = smx;                    // [64 keys][RS]
-  unsigned char* vt = smx + TILE;             // [64 keys][RS]
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int i16 = lane & 15, g = lane >> 4;
-  // workgroup -> (image, query tile): consecutive workgroup ids go round the 8 XCDs; give XCD x the images = x mod 8
-  const int nq = T / MHA_BQ;
-  int b, qt;
-  if ((B & 7) == 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int grp = slot / nq;
-    b = grp * 8 + xcd;
-    qt = slot - grp * nq;
-  } else {
-    b = blockIdx.x / nq;
-    qt = blockIdx.x - b * nq;
-  }
-  const int q0 = qt * MHA_BQ + wave * 16;
-  const float* qb = q + ((long)b * T) * ldq;
-  const unsigned char* kimg = k6 + (long)b * T * RS + lane * 16;
-  const unsigned char* vimg = v6 + (long)b * T * RS + lane * 16;
-  auto dma_tile = [&](const unsigned char* img, int k0, unsigned char* dst) {
-    const unsigned char* src = img + (long)k0 * RS;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int u = wave + 8 * i;
-      if (u < NINS) mha_dma(src + u * 1024, dst + u * 1024);
-    }
-  };
-  dma_tile(kimg, 0, kt);
-  dma_tile(vimg, 0, vt);
-
-  mbf16x8 qq[NK][3];
-  const float s2 = scale * 1.44269504088896340736f;
-#pragma unroll
-  for (int kk = 0; kk < NK; ++kk) {
-    const int c0 = 32 * kk + 8 * g;
-    float x[8];
-    if (c0 < D) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldq + c0);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(qb + (long)(q0 + i16) * ldq + c0 + 4);
-      x[0] = a.x * s2; x[1] = a.y * s2; x[2] = a.z * s2; x[3] = a.w * s2;
-      x[4] = c.x * s2; x[5] = c.y * s2; x[6] = c.z * s2; x[7] = c.w * s2;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = 0.f;
-    }
-    mha_split8(x, qq[kk]);
-  }
-  f32x4 o[DF];
-#pragma unroll
-  for (int n = 0; n < DF; ++n) o[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float mrun = -INFINITY, lrun = 0.f;
-  int koff[NK];
-#pragma unroll
-  for (int kk = 0; kk < NK; ++kk) {
-    const int c0 = 32 * kk + 8 * g;
-    koff[kk] = (c0 < D ? c0 : 0) * 2;
-  }
-  const int tr_off = (4 * g + (i16 >> 2)) * RS + (i16 & 3) * 8;
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int k0 = 0; k0 < T; k0 += MHA_BK) {
-    f32x4 st[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      st[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      const unsigned char* krow = kt + (16 * f + i16) * RS;
-#pragma unroll
-      for (int kk = 0; kk < NK; ++kk) {
-        mbf16x8 aa[3];
-#pragma unroll
-        for (int qp = 0; qp < 3; ++qp) {
-          aa[qp] = *reinterpret_cast<const mbf16x8*>(krow + koff[kk] + qp * LO);
-          if (32 * kk + 8 * g >= D) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) aa[qp][e] = (__bf16)0.f;
-          }
-        }
-        mha_mma6(st[f], aa, qq[kk]);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // V(j) (sent during the previous P V phase) has landed
-    __syncthreads();                                       // ... for everyone, and nobody reads K(j) any more
-    if (k0 + MHA_BK < T) dma_tile(kimg, k0 + MHA_BK, kt);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) mx = fmaxf(mx, st[f][rg]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mnew = fmaxf(mrun, mx);
-    if (__any(mnew > mrun)) {
-      const float fac = __builtin_amdgcn_exp2f(mrun - mnew);
-      lrun *= fac;
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const float fr = __shfl(fac, g * 4 + rg, 64);
-#pragma unroll
-        for (int n = 0; n < DF; ++n) o[n][rg] *= fr;
-      }
-      mrun = mnew;
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      float pv[8];
-#pragma unroll
-      for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float e2 = __builtin_amdgcn_exp2f(st[2 * h + fb][rg] - mrun);
-          pv[4 * fb + rg] = e2;
-          lrun += e2;
-        }
-      mbf16x8 pp[3];
-      mha_split8(pv, pp);
-      const unsigned char* vbase = vt + 32 * h * RS + tr_off;
-#pragma unroll
-      for (int n = 0; n < DF; ++n) {
-        mbf16x8 bb[3];
-#pragma unroll
-        for (int qp = 0; qp < 3; ++qp) bb[qp] = mha_tr_pair(vbase + n * 32 + qp * LO, vbase + n * 32 + qp * LO + 16 * RS);
-        mha_mma6(o[n], pp, bb);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // K(j + 1) has landed
-    __syncthreads();                                       // ... for everyone, and nobody reads V(j) any more
-    if (k0 + MHA_BK < T) dma_tile(vimg, k0 + MHA_BK, vt);
-  }
-  lrun += __shfl_xor(lrun, 16, 64);
-  lrun += __shfl_xor(lrun, 32, 64);
-  const float linv = 1.f / lrun;
-  if (lse && g == 0) lse[(long)b * T + q0 + i16] = (mrun + __builtin_amdgcn_logf(lrun)) * 0.69314718055994530942f;
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg) {
-    const float fl = __shfl(linv, g * 4 + rg, 64);
-    float* op = out + ((long)b * T + q0 + g * 4 + rg) * (long)D;
-#pragma unroll
-    for (int n = 0; n < DF; ++n) op[16 * n + i16] = o[n][rg] * fl;
-  }
-}
-
-// The same with 32 queries per wavefront.  With 16, every wavefront reads the whole K and V tile from LDS for 180 MFMAs:
+// The attention kernel over the pre-split tiles: 32 queries per wavefront.  With 16 (as in mha_fwd_x6_kernel), every
+// wavefront reads the whole K and V tile from LDS for 180 MFMAs:
 // 8 wavefronts x 90 KB per 64 keys = 5760 LDS cycles per CU against 5760 MFMA cycles per SIMD - the LDS port is as busy as
 // the matrix pipe and the two do not overlap perfectly (measured 0.45-0.5 of the MFMA roof).  Two query blocks per
 // wavefront reuse every K fragment (A operand of S^T) and every V fragment (B operand of P V) twice: half the LDS bytes
@@ -591,13 +427,14 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6p_kernel(const float* __rest
 // wavefronts on 2048 slots would be 1.5 rounds), a workgroup keeps 8 wavefronts and 128 queries and splits the KEYS:
 // wavefronts 0-3 attend to the first half of the keys, 4-7 to the second (each half streams its own 32-key K and V tiles,
 // 4 x 22 KB of LDS at d = 112), and the two partial soft-max states of a query (o, m, l) are merged through LDS at the end.
+// One head, out and lse contiguous ([B][T][D], [B][T]); q with its own row stride.
 template <int DF>
 __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __restrict__ q,
                                                              const unsigned char* __restrict__ k6,
                                                              const unsigned char* __restrict__ v6, int B, int T, int ldq,
                                                              float scale, float* __restrict__ out,
                                                              float* __restrict__ lse) {
-  constexpr int D = DF * 16, LO = D * 2, RS = D * 6 + (((D * 6) % 64 == 32) ? 0 : 32), NK = (D + 31) / 32;
+  constexpr int D = DF * 16, LO = SplitRow<D, 3>::LO, RS = SplitRow<D, 3>::RS, NK = (D + 31) / 32;
   constexpr int BK = 32, TILE = BK * RS, NINS = TILE / 1024, NI = (NINS + 3) / 4;
   static_assert(TILE % 1024 == 0, "a 32-key tile is a whole number of 1 KB wave copies");
   extern __shared__ __attribute__((aligned(16))) unsigned char smx[];
@@ -607,6 +444,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
   unsigned char* kt = smx + kh * 2 * TILE;    // this half's [32 keys][RS]
   unsigned char* vt = kt + TILE;
   const int i16 = lane & 15, g = lane >> 4;
+  // workgroup -> (image, query tile): consecutive workgroup ids go round the 8 XCDs; give XCD x the images = x mod 8
   const int nq = T / MHA_BQ;
   int b, qt;
   if ((B & 7) == 0) {
@@ -634,7 +472,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
   dma_tile(kimg, 0, kt);
   dma_tile(vimg, 0, vt);
 
-  mbf16x8 qq[2][NK][3];
+  bf16x8 qq[2][NK][3];
   const float s2 = scale * 1.44269504088896340736f;
 #pragma unroll
   for (int w = 0; w < 2; ++w)
@@ -676,17 +514,17 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
       const unsigned char* krow = kt + (16 * f + i16) * RS;
 #pragma unroll
       for (int kk = 0; kk < NK; ++kk) {
-        mbf16x8 aa[3];
+        bf16x8 aa[3];
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) {
-          aa[qp] = *reinterpret_cast<const mbf16x8*>(krow + koff[kk] + qp * LO);
+          aa[qp] = *reinterpret_cast<const bf16x8*>(krow + koff[kk] + qp * LO);
           if (32 * kk + 8 * g >= D) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) aa[qp][e] = (__bf16)0.f;
           }
         }
-        mha_mma6(sx[0][f], aa, qq[0][kk]);
-        mha_mma6(sx[1][f], aa, qq[1][kk]);
+        mfma_split<3>(sx[0][f], aa, qq[0][kk]);
+        mfma_split<3>(sx[1][f], aa, qq[1][kk]);
       }
     }
   };
@@ -740,10 +578,10 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
         sn[1][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
       const unsigned char* krow = kt + (16 * f + i16) * RS;
-      mbf16x8 aa[3];
+      bf16x8 aa[3];
 #pragma unroll
       for (int qp = 0; qp < 3; ++qp) {
-        aa[qp] = *reinterpret_cast<const mbf16x8*>(krow + koff[kk] + qp * LO);
+        aa[qp] = *reinterpret_cast<const bf16x8*>(krow + koff[kk] + qp * LO);
         if (32 * kk + 8 * g >= D) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) aa[qp][e] = (__bf16)0.f;
@@ -760,10 +598,10 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
           const int w = pr >> 2, ix = 2 * ((pr >> 1) & 1) + (pr & 1);
           asm volatile("" : "+v"(a0), "+v"(ppu[w][0][ix]), "+v"(ppu[w][1][ix]), "+v"(ppu[w][2][ix]), "+v"(lrun[w]));
         }
-        aa[0] = __builtin_bit_cast(mbf16x8, a0);
+        aa[0] = __builtin_bit_cast(bf16x8, a0);
       }
-      mha_mma6(sn[0][f], aa, qq[0][kk]);
-      mha_mma6(sn[1][f], aa, qq[1][kk]);
+      mfma_split<3>(sn[0][f], aa, qq[0][kk]);
+      mfma_split<3>(sn[1][f], aa, qq[1][kk]);
 #pragma unroll
       for (int pr = 0; pr < 8; ++pr) {
         if ((pr * SL) / 8 != i) continue;
@@ -782,7 +620,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
         }
       }
     }
-    mbf16x8 pp[2][3];
+    bf16x8 pp[2][3];
 #pragma unroll
     for (int w = 0; w < 2; ++w)
 #pragma unroll
@@ -790,7 +628,7 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
         typedef unsigned mu32x4 __attribute__((ext_vector_type(4)));
         mu32x4 r = {ppu[w][qp][0], ppu[w][qp][1], ppu[w][qp][2], ppu[w][qp][3]};
         asm volatile("" : "+v"(r));       // the probabilities stay on this side of the barrier
-        pp[w][qp] = __builtin_bit_cast(mbf16x8, r);
+        pp[w][qp] = __builtin_bit_cast(bf16x8, r);
       }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // V(j) has landed
     __syncthreads();                                       // ... for everyone, and nobody reads K(j + 1) any more
@@ -798,12 +636,12 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
     const unsigned char* vbase = vt + tr_off;
 #pragma unroll
     for (int n = 0; n < DF; ++n) {
-      mbf16x8 bb[3];
+      bf16x8 bb[3];
 #pragma unroll
       for (int qp = 0; qp < 3; ++qp)
-        bb[qp] = mha_tr_pair(vbase + n * 32 + qp * LO, vbase + n * 32 + qp * LO + 16 * RS);
-      mha_mma6(o[0][n], pp[0], bb);
-      mha_mma6(o[1][n], pp[1], bb);
+        bb[qp] = tr_pair(vbase + n * 32 + qp * LO, vbase + n * 32 + qp * LO + 16 * RS);
+      mfma_split<3>(o[0][n], pp[0], bb);
+      mfma_split<3>(o[1][n], pp[1], bb);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // K(j + 2) has landed
     __syncthreads();                                       // ... for everyone, and nobody reads V(j) any more
@@ -852,17 +690,8 @@ __global__ __launch_bounds__(512, 1) void mha_fwd_x6q_kernel(const float* __rest
   }
 }
 
-static size_t mha_x6_lds(int d) {
-  const int rs = d * 6 + (((d * 6) % 64 == 32) ? 0 : 32);
-  return (size_t)2 * MHA_BK * rs;
-}
-
 static size_t mha_lds(int d) {
   return ((size_t)MHA_BK * (d + 8) + (size_t)d * (MHA_BK + 8) + (size_t)8 * 16 * (MHA_BK + 8)) * sizeof(float);
-}
-
-extern "C" int buctd_mha_fwd_supported(int T, int d) {
-  return (T > 0 && T % MHA_BQ == 0 && d >= 16 && d <= 128 && d % 16 == 0) ? 1 : 0;
 }
 
 extern "C" int buctd_mha_heads_fwd_supported(int T, int h, int dh) {
@@ -873,21 +702,20 @@ template <int DF, bool TAIL>
 static int mha_launch(int B, int h, const MhaFwdArgs& a, int x6, hipStream_t st) {
   static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
   void (*fn)(MhaFwdArgs) = x6 ? mha_fwd_x6_kernel<DF, TAIL> : mha_fwd_kernel<DF, TAIL>;
-  const size_t lds = x6 ? mha_x6_lds(DF * 16) : mha_lds(DF * 16);
-  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, attr_done[x6 ? 1 : 0], "buctd_mha_fwd")) return rc;
+  const size_t lds = x6 ? (size_t)2 * MHA_BK * SplitRow<DF * 16, 3>::RS : mha_lds(DF * 16);
+  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, attr_done[x6 ? 1 : 0], "buctd_mha_heads_fwd")) return rc;
   hipLaunchKernelGGL(fn, dim3((a.T + MHA_BQ - 1) / MHA_BQ, B, h), dim3(512), lds, st, a);
-  BUCTD_CHECK_LAUNCH("buctd_mha_fwd");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_fwd");
   return BUCTD_OK;
 }
 
-// the general launcher: the one-head entry points below are its h = 1, ldk = ldq, ldo = d case
 static int mha_run(const buctd_mha_args& g, int x6, void* stream) {
-  BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.B > 0 && g.B <= 65535, "buctd_mha_fwd: null pointer or bad batch");
+  BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.B > 0 && g.B <= 65535, "buctd_mha_heads_fwd: null pointer or bad batch");
   BUCTD_CHECK_ARG(buctd_mha_heads_fwd_supported(g.T, g.h, g.dh),
-                  "buctd_mha_fwd: unsupported shape T%d h%d dh%d (T %% 64 == 0, dh %% 16 == 0, dh <= 128)", g.T, g.h, g.dh);
+                  "buctd_mha_heads_fwd: unsupported shape T%d h%d dh%d (T %% 64 == 0, dh %% 16 == 0, dh <= 128)", g.T, g.h, g.dh);
   const int hd = g.h * g.dh;
   BUCTD_CHECK_ARG(g.ldq >= hd && g.ldk >= hd && g.ldv >= hd && g.ldo >= hd && g.ldq % 4 == 0 && g.ldk % 4 == 0 && g.ldv % 4 == 0,
-                  "buctd_mha_fwd: row strides must be >= h * dh and 16-byte aligned");
+                  "buctd_mha_heads_fwd: row strides must be >= h * dh and 16-byte aligned");
   MhaFwdArgs a;
   a.q = g.q; a.k = g.k; a.v = g.v; a.out = g.out; a.lse = g.lse;
   a.T = g.T; a.ldq = g.ldq; a.ldk = g.ldk; a.ldv = g.ldv; a.ldo = g.ldo;
@@ -899,29 +727,8 @@ static int mha_run(const buctd_mha_args& g, int x6, void* stream) {
     MHA_CASE(1) MHA_CASE(2) MHA_CASE(3) MHA_CASE(4) MHA_CASE(5) MHA_CASE(6) MHA_CASE(7) MHA_CASE(8)
 #undef MHA_CASE
   }
-  buctd_set_error("buctd_mha_fwd: no kernel for dh=%d", g.dh);
+  buctd_set_error("buctd_mha_heads_fwd: no kernel for dh=%d", g.dh);
   return BUCTD_EINVAL;
-}
-
-static int mha_run1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                    float* out, float* lse, int x6, void* stream) {
-  BUCTD_CHECK_ARG(buctd_mha_fwd_supported(T, d), "buctd_mha_fwd: unsupported shape T%d d%d (T %% 128 == 0, d %% 16 == 0, d <= 128)",
-                  T, d);
-  buctd_mha_args g = {};
-  g.B = B; g.T = T; g.h = 1; g.dh = d;
-  g.q = q; g.k = k; g.v = v; g.ldq = ldqk; g.ldk = ldqk; g.ldv = ldv;
-  g.out = out; g.ldo = d; g.lse = lse; g.scale = scale;
-  return mha_run(g, x6, stream);
-}
-
-extern "C" int buctd_mha_fwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                             float scale, float* out, float* lse, void* stream) {
-  return mha_run1(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 0, stream);
-}
-
-extern "C" int buctd_mha_fwd_bf16x6(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
-                                    int ldv, float scale, float* out, float* lse, void* stream) {
-  return mha_run1(B, T, d, q, k, v, ldqk, ldv, scale, out, lse, 1, stream);
 }
 
 extern "C" int buctd_mha_heads_fwd(const buctd_mha_args* a, void* stream) {
@@ -934,59 +741,55 @@ extern "C" int buctd_mha_heads_fwd_bf16x6(const buctd_mha_args* a, void* stream)
   return mha_run(*a, 1, stream);
 }
 
-static int mha_x6_rs(int d) { return d * 6 + (((d * 6) % 64 == 32) ? 0 : 32); }
-static constexpr int mha_x6_rs_c(int d) { return d * 6 + (((d * 6) % 64 == 32) ? 0 : 32); }
+// what the pre-split kernel covers (one head on top of this): whole 128-query tiles, two key halves of whole 32-key tiles
+static bool mha_presplit_shape(int T, int d) { return T > 0 && T % MHA_BQ == 0 && d >= 16 && d <= 128 && d % 16 == 0; }
 
 extern "C" size_t buctd_mha_fwd_bf16x6_workspace(int B, int T, int d) {
-  if (B <= 0 || !buctd_mha_fwd_supported(T, d)) return 0;
-  return (size_t)2 * B * T * mha_x6_rs(d);
+  if (B <= 0 || !mha_presplit_shape(T, d)) return 0;
+  return (size_t)2 * B * T * split_row_bytes(d, 3);
 }
 
 template <int DF>
 static int mha_launch_p(int B, int T, const float* q, const unsigned char* k6, const unsigned char* v6, int ldq, float scale,
                         float* out, float* lse, hipStream_t st) {
-  static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
-  constexpr bool wide = true;
-  // wide (default): 32 queries per wavefront, keys split over the two wave quartets, 32-key tiles; BUCTD_MHA_Q16=1 keeps the
-  // 16-query kernel (bit-identical to buctd_mha_fwd_bf16x6) for comparison
-  void (*fn)(const float*, const unsigned char*, const unsigned char*, int, int, int, float, float*, float*) =
-      wide ? mha_fwd_x6q_kernel<DF> : mha_fwd_x6p_kernel<DF>;
-  const size_t lds = wide ? (size_t)4 * 32 * mha_x6_rs_c(DF * 16) : mha_x6_lds(DF * 16);
-  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, attr_done[wide ? 1 : 0], "buctd_mha_fwd_bf16x6_ws"))
+  static unsigned char attr_done[BUCTD_MAX_DEVICES] = {0};
+  const size_t lds = (size_t)4 * 32 * SplitRow<DF * 16, 3>::RS;      // K and V tiles of 32 keys for each key half
+  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(mha_fwd_x6q_kernel<DF>), 160 * 1024, attr_done,
+                                           "buctd_mha_heads_fwd_bf16x6_ws"))
     return rc;
-  hipLaunchKernelGGL(fn, dim3((unsigned)(B * (T / MHA_BQ))), dim3(512), lds, st, q, k6, v6, B, T, ldq, scale,
+  hipLaunchKernelGGL(mha_fwd_x6q_kernel<DF>, dim3((unsigned)(B * (T / MHA_BQ))), dim3(512), lds, st, q, k6, v6, B, T, ldq, scale,
                      out, lse);
-  BUCTD_CHECK_LAUNCH("buctd_mha_fwd_bf16x6_ws");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_fwd_bf16x6_ws");
   return BUCTD_OK;
 }
 
-extern "C" int buctd_mha_fwd_bf16x6_ws(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
-                                       int ldv, float scale, float* out, float* lse, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  BUCTD_CHECK_ARG(q && k && v && out && B > 0, "buctd_mha_fwd_bf16x6_ws: null pointer");
-  BUCTD_CHECK_ARG(buctd_mha_fwd_supported(T, d),
-                  "buctd_mha_fwd_bf16x6_ws: unsupported shape T%d d%d (T %% 128 == 0, d %% 16 == 0, d <= 128)", T, d);
-  BUCTD_CHECK_ARG(ldqk >= d && ldv >= d && ldqk % 4 == 0 && ldv % 4 == 0,
-                  "buctd_mha_fwd_bf16x6_ws: row strides must be >= d and 16-byte aligned");
+extern "C" int buctd_mha_heads_fwd_bf16x6_ws(const buctd_mha_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd_bf16x6_ws: null descriptor");
+  const int B = a->B, T = a->T, d = a->dh;
+  BUCTD_CHECK_ARG(a->q && a->k && a->v && a->out && B > 0, "buctd_mha_heads_fwd_bf16x6_ws: null pointer or bad batch");
+  BUCTD_CHECK_ARG(a->h == 1 && mha_presplit_shape(T, d),
+                  "buctd_mha_heads_fwd_bf16x6_ws: unsupported shape T%d h%d dh%d (h == 1, T %% 128 == 0, dh %% 16 == 0, dh <= 128)",
+                  T, a->h, d);
+  BUCTD_CHECK_ARG(a->ldq >= d && a->ldk >= d && a->ldv >= d && a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->ldo == d,
+                  "buctd_mha_heads_fwd_bf16x6_ws: row strides must be >= dh and 16-byte aligned, out contiguous (ldo == dh)");
+  const int rs = split_row_bytes(d, 3);
   const size_t need = buctd_mha_fwd_bf16x6_workspace(B, T, d);
-  BUCTD_CHECK_ARG(workspace && workspace_bytes >= need, "buctd_mha_fwd_bf16x6_ws: workspace of %zu bytes needed, %zu given", need,
-                  workspace_bytes);
-  BUCTD_CHECK_ARG((long)B * T * mha_x6_rs(d) < (1L << 40), "buctd_mha_fwd_bf16x6_ws: tensor too large");
+  BUCTD_CHECK_ARG(workspace && workspace_bytes >= need, "buctd_mha_heads_fwd_bf16x6_ws: workspace of %zu bytes needed, %zu given",
+                  need, workspace_bytes);
+  BUCTD_CHECK_ARG((long)B * T * rs < (1L << 40), "buctd_mha_heads_fwd_bf16x6_ws: tensor too large");
   hipStream_t st = (hipStream_t)stream;
   unsigned char* k6 = (unsigned char*)workspace;
   unsigned char* v6 = k6 + need / 2;
   const long rows = (long)B * T;
   long blocks = (rows * (d / 4) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(mha_kv_split_kernel, dim3((unsigned)blocks, 2), dim3(256), 0, st, k, v, rows, d, ldqk, ldv, mha_x6_rs(d),
-                     k6, v6);
-  BUCTD_CHECK_LAUNCH("buctd_mha_fwd_bf16x6_ws (split)");
+  hipLaunchKernelGGL(mha_kv_split_kernel, dim3((unsigned)blocks, 2), dim3(256), 0, st, a->k, a->v, rows, d, a->ldk, a->ldv, rs, k6, v6);
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_fwd_bf16x6_ws (split)");
   switch (d / 16) {
-#define MHA_CASE(n) case n: return mha_launch_p<n>(B, T, q, k6, v6, ldqk, scale, out, lse, st);
+#define MHA_CASE(n) case n: return mha_launch_p<n>(B, T, a->q, k6, v6, a->ldq, a->scale, a->out, a->lse, st);
     MHA_CASE(1) MHA_CASE(2) MHA_CASE(3) MHA_CASE(4) MHA_CASE(5) MHA_CASE(6) MHA_CASE(7) MHA_CASE(8)
 #undef MHA_CASE
   }
-  buctd_set_error("buctd_mha_fwd_bf16x6_ws: no kernel for d=%d", d);
+  buctd_set_error("buctd_mha_heads_fwd_bf16x6_ws: no kernel for dh=%d", d);
   return BUCTD_EINVAL;
 }
-

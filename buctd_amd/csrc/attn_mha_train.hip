@@ -378,10 +378,6 @@ static size_t mt_fwd_lds(int d) {
 }
 static size_t mt_bwd_lds(int d) { return ((size_t)2 * MT_BS * (d + 8) + 2 * MT_BS) * sizeof(float); }
 
-extern "C" int buctd_mha_train_supported(int T, int d) {
-  return (T > 0 && T % MT_BO == 0 && d >= 16 && d <= 128 && d % 16 == 0) ? 1 : 0;
-}
-
 extern "C" int buctd_mha_heads_train_supported(int T, int h, int dh) {
   return (T > 0 && T % MT_BS == 0 && h >= 1 && h <= 65535 && dh >= 16 && dh <= 128 && dh % 16 == 0) ? 1 : 0;
 }
@@ -396,24 +392,24 @@ static dim3 mt_grid(int B, int h, int T) { return dim3((T + MT_BO - 1) / MT_BO, 
 template <int DF, bool DSEED, bool TAIL>
 static int mt_fwd_launch(int B, int h, const MhaTrainFwdArgs& a, SeedArg<DSEED> seed, hipStream_t st) {
   static unsigned char done[BUCTD_MAX_DEVICES] = {0};
-  const int rc = mt_attr(mha_fwd_train_kernel<DF, DSEED, TAIL>, done, "buctd_mha_fwd_train");
+  const int rc = mt_attr(mha_fwd_train_kernel<DF, DSEED, TAIL>, done, "buctd_mha_heads_fwd_train");
   if (rc) return rc;
   hipLaunchKernelGGL((mha_fwd_train_kernel<DF, DSEED, TAIL>), mt_grid(B, h, a.T), dim3(512), mt_fwd_lds(DF * 16), st, a, seed);
-  BUCTD_CHECK_LAUNCH("buctd_mha_fwd_train");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_fwd_train");
   return BUCTD_OK;
 }
 
 template <int DF, bool DSEED, bool TAIL>
 static int mt_bwd_launch(int B, int h, int T, const SeededArgs<MhaBwdArgs, DSEED>& a, hipStream_t st) {
   static unsigned char done[2][BUCTD_MAX_DEVICES] = {{0}};
-  int rc = mt_attr(mha_bwd_kernel<DF, false, DSEED, TAIL>, done[0], "buctd_mha_bwd");
+  int rc = mt_attr(mha_bwd_kernel<DF, false, DSEED, TAIL>, done[0], "buctd_mha_heads_bwd");
   if (rc) return rc;
-  rc = mt_attr(mha_bwd_kernel<DF, true, DSEED, TAIL>, done[1], "buctd_mha_bwd");
+  rc = mt_attr(mha_bwd_kernel<DF, true, DSEED, TAIL>, done[1], "buctd_mha_heads_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL((mha_bwd_kernel<DF, true, DSEED, TAIL>), mt_grid(B, h, T), dim3(512), mt_bwd_lds(DF * 16), st, a);
-  BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dK, dV)");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_bwd (dK, dV)");
   hipLaunchKernelGGL((mha_bwd_kernel<DF, false, DSEED, TAIL>), mt_grid(B, h, T), dim3(512), mt_bwd_lds(DF * 16), st, a);
-  BUCTD_CHECK_LAUNCH("buctd_mha_bwd (dQ)");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_bwd (dQ)");
   return BUCTD_OK;
 }
 
@@ -422,14 +418,13 @@ static bool mt_strides_ok(const buctd_mha_args& g) {
   return g.ldq >= hd && g.ldk >= hd && g.ldv >= hd && g.ldo >= hd && g.ldq % 4 == 0 && g.ldk % 4 == 0 && g.ldv % 4 == 0;
 }
 
-// the general launchers: the one-head entry points below are their h = 1, ldk = ldq, ldo = lddo = d case
 template <bool DSEED>
 static int mha_fwd_train(const buctd_mha_args& g, SeedArg<DSEED> seed, void* stream) {
   BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.lse && g.B > 0 && g.B <= 65535 && seed_ok(seed),
-                  "buctd_mha_fwd_train: null pointer or bad batch");
-  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_fwd_train: unsupported shape T%d h%d dh%d", g.T,
+                  "buctd_mha_heads_fwd_train: null pointer or bad batch");
+  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_heads_fwd_train: unsupported shape T%d h%d dh%d", g.T,
                   g.h, g.dh);
-  BUCTD_CHECK_ARG(mt_strides_ok(g) && g.p_drop >= 0.f && g.p_drop < 1.f, "buctd_mha_fwd_train: bad strides or dropout probability");
+  BUCTD_CHECK_ARG(mt_strides_ok(g) && g.p_drop >= 0.f && g.p_drop < 1.f, "buctd_mha_heads_fwd_train: bad strides or dropout probability");
   MhaTrainFwdArgs a;
   a.q = g.q; a.k = g.k; a.v = g.v; a.out = g.out; a.lse = g.lse;
   a.T = g.T; a.ldq = g.ldq; a.ldk = g.ldk; a.ldv = g.ldv; a.ldo = g.ldo;
@@ -448,21 +443,21 @@ static int mha_fwd_train(const buctd_mha_args& g, SeedArg<DSEED> seed, void* str
 template <bool DSEED>
 static int mha_bwd(const buctd_mha_args& g, SeedArg<DSEED> seed, void* workspace, size_t workspace_bytes, void* stream) {
   BUCTD_CHECK_ARG(g.q && g.k && g.v && g.out && g.dout && g.lse && g.dq && g.dk && g.dv && g.B > 0 && g.B <= 65535 && seed_ok(seed),
-                  "buctd_mha_bwd: null pointer or bad batch");
-  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_bwd: unsupported shape T%d h%d dh%d", g.T, g.h, g.dh);
+                  "buctd_mha_heads_bwd: null pointer or bad batch");
+  BUCTD_CHECK_ARG(buctd_mha_heads_train_supported(g.T, g.h, g.dh), "buctd_mha_heads_bwd: unsupported shape T%d h%d dh%d", g.T, g.h, g.dh);
   const int hd = g.h * g.dh;
   BUCTD_CHECK_ARG(mt_strides_ok(g) && g.lddo >= hd && g.lddo % 4 == 0 && g.lddq >= hd && g.lddk >= hd && g.lddv >= hd,
-                  "buctd_mha_bwd: bad strides");
+                  "buctd_mha_heads_bwd: bad strides");
   const size_t need = buctd_mha_heads_bwd_workspace(g.B, g.h, g.T);
   if (!workspace || workspace_bytes < need) {
-    buctd_set_error("buctd_mha_bwd: workspace %zu bytes < required %zu", workspace_bytes, need);
+    buctd_set_error("buctd_mha_heads_bwd: workspace %zu bytes < required %zu", workspace_bytes, need);
     return BUCTD_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   const long items = (long)g.B * g.h * g.T;
   hipLaunchKernelGGL(mha_rowdot_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, g.dout, g.lddo, g.out, g.ldo, items,
                      g.T, g.h, g.dh, (float*)workspace);
-  BUCTD_CHECK_LAUNCH("buctd_mha_bwd (row dots)");
+  BUCTD_CHECK_LAUNCH("buctd_mha_heads_bwd (row dots)");
   SeededArgs<MhaBwdArgs, DSEED> args;
   MhaBwdArgs& a = kernel_args(args);
   a.q = g.q; a.k = g.k; a.v = g.v; a.dout = g.dout; a.lse = g.lse; a.dvec = (const float*)workspace;
@@ -486,70 +481,11 @@ static int mha_bwd(const buctd_mha_args& g, SeedArg<DSEED> seed, void* workspace
   return BUCTD_EINVAL;
 }
 
-static int mt_one_head(buctd_mha_args& g, const char* who, int B, int T, int d, const float* q, const float* k, const float* v,
-                       int ldqk, int ldv, float scale, float p_drop, float* out, float* lse) {
-  BUCTD_CHECK_ARG(buctd_mha_train_supported(T, d), "%s: unsupported shape T%d d%d", who, T, d);
-  g = buctd_mha_args{};
-  g.B = B; g.T = T; g.h = 1; g.dh = d;
-  g.q = q; g.k = k; g.v = v; g.ldq = ldqk; g.ldk = ldqk; g.ldv = ldv;
-  g.out = out; g.ldo = d; g.lse = lse; g.scale = scale; g.p_drop = p_drop;
-  return BUCTD_OK;
-}
-
-template <bool DSEED>
-static int mha_fwd_train1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                          float p_drop, SeedArg<DSEED> seed, float* out, float* lse, void* stream) {
-  buctd_mha_args g;
-  if (const int rc = mt_one_head(g, "buctd_mha_fwd_train", B, T, d, q, k, v, ldqk, ldv, scale, p_drop, out, lse)) return rc;
-  return mha_fwd_train<DSEED>(g, seed, stream);
-}
-
-template <bool DSEED>
-static int mha_bwd1(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
-                    const float* dout, const float* lse, float scale, float p_drop, SeedArg<DSEED> seed, float* dq, float* dk,
-                    int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream) {
-  buctd_mha_args g;
-  if (const int rc = mt_one_head(g, "buctd_mha_bwd", B, T, d, q, k, v, ldqk, ldv, scale, p_drop, const_cast<float*>(out),
-                                 const_cast<float*>(lse)))
-    return rc;
-  g.dout = dout; g.lddo = d;
-  g.dq = dq; g.dk = dk; g.dv = dv; g.lddq = lddqk; g.lddk = lddqk; g.lddv = lddv;
-  return mha_bwd<DSEED>(g, seed, workspace, workspace_bytes, stream);
-}
-
-/* softmax(scale q k^T) -> dropout(p_drop, seed) -> . v for one head, fused (no T x T tensor), train mode: also writes the
- * row statistic lse[B][T] the backward needs.  q, k: rows of stride ldqk floats, v: ldv; out: [B][T][d] contiguous.
- * Reference: nn.MultiheadAttention in transpose_h.py:192-197 (forward of the training step). */
-extern "C" int buctd_mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                                   float scale, float p_drop, uint64_t seed, float* out, float* lse, void* stream) {
-  return mha_fwd_train1<false>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
-}
-extern "C" int buctd_mha_fwd_train_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk,
-                                         int ldv, float scale, float p_drop, const uint64_t* seed, float* out, float* lse,
-                                         void* stream) {
-  return mha_fwd_train1<true>(B, T, d, q, k, v, ldqk, ldv, scale, p_drop, seed, out, lse, stream);
-}
-
-/* backward of buctd_mha_fwd_train: dq, dk (rows of stride lddqk), dv (stride lddv) from q, k, v, the forward's out and lse,
- * and dout [B][T][d].  workspace: B * T floats (the row dots dout . out). */
-extern "C" size_t buctd_mha_bwd_workspace(int B, int T) { return (size_t)B * T * sizeof(float); }
+/* The entry points (include/buctd_hip.h: buctd_mha_args).  Forward: softmax(scale q k^T) -> dropout(p_drop, seed) -> . v per
+ * head, fused (no T x T tensor), also writes the row statistic lse the backward needs (reference: nn.MultiheadAttention in
+ * transpose_h.py:192-197, forward of the training step).  Backward: dq, dk, dv from q, k, v, the forward's out and lse, and
+ * dout; workspace: B h T floats (the row dots dout . out).  _dseed: the seed is read from device memory. */
 extern "C" size_t buctd_mha_heads_bwd_workspace(int B, int h, int T) { return (size_t)B * h * T * sizeof(float); }
-extern "C" int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                             const float* out, const float* dout, const float* lse, float scale, float p_drop, uint64_t seed,
-                             float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes,
-                             void* stream) {
-  return mha_bwd1<false>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
-                         workspace_bytes, stream);
-}
-extern "C" int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                                   const float* out, const float* dout, const float* lse, float scale, float p_drop,
-                                   const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-  return mha_bwd1<true>(B, T, d, q, k, v, ldqk, ldv, out, dout, lse, scale, p_drop, seed, dq, dk, lddqk, dv, lddv, workspace,
-                        workspace_bytes, stream);
-}
-
-/* the general form (include/buctd_hip.h: buctd_mha_args) */
 extern "C" int buctd_mha_heads_fwd_train(const buctd_mha_args* a, uint64_t seed, void* stream) {
   BUCTD_CHECK_ARG(a, "buctd_mha_heads_fwd_train: null descriptor");
   return mha_fwd_train<false>(*a, seed, stream);

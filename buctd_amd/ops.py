@@ -2415,33 +2415,20 @@ def mha_fwd(qk, v, scale=None, h=1, k=None):
     Packed form (k=None): qk [B, T, 2d] = q | k side by side (the packed nn.MultiheadAttention input projection), v [B, T, d]
     -> [B, T, d].  Unpacked form: qk = q, k, v [B, T, d] separate tensors (contiguous, or channel slices of wider ones).
     h heads of width d / h; scale defaults to 1 / sqrt(d / h)."""
-    B, T = qk.shape[0], qk.shape[1]
-    d = v.shape[2]
-    if k is not None or h != 1 or lib().buctd_mha_fwd_supported(T, d) != 1:
-        a, keep, B, T, d = _mha_desc(qk, k, v, int(h), scale)
-        out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
-        a.out, a.ldo = ptr(out), d
-        fn = lib().buctd_mha_heads_fwd_bf16x6 if _conv_math["mode"] == "bf16x6" and _MHA_X6 else lib().buctd_mha_heads_fwd
-        check(fn(C.byref(a), stream_ptr()), "mha_fwd")
-        return out
-    _f32(qk, "mha qk")
-    _f32(v, "mha v")
-    two_d = qk.shape[2]
+    a, keep, B, T, d = _mha_desc(qk, k, v, int(h), scale)
     out = torch.empty((B, T, d), dtype=torch.float32, device=qk.device)
-    kptr = C.c_void_p(qk.data_ptr() + 4 * d)
+    a.out, a.ldo = ptr(out), d
     # default math mode: both products in bf16x6 (fp32 class on the bf16 matrix cores); fp32 mode: exact fp32 MFMA
-    sc = (1.0 / math.sqrt(d)) if scale is None else float(scale)
-    if _conv_math["mode"] == "bf16x6" and _MHA_X6:
-        if _MHA_PRESPLIT:       # keys / values split once into the workspace, streamed by DMA (same bits, faster)
-            nb = _memo(("mhaws", B, T, d), lambda: lib().buctd_mha_fwd_bf16x6_workspace(B, T, d))
-            ws = workspace(nb, qk.device)
-            check(lib().buctd_mha_fwd_bf16x6_ws(B, T, d, ptr(qk), kptr, ptr(v), two_d, v.shape[2], sc, ptr(out), None,
-                                                ptr(ws), ws.numel(), stream_ptr()), "mha_fwd")
-            return out
-        fn = lib().buctd_mha_fwd_bf16x6
+    x6 = _conv_math["mode"] == "bf16x6" and _MHA_X6
+    # packed one-head form: keys / values split once into the workspace, streamed by DMA (equal to round-off, faster)
+    nb = _memo(("mhaws", B, T, d), lambda: lib().buctd_mha_fwd_bf16x6_workspace(B, T, d)) \
+        if x6 and _MHA_PRESPLIT and k is None and h == 1 else 0
+    if nb:
+        ws = workspace(nb, qk.device)
+        check(lib().buctd_mha_heads_fwd_bf16x6_ws(C.byref(a), ptr(ws), ws.numel(), stream_ptr()), "mha_fwd")
     else:
-        fn = lib().buctd_mha_fwd
-    check(fn(B, T, d, ptr(qk), kptr, ptr(v), two_d, v.shape[2], sc, ptr(out), None, stream_ptr()), "mha_fwd")
+        fn = lib().buctd_mha_heads_fwd_bf16x6 if x6 else lib().buctd_mha_heads_fwd
+        check(fn(C.byref(a), stream_ptr()), "mha_fwd")
     return out
 
 

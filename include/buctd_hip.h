@@ -623,47 +623,12 @@ int buctd_adam_step(float* p, const float* g, float* m, float* v, long n, float 
 int buctd_sgd_step(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum, float weight_decay,
                    int nesterov, int first_step, float gscale, void* stream);
 
-/* Fused single-head self-attention forward (flash style, exact fp32) - nn.MultiheadAttention of the TransPose encoder
- * layer, transpose_h.py:192-197, in eval mode / without attention dropout: out[b][i] = softmax_j(scale * q_i . k_j) v_j.
- * q, k: [B][T][.] rows of stride ldqk floats (q and k may be the two halves of one packed projection: k = q + d);
- * v: [B][T][.] stride ldv; out: [B][T][d] contiguous; lse (NULL ok): [B][T] log-sum-exp of the scaled logits.
- * T % 128 == 0, d % 16 == 0, d <= 128. */
-int buctd_mha_fwd_supported(int T, int d);
-int buctd_mha_fwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                  float* out, float* lse, void* stream);
-/* the same in the bf16x6 arithmetic of the convolutions (three bf16 pieces per operand, six MFMAs per product, fp32
- * accumulate: fp32 class on the bf16 matrix cores); probabilities stay in registers (S^T formulation). */
-int buctd_mha_fwd_bf16x6(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                         float scale, float* out, float* lse, void* stream);
-/* bf16x6 attention over keys / values split ONCE per call into the workspace (6 B per element, the kernel's LDS tile layout)
- * and streamed into LDS by DMA - same results bit for bit as buctd_mha_fwd_bf16x6 (same pieces, same MFMA order), faster:
- * no per-workgroup re-split, K/V copies overlap the products, one image per XCD L2. */
-size_t buctd_mha_fwd_bf16x6_workspace(int B, int T, int d);
-int buctd_mha_fwd_bf16x6_ws(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                            float scale, float* out, float* lse, void* workspace, size_t workspace_bytes, void* stream);
-/* The same attention for TRAINING (transpose_h.py:168-213, autograd of softmax -> dropout -> . v), fused in both
- * directions - nothing T x T in HBM: forward with in-kernel attention dropout (counter hash keyed by (seed, (b T + q) T + key),
- * the function of buctd_softmax_dropout_fwd) and the row statistic lse [B][T]; flash-style backward (one kernel template in
- * two roles: dK/dV with the keys owned, dQ with the queries owned).  Exact fp32 MFMA.  T % 128 == 0, d % 16 == 0, d <= 128. */
-int buctd_mha_train_supported(int T, int d);
-int buctd_mha_fwd_train(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, float scale,
-                        float p_drop, uint64_t seed, float* out, float* lse, void* stream);
-size_t buctd_mha_bwd_workspace(int B, int T);
-int buctd_mha_bwd(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv, const float* out,
-                  const float* dout, const float* lse, float scale, float p_drop, uint64_t seed, float* dq, float* dk,
-                  int lddqk, float* dv, int lddv, void* workspace, size_t workspace_bytes, void* stream);
-/* device-seed forms (transpose_h.py:192-197 in a captured training step) */
-int buctd_mha_fwd_train_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                              float scale, float p_drop, const uint64_t* seed, float* out, float* lse, void* stream);
-int buctd_mha_bwd_dseed(int B, int T, int d, const float* q, const float* k, const float* v, int ldqk, int ldv,
-                        const float* out, const float* dout, const float* lse, float scale, float p_drop,
-                        const uint64_t* seed, float* dq, float* dk, int lddqk, float* dv, int lddv, void* workspace,
-                        size_t workspace_bytes, void* stream);
-
-/* General calling form of the fused attention above: h heads and q, k, v, out (dq, dk, dv) as separate tensors, each with
- * its own row stride in floats (self_attention.py:74-86 with h heads; nn.MultiheadAttention with N_HEAD > 1).  Head i reads
- * columns [i dh, (i + 1) dh) of q, k, v and writes the same columns of out / dq / dk / dv; lse is [B][h][T].  The packed
- * one-head projection is the special case h = 1, k = q + dh, ldk = ldq.  Attention dropout draws the mask of
+/* Fused self-attention (flash style, nothing T x T in memory) - nn.MultiheadAttention of the TransPose encoder layer
+ * (transpose_h.py:168-213) and the CoAM attention cores (self_attention.py:74-86):
+ *     out[b][i] = sum_j dropout(softmax_j(scale * q_i . k_j)) v_j   per head.
+ * One calling form, the descriptor: h heads and q, k, v, out (dq, dk, dv) as separate tensors, each with its own row stride
+ * in floats.  Head i reads columns [i dh, (i + 1) dh) of q, k, v and writes the same columns of out / dq / dk / dv; lse is
+ * [B][h][T].  A packed one-head projection q | k is h = 1, k = q + dh, ldk = ldq.  Attention dropout draws the mask of
  * buctd_softmax_dropout_fwd on a [B][h][T][T] tensor: counter ((b h + head) T + query) T + key.
  * T % 64 == 0 (a last half block of query / key rows is masked), dh % 16 == 0, dh <= 128, Tq == Tk, dk == dv.
  * Every pointer 16-byte aligned, ldq / ldk / ldv / lddo multiples of 4.  Fields a pass does not use may be NULL / 0. */
@@ -678,9 +643,23 @@ typedef struct buctd_mha_args {
   float* dq; float* dk; float* dv;
   int lddq, lddk, lddv;
 } buctd_mha_args;
+/* eval / no dropout.  buctd_mha_heads_fwd: exact fp32 MFMA.  _bf16x6: the bf16x6 arithmetic of the convolutions (three bf16
+ * pieces per operand, six MFMAs per product, fp32 accumulate: fp32 class on the bf16 matrix cores); probabilities stay in
+ * registers (S^T formulation). */
 int buctd_mha_heads_fwd_supported(int T, int h, int dh);
-int buctd_mha_heads_fwd(const buctd_mha_args* a, void* stream);         /* exact fp32 MFMA */
-int buctd_mha_heads_fwd_bf16x6(const buctd_mha_args* a, void* stream);  /* bf16x6, as buctd_mha_fwd_bf16x6 */
+int buctd_mha_heads_fwd(const buctd_mha_args* a, void* stream);
+int buctd_mha_heads_fwd_bf16x6(const buctd_mha_args* a, void* stream);
+/* bf16x6 attention over keys / values split ONCE per call into the workspace (6 B per element, the kernel's LDS tile layout)
+ * and streamed into LDS by DMA: no per-workgroup re-split, K/V copies overlap the products, one image per XCD L2.  The same
+ * pieces and products as buctd_mha_heads_fwd_bf16x6 with another association of the online soft-max (32-key tiles, the key
+ * range in two halves that are merged): equal to fp32 round-off, not bit for bit.
+ * Covers h == 1, T % 128 == 0, dh % 16 == 0, dh <= 128, ldo == dh, lse (NULL ok) [B][1][T]; ldk may differ from ldq.
+ * buctd_mha_fwd_bf16x6_workspace(B, T, d): the bytes needed, 0 for a shape (T, d) this path does not cover. */
+size_t buctd_mha_fwd_bf16x6_workspace(int B, int T, int d);
+int buctd_mha_heads_fwd_bf16x6_ws(const buctd_mha_args* a, void* workspace, size_t workspace_bytes, void* stream);
+/* TRAINING (autograd of softmax -> dropout -> . v), fused in both directions: forward with in-kernel attention dropout and
+ * the row statistic lse; flash-style backward (one kernel template in two roles: dK/dV with the keys owned, dQ with the
+ * queries owned).  Exact fp32 MFMA.  _dseed: the seed is read from device memory (a captured training step). */
 int buctd_mha_heads_train_supported(int T, int h, int dh);
 int buctd_mha_heads_fwd_train(const buctd_mha_args* a, uint64_t seed, void* stream);
 size_t buctd_mha_heads_bwd_workspace(int B, int h, int T);              /* B h T floats: the row dots dout . out */

@@ -1,6 +1,7 @@
 """CoAM attention cores: ops.PositionAttention / ops.ChannelAttention (batched MFMA matmuls + fused softmax) against
 the formulas of reference lib/models/self_attention.py:74-87 and 146-159 evaluated in fp64 on the CPU.
 Bar: forward and all gradients within 2e-5 relative (fp32 round-off through a softmax)."""
+import ctypes as C
 import math
 
 import pytest
@@ -100,10 +101,11 @@ def test_fused_mha_forward_vs_fp64(dev, B, T, d, mode):
 
 @pytest.mark.parametrize("B,T,d", [(8, 384, 112), (16, 128, 48), (3, 256, 16), (1, 3072, 112), (2, 256, 128)])
 def test_fused_mha_presplit_matches_the_in_kernel_split(dev, B, T, d, monkeypatch):
-    """buctd_mha_fwd_bf16x6_ws (keys / values split once into the workspace, DMA-staged tiles, 32 queries per wavefront,
-    the key range split over the two wave quartets and merged, one image per XCD - B a multiple of 8 takes the XCD-aware
-    workgroup map, other B the plain one) against buctd_mha_fwd_bf16x6: the same exact pieces and products, a different
-    association of the online soft-max (32-key tiles, two halves merged) -> equal to fp32 round-off, and as close to fp64.
+    """buctd_mha_heads_fwd_bf16x6_ws (keys / values split once into the workspace, DMA-staged tiles, 32 queries per
+    wavefront, the key range split over the two wave quartets and merged, one image per XCD - B a multiple of 8 takes the
+    XCD-aware workgroup map, other B the plain one) against buctd_mha_heads_fwd_bf16x6: the same exact pieces and products, a
+    different association of the online soft-max (32-key tiles, two halves merged) -> equal to fp32 round-off, and as close
+    to fp64.  The entry refuses what the kernel does not cover (several heads, T % 128 != 0) before anything is launched.
     The workspace is dirtied first: pad bytes of the image rows are never read."""
     from buctd_amd import ops
     g = torch.Generator().manual_seed(B * T + d + 5)
@@ -126,12 +128,24 @@ def test_fused_mha_presplit_matches_the_in_kernel_split(dev, B, T, d, monkeypatc
     lse = torch.empty(B, T, device=dev)
     ws = ops.workspace(ops.lib().buctd_mha_fwd_bf16x6_workspace(B, T, d), dev)
     out2 = torch.empty_like(out)
-    ops.check(ops.lib().buctd_mha_fwd_bf16x6_ws(B, T, d, ops.ptr(qk), qk.data_ptr() + 4 * d, ops.ptr(v), 2 * d, d,
-                                                1.0 / math.sqrt(d), ops.ptr(out2), ops.ptr(lse), ops.ptr(ws), ws.numel(),
-                                                ops.stream_ptr()), "mha_fwd_ws")
+    from buctd_amd._C import MhaArgs
+
+    def desc(T_, h, dh):
+        a = MhaArgs()
+        a.B, a.T, a.h, a.dh = B, T_, h, dh
+        a.q, a.k, a.v, a.ldq, a.ldk, a.ldv = ops.ptr(qk), qk.data_ptr() + 4 * d, ops.ptr(v), 2 * d, 2 * d, d
+        a.out, a.ldo, a.lse, a.scale = ops.ptr(out2), h * dh, ops.ptr(lse), 1.0 / math.sqrt(d)
+        return a
+
+    entry = ops.lib().buctd_mha_heads_fwd_bf16x6_ws
+    ops.check(entry(C.byref(desc(T, 1, d)), ops.ptr(ws), ws.numel(), ops.stream_ptr()), "mha_fwd_ws")
     l64 = torch.logsumexp(qk[..., :d].double() @ qk[..., d:].double().transpose(1, 2) / math.sqrt(d), dim=-1)
     assert torch.equal(out2, out) and (lse.double() - l64).abs().max().item() <= 1e-4
     assert ops.lib().buctd_mha_fwd_bf16x6_workspace(B, 100, d) == 0
+    for bad in (desc(T, 2, d), desc(192, 1, d)):               # refused: nothing is launched, out2 stays as it is
+        assert entry(C.byref(bad), ops.ptr(ws), ws.numel(), ops.stream_ptr()) != 0
+        assert b"buctd_mha_heads_fwd_bf16x6_ws: unsupported shape" in ops.lib().buctd_last_error()
+    assert torch.equal(out2, out)
 
 
 @pytest.mark.parametrize("B,T,d", [(2, 384, 48), (1, 3072, 112), (3, 128, 16), (2, 256, 128)])

@@ -185,9 +185,9 @@ def _args(ops, B, T, h, dh, q, k, v, ldq, ldk, ldv, out, lse, p=0.0):
 
 
 @pytest.mark.parametrize("B,T,d", [(2, 384, 48), (1, 3072, 112), (3, 128, 16), (2, 256, 128), (2, 256, 96)])
-def test_one_head_entry_points_are_the_general_form_bit_for_bit(dev, B, T, d):
-    """the shapes of the one-head tests: buctd_mha_fwd / _bf16x6 / _fwd_train / _bwd against the general entry points with
-    h = 1, k = q + d - out, lse, dq, dk, dv identical bit for bit (with dropout on in the training pair)"""
+def test_host_ops_reach_the_general_entry_points(dev, B, T, d, monkeypatch):
+    """packed one-head ops.FusedMHA (dropout on) and ops.mha_fwd (in-kernel split, both math modes) are the general entry
+    points with h = 1, k = q + d: out, d(q | k), dv identical bit for bit"""
     from buctd_amd import ops
     lib, sp = ops.lib(), ops.stream_ptr
     g = torch.Generator().manual_seed(B * T + d)
@@ -195,35 +195,57 @@ def test_one_head_entry_points_are_the_general_form_bit_for_bit(dev, B, T, d):
     v = torch.randn(B, T, d, generator=g).to(dev)
     dout = torch.randn(B, T, d, generator=g).to(dev)
     qp, kp, vp = qk.data_ptr(), qk.data_ptr() + 4 * d, v.data_ptr()
-    sc, p, seed = 1.0 / math.sqrt(d), 0.2, 0xABCDEF12345
+    p, seed = 0.2, 0xABCDEF12345
     new = lambda *s: torch.empty(*s, device=dev)
-    for old_fn, gen_fn in ((lib.buctd_mha_fwd, lib.buctd_mha_heads_fwd), (lib.buctd_mha_fwd_bf16x6, lib.buctd_mha_heads_fwd_bf16x6)):
-        o0, l0, o1, l1 = new(B, T, d), new(B, T), new(B, T, d), new(B, 1, T)
-        ops.check(old_fn(B, T, d, qp, kp, vp, 2 * d, d, sc, o0.data_ptr(), l0.data_ptr(), sp()), "old")
-        ops.check(gen_fn(ctypes.byref(_args(ops, B, T, 1, d, qp, kp, vp, 2 * d, 2 * d, d, o1, l1)), sp()), "general")
-        assert torch.equal(o0, o1) and torch.equal(l0, l1.view(B, T))
-    o0, l0, o1, l1 = new(B, T, d), new(B, T), new(B, T, d), new(B, 1, T)
-    ops.check(lib.buctd_mha_fwd_train(B, T, d, qp, kp, vp, 2 * d, d, sc, p, seed, o0.data_ptr(), l0.data_ptr(), sp()), "old")
+    o1, l1 = new(B, T, d), new(B, 1, T)
     a = _args(ops, B, T, 1, d, qp, kp, vp, 2 * d, 2 * d, d, o1, l1, p)
     ops.check(lib.buctd_mha_heads_fwd_train(ctypes.byref(a), seed, sp()), "general")
-    assert torch.equal(o0, o1) and torch.equal(l0, l1.view(B, T))
-    g0, dv0, g1, dv1 = new(B, T, 2 * d), new(B, T, d), new(B, T, 2 * d), new(B, T, d)
-    ws = ops.workspace(lib.buctd_mha_bwd_workspace(B, T), qk.device)
-    ops.check(lib.buctd_mha_bwd(B, T, d, qp, kp, vp, 2 * d, d, o0.data_ptr(), dout.data_ptr(), l0.data_ptr(), sc, p, seed,
-                                g0.data_ptr(), g0.data_ptr() + 4 * d, 2 * d, dv0.data_ptr(), d, ws.data_ptr(), ws.numel(), sp()),
-              "old")
+    g1, dv1 = new(B, T, 2 * d), new(B, T, d)
+    ws = ops.workspace(lib.buctd_mha_heads_bwd_workspace(B, 1, T), qk.device)
     a.dout, a.lddo = dout.data_ptr(), d
     a.dq, a.dk, a.dv, a.lddq, a.lddk, a.lddv = g1.data_ptr(), g1.data_ptr() + 4 * d, dv1.data_ptr(), 2 * d, 2 * d, d
-    assert lib.buctd_mha_heads_bwd_workspace(B, 1, T) == lib.buctd_mha_bwd_workspace(B, T)
     ops.check(lib.buctd_mha_heads_bwd(ctypes.byref(a), seed, ws.data_ptr(), ws.numel(), sp()), "general")
-    assert torch.equal(g0, g1) and torch.equal(dv0, dv1)
-    # and the host op reaches them: packed one-head FusedMHA == the old entry points
     ql, vl = qk.clone().requires_grad_(True), v.clone().requires_grad_(True)
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(ops, "next_seed", lambda: seed)
         out = ops.FusedMHA.apply(ql, vl, p, True)
         out.backward(dout)
-    assert torch.equal(out.detach(), o0) and torch.equal(ql.grad, g0) and torch.equal(vl.grad, dv0)
+    assert torch.equal(out.detach(), o1) and torch.equal(ql.grad, g1) and torch.equal(vl.grad, dv1)
+    # eval
+    monkeypatch.setattr(ops, "_MHA_PRESPLIT", False)
+    old = ops.get_conv_math()
+    for mode, gen_fn in (("bf16x6", lib.buctd_mha_heads_fwd_bf16x6), ("fp32", lib.buctd_mha_heads_fwd)):
+        o2 = new(B, T, d)
+        ops.check(gen_fn(ctypes.byref(_args(ops, B, T, 1, d, qp, kp, vp, 2 * d, 2 * d, d, o2, None)), sp()), "general")
+        ops.set_conv_math(mode)
+        try:
+            out = ops.mha_fwd(qk, v)
+        finally:
+            ops.set_conv_math(old)
+        assert torch.equal(out, o2), mode
+
+
+@pytest.mark.parametrize("T,h,layout,presplit", [(128, 1, "packed", True), (192, 1, "packed", False), (128, 1, "views", False),
+                                                 (128, 2, "packed", False)])
+def test_only_the_packed_one_head_form_takes_the_presplit_kernel(dev, T, h, layout, presplit, monkeypatch):
+    """which C entry ops.mha_fwd calls in the default (bf16x6) mode: the pre-split kernel for the packed one-head form in
+    whole 128-query tiles, the in-kernel split for everything else - the smallest shape on each side of every condition"""
+    from buctd_amd import ops
+    lib = ops.lib()
+    calls = {}
+    for name in ("buctd_mha_heads_fwd_bf16x6_ws", "buctd_mha_heads_fwd_bf16x6", "buctd_mha_heads_fwd"):
+        def wrapped(*a, _n=name, _fn=getattr(lib, name)):
+            calls[_n] = calls.get(_n, 0) + 1
+            return _fn(*a)
+        monkeypatch.setattr(lib, name, wrapped)
+    assert ops.get_conv_math() == "bf16x6" and ops._MHA_X6 and ops._MHA_PRESPLIT
+    B, dh = 2, 16
+    q, k, v = _operands(B, T, h, dh, layout, dev, T + h)
+    out = ops.mha_fwd(q, v, h=h, k=k)
+    assert calls == {"buctd_mha_heads_fwd_bf16x6_ws" if presplit else "buctd_mha_heads_fwd_bf16x6": 1}, calls
+    q64, k64 = (q[..., :h * dh], q[..., h * dh:]) if k is None else (q, k)
+    err = _e(out, _ref64(q64, k64, v, h))
+    assert err <= BAR, err
 
 
 # ---------------------------------------------------------------------------------------------------------- models ----

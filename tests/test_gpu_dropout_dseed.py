@@ -58,7 +58,7 @@ def test_elementwise_dropout_dseed_equals_value_seed(dev):
 def test_fused_mha_dseed_equals_value_seed(dev):
     import ctypes as C
     from buctd_amd import ops
-    from buctd_amd._C import lib, check
+    from buctd_amd._C import MhaArgs, lib, check
     B, T, d = 2, 256, 32
     g = torch.Generator().manual_seed(3)
     qk = torch.randn(B, T, 2 * d, generator=g).to(dev)
@@ -68,19 +68,22 @@ def test_fused_mha_dseed_equals_value_seed(dev):
     scale, p = 1.0 / math.sqrt(d), 0.1
     res = []
     for dseed in (False, True):
-        fwd = lib().buctd_mha_fwd_train_dseed if dseed else lib().buctd_mha_fwd_train
-        bwd = lib().buctd_mha_bwd_dseed if dseed else lib().buctd_mha_bwd
+        fwd = lib().buctd_mha_heads_fwd_train_dseed if dseed else lib().buctd_mha_heads_fwd_train
+        bwd = lib().buctd_mha_heads_bwd_dseed if dseed else lib().buctd_mha_heads_bwd
         s = table.data_ptr() if dseed else SEED
         out = torch.empty(B, T, d, device=dev)
         lse = torch.empty(B, T, device=dev)
-        check(fwd(B, T, d, qk.data_ptr(), C.c_void_p(qk.data_ptr() + 4 * d), v.data_ptr(), 2 * d, d, scale, p, s,
-                  out.data_ptr(), lse.data_ptr(), _stream()), "mha_fwd_train")
+        a = MhaArgs()                      # one head, packed: k = q + d
+        a.B, a.T, a.h, a.dh = B, T, 1, d
+        a.q, a.k, a.v, a.ldq, a.ldk, a.ldv = qk.data_ptr(), qk.data_ptr() + 4 * d, v.data_ptr(), 2 * d, 2 * d, d
+        a.out, a.ldo, a.lse, a.scale, a.p_drop = out.data_ptr(), d, lse.data_ptr(), scale, p
+        check(fwd(C.byref(a), s, _stream()), "mha_fwd_train")
         dqk = torch.empty_like(qk)
         dv = torch.empty_like(v)
-        ws = ops.workspace(lib().buctd_mha_bwd_workspace(B, T), dev)
-        check(bwd(B, T, d, qk.data_ptr(), C.c_void_p(qk.data_ptr() + 4 * d), v.data_ptr(), 2 * d, d, out.data_ptr(),
-                  dout.data_ptr(), lse.data_ptr(), scale, p, s, dqk.data_ptr(), C.c_void_p(dqk.data_ptr() + 4 * d), 2 * d,
-                  dv.data_ptr(), d, ws.data_ptr(), ws.numel(), _stream()), "mha_bwd")
+        ws = ops.workspace(lib().buctd_mha_heads_bwd_workspace(B, 1, T), dev)
+        a.dout, a.lddo = dout.data_ptr(), d
+        a.dq, a.dk, a.dv, a.lddq, a.lddk, a.lddv = dqk.data_ptr(), dqk.data_ptr() + 4 * d, dv.data_ptr(), 2 * d, 2 * d, d
+        check(bwd(C.byref(a), s, ws.data_ptr(), ws.numel(), _stream()), "mha_bwd")
         res.append((out, lse, dqk, dv))
     for a, b in zip(*res):
         assert torch.equal(a, b)

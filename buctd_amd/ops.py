@@ -13,6 +13,7 @@ autograd, so no AccumulateGrad add kernels run.
 """
 import ctypes as C
 import math
+import weakref
 
 import torch
 
@@ -419,6 +420,26 @@ def _memo(key, fn):
     return v
 
 
+def _dkey(d):
+    """A ConvDesc as part of a _memo key."""
+    return d.N, d.H, d.W, d.Ci, d.Co, d.R, d.S, d.stride, d.pad
+
+
+def _stats_buffers(key, query, Cn, device, counts=False):
+    """Where a kernel puts the BatchNorm partial sums of its Cn output channels: (part, info) with part [ngroups, Cn, 2] and
+    info = (ngroups, rows_per_group[, counts]) as bn_finalize takes it.  query(ngroups*, rows_per_group*) is the kernel's
+    *_stats_groups entry point, asked once per key; counts: the kernel also writes the valid rows of every group."""
+    def ask():
+        ng, rpg = C.c_int(), C.c_int()
+        check(query(C.byref(ng), C.byref(rpg)), "stats_groups")
+        return ng.value, rpg.value
+    ng, rpg = _memo(key, ask)
+    part = torch.empty((ng, Cn, 2), dtype=torch.float32, device=device)
+    if counts:
+        return part, (ng, rpg, torch.empty(ng, dtype=torch.int32, device=device))
+    return part, (ng, rpg)
+
+
 _CONV_MATH_MODES = ("fp32", "bf16x6", "bf16x3")
 _conv_math = {"mode": "bf16x6"}
 
@@ -456,10 +477,12 @@ def _bf16x3_ok(d):
 
 
 _weights_epoch = {"n": 0}
-# After an optimizer step every prepared filter image of the model is rebuilt by ONE launch on the stream of the step
-# (refresh_prepared, called by FusedAdam) instead of ~430 small launches in front of the convolutions that need them:
-# off the critical path of the next forward / backward, 430 launches less per step.
-_prep_registry = {"weights": [], "table": None, "table_key": None, "event": None, "stream": None, "waited": set()}
+# After an optimizer step every prepared filter image of the model is rebuilt by ONE launch per image family on the stream
+# of the step (refresh_prepared, called by FusedAdam) instead of ~430 small launches in front of the convolutions that need
+# them: off the critical path of the next forward / backward, 430 launches less per step.
+_prep_registry = {"weights": [], "c3_table": None, "c3_key": None, "gc_table": None, "gc_key": None,
+                  "event": None, "stream": None, "waited": set()}
+_derived_rebuilds = {"n": 0}
 
 
 def weights_epoch():
@@ -473,9 +496,74 @@ def weights_updated():
 
 
 def refresh_prepared(device):
-    """Rebuild all registered prepared filter images now (one launch on the current stream)."""
+    """Rebuild all registered prepared filter images now (one launch per family on the current stream)."""
     if _conv_math["mode"] != "fp32":
         _prep_all(device)
+
+
+def derived_rebuilds():
+    """Counts the derived tensors (weight images, eval BatchNorm folds) built anew: the addresses a captured graph may have
+    baked in and that went stale.  A batched refresh rewrites images in place and does not count."""
+    return _derived_rebuilds["n"]
+
+
+def _produced_here(device):
+    """(event, stream handle, streams that already waited) of what was just enqueued on the current stream."""
+    return _new_event(), torch.cuda.current_stream(device).cuda_stream, set()
+
+
+def _wait_once(device, ev, stream, waited):
+    """Produced on another stream: order the current stream behind the producing event, once per stream."""
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream != stream and cur.cuda_stream not in waited:
+        _wait_event(cur, ev)
+        waited.add(cur.cuda_stream)
+
+
+def _rewritten_in_place(old, new):
+    """Same storage, tensor version and math mode, other optimizer epoch: the values changed through raw pointers."""
+    return old[:2] == new[:2] and old[3] == new[3] and old[2] != new[2]
+
+
+class _Derived:
+    """The images that kernels consume in place of one parameter tensor, kept on it as w._buctd_derived while
+    key = (data_ptr, _version, weights_epoch, conv-math mode) holds (the 3x3 image depends on the mode; the other two
+    families exist only in bf16x6).  slots[slot] = (image, None or _produced_here()); the families' slots cannot collide:
+      "c3", flip 0 / 1: 3x3 / stride-1 stage image;  "gc", (kind, direction): gathered-convolution image;
+      "x6", "n" / "t": bf16x6 GEMM image of a Linear weight / of its transpose.
+    Stream rule.  "x6": an event is recorded where the image is built and every other stream waits on it once.
+    "c3", "gc": the weight is registered for the batched refresh (_prep_all), which records one event, and every other stream
+    waits once on the latest refresh (_prep_wait).  An image of theirs that is built lazily - first use, version bump, new
+    storage - records NO event: it relies on its layer always running on the stream that built it or behind a join with it."""
+    key, registered = None, False
+
+    @staticmethod
+    def get(w, family, slot, build):
+        key = (w.data_ptr(), w._version, _weights_epoch["n"], _conv_math["mode"])
+        d = getattr(w, "_buctd_derived", None)
+        batched = family != "x6"
+        if d is None or d.key != key:
+            if d is not None and batched and _rewritten_in_place(d.key, key):
+                _prep_all(w.device)       # by the optimizer kernel: batch-refresh every registered image, this one included
+            if d is None or d.key != key:
+                d = d or _Derived()
+                d.key, d.slots = key, {}
+                try:
+                    w._buctd_derived = d
+                    if batched and not d.registered:      # one registry entry per weight, however often its key changes
+                        _prep_registry["weights"].append(weakref.ref(w))
+                        d.registered = True
+                except (AttributeError, RuntimeError, TypeError):
+                    pass                  # takes no attributes: an image per call, outside the batched refresh
+        img = d.slots.get(slot)
+        if img is None:
+            _derived_rebuilds["n"] += 1
+            img = d.slots[slot] = (build(), None if batched else _produced_here(w.device))
+        if batched:
+            _prep_wait(w.device)
+        else:
+            _wait_once(w.device, *img[1])
+        return img[0]
 
 
 class _PrepItem(C.Structure):
@@ -483,51 +571,68 @@ class _PrepItem(C.Structure):
                 ("reserved", C.c_int), ("piece_begin", C.c_long)]
 
 
+def _c3_pieces(img, mode):
+    """include/buctd_hip.h: "an item has steps * Nc * 8 pieces (= prep_bytes / 16 for bf16x3, / 24 for bf16x6)"."""
+    return img.numel() // (24 if mode == "bf16x6" else 16)
+
+
+def _c3_table(items):
+    return bytes((_PrepItem * len(items))(*[_PrepItem(*it) for it in items]))
+
+
+def _gc_table(items):
+    isz = int(lib().buctd_gconv_x6_prep_item_bytes())
+    buf = C.create_string_buffer(isz * len(items))
+    for i, (kind, Ci, Co, wptr, direction, iptr) in enumerate(items):
+        check(lib().buctd_gconv_x6_prep_item(kind, Ci, Co, C.c_void_p(wptr), direction, C.c_void_p(iptr),
+                                             C.c_void_p(C.addressof(buf) + i * isz)), "gconv_x6_prep_item")
+    return buf.raw
+
+
+def _device_table(name, items, to_bytes, device):
+    """The launch table of one batched kernel on the device, rebuilt only when its items change."""
+    key = tuple(items)
+    if _prep_registry[name + "_key"] != key:
+        _prep_registry[name + "_table"] = torch.frombuffer(bytearray(to_bytes(items)), dtype=torch.uint8).to(device)
+        _prep_registry[name + "_key"] = key
+    return ptr(_prep_registry[name + "_table"])
+
+
 def _prep_all(device):
-    """Refresh every registered prepared image whose filter was rewritten in place (same storage, new epoch) with ONE
-    launch instead of one per filter and direction (~430 per CoAM-W48 train step)."""
-    epoch = _weights_epoch["n"]
-    mode = _conv_math["mode"]
-    np_pieces = 3 if mode == "bf16x6" else 2
-    unit = 24 if np_pieces == 3 else 16          # image bytes per piece of the batched kernel
-    items, live, total = [], [], 0
+    """Refresh every registered image whose filter was rewritten in place (same storage, new epoch) with ONE launch per
+    family instead of one per filter and direction (~430 per CoAM-W48 train step)."""
+    epoch, mode = _weights_epoch["n"], _conv_math["mode"]
+    c3, gc, live, total = [], [], [], 0
     for ref in _prep_registry["weights"]:
         w = ref()
-        if w is None or not w.is_cuda or w.device != device:
-            continue
-        cache = getattr(w, "_buctd_prep", None)
-        if cache is None or cache[0][0] != w.data_ptr():
+        if w is None:
             continue
         live.append(ref)
-        if cache[0] == (w.data_ptr(), w._version, epoch, mode) or cache[0][3] != mode:
-            continue
-        Co, Ci = _wshape(w)[0], _wshape(w)[1]
-        for flip in (0, 1):
-            img = cache[1 + flip]
-            if img is None:
-                continue
-            items.append((w.data_ptr(), img.data_ptr(), Ci, Co, flip, np_pieces, total))
-            total += img.numel() // unit
-        cache[0] = (w.data_ptr(), w._version, epoch, mode)
+        d, key = w._buctd_derived, (w.data_ptr(), w._version, epoch, mode)
+        if not w.is_cuda or w.device != device or d.key == key or (d.key[0], d.key[3]) != (key[0], mode):
+            continue                      # current, or new storage / other mode: rebuilt lazily on its next use
+        Co, Ci = _wshape(w)[:2]
+        for slot, (img, _) in list(d.slots.items()):
+            if slot in (0, 1):
+                c3.append((w.data_ptr(), img.data_ptr(), Ci, Co, slot, 3 if mode == "bf16x6" else 2, total))
+                total += _c3_pieces(img, mode)
+            elif type(slot) is tuple:
+                gc.append((slot[0], Ci, Co, w.data_ptr(), slot[1], img.data_ptr()))
+            else:
+                del d.slots[slot]         # a Linear image of the same tensor has no batched kernel: rebuilt on its next use
+        d.key = key
     _prep_registry["weights"] = live
-    launched = False
-    if items:
-        key = tuple(items)
-        if _prep_registry["table_key"] != key:
-            arr = (_PrepItem * len(items))(*[_PrepItem(*it) for it in items])
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            _prep_registry["table"] = host.to(device)
-            _prep_registry["table_key"] = key
-        check(lib().buctd_conv3x3_bf16x3_prep_batched(ptr(_prep_registry["table"]), len(items), total, stream_ptr()),
-              "conv3x3 prep_batched")
-        launched = True
-    launched = _gprep_all(device, epoch) or launched
-    if not launched:
-        return
-    ev = torch.cuda.Event()
-    ev.record()
-    _prep_registry["event"], _prep_registry["stream"] = ev, torch.cuda.current_stream(device).cuda_stream
-    _prep_registry["waited"] = set()
+    if c3:
+        check(lib().buctd_conv3x3_bf16x3_prep_batched(_device_table("c3", c3, _c3_table, device), len(c3), total,
+                                                      stream_ptr()), "conv3x3 prep_batched")
+    if gc:
+        check(lib().buctd_gconv_x6_prep_batched(_device_table("gc", gc, _gc_table, device), len(gc), stream_ptr()),
+              "gconv_x6_prep_batched")
+    if c3 or gc:
+        ev = torch.cuda.Event()
+        ev.record()
+        _prep_registry["event"], _prep_registry["stream"] = ev, torch.cuda.current_stream(device).cuda_stream
+        _prep_registry["waited"] = set()
 
 
 def _prep_wait(device):
@@ -540,72 +645,14 @@ def _prep_wait(device):
             _prep_registry["waited"].add(cur)
 
 
-_gprep_registry = {"weights": [], "table": None, "table_key": None}
-
-
-def _gprep_all(device, epoch):
-    """The gathered-convolution images (csrc/conv_gather_x6.hip) of every registered filter in ONE launch; True if launched."""
-    if _conv_math["mode"] != "bf16x6":
-        return False
-    items, live = [], []
-    for ref in _gprep_registry["weights"]:
-        w = ref()
-        if w is None or not w.is_cuda or w.device != device:
-            continue
-        cache = getattr(w, "_buctd_gprep", None)
-        if cache is None or cache[0][0] != w.data_ptr():
-            continue
-        live.append(ref)
-        if cache[0] == (w.data_ptr(), w._version, epoch):
-            continue
-        Co, Ci = _wshape(w)[0], _wshape(w)[1]
-        for direction in (0, 1):
-            img = cache[2 + direction]
-            if img is not None:
-                items.append((cache[1], Ci, Co, w.data_ptr(), direction, img.data_ptr()))
-        cache[0] = (w.data_ptr(), w._version, epoch)
-    _gprep_registry["weights"] = live
-    if not items:
-        return False
-    key = tuple(items)
-    if _gprep_registry["table_key"] != key:
-        isz = int(lib().buctd_gconv_x6_prep_item_bytes())
-        buf = C.create_string_buffer(isz * len(items))
-        base = C.addressof(buf)
-        for i, (kind, Ci, Co, wptr, direction, iptr) in enumerate(items):
-            check(lib().buctd_gconv_x6_prep_item(kind, Ci, Co, C.c_void_p(wptr), direction, C.c_void_p(iptr),
-                                                 C.c_void_p(base + i * isz)), "gconv_x6_prep_item")
-        _gprep_registry["table"] = torch.frombuffer(bytearray(buf.raw), dtype=torch.uint8).to(device)
-        _gprep_registry["table_key"] = key
-    check(lib().buctd_gconv_x6_prep_batched(ptr(_gprep_registry["table"]), len(items), stream_ptr()), "gconv_x6_prep_batched")
-    return True
-
-
 def _conv3x3_prepared(w, flip):
     """bf16 hi|lo stage image of a 3x3 filter (conv3x3.hip), cached on the weight tensor until it changes."""
-    import weakref
-    Co, Ci = _wshape(w)[0], _wshape(w)[1]
-    epoch = _weights_epoch["n"]
-    key = (w.data_ptr(), w._version, epoch, _conv_math["mode"])
-    cache = getattr(w, "_buctd_prep", None)
-    if cache is not None and cache[0] != key and cache[0][:2] == key[:2] and cache[0][3:] == key[3:]:
-        _prep_all(w.device)       # rewritten in place by the optimizer kernel: batch-refresh all registered images
-    if cache is None or cache[0] != key:
-        first = cache is None
-        cache = [key, None, None]
-        try:
-            w._buctd_prep = cache
-            if first:
-                _prep_registry["weights"].append(weakref.ref(w))
-        except (AttributeError, RuntimeError, TypeError):
-            pass
-    if cache[1 + flip] is None:
-        nbytes = _c3fn("_prep_bytes")(Ci, Co, flip)
-        img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    def build():
+        Co, Ci = _wshape(w)[:2]
+        img = torch.empty(_c3fn("_prep_bytes")(Ci, Co, flip), dtype=torch.uint8, device=w.device)
         check(_c3fn("_prep")(Ci, Co, ptr(w), flip, ptr(img), stream_ptr()), "conv3x3 prep")
-        cache[1 + flip] = img
-    _prep_wait(w.device)
-    return cache[1 + flip]
+        return img
+    return _Derived.get(w, "c3", flip, build)
 
 
 def _conv3x3_bf16x3(x, w, flip, cin, cout, bias, scale, shift, residual, relu, stats, in_bn=None):
@@ -631,14 +678,9 @@ def _conv3x3_bf16x3(x, w, flip, cin, cout, bias, scale, shift, residual, relu, s
     if isinstance(in_bn, BnAccInput):
         raise _C.BuctdHipError("conv3x3: BnAccInput needs the bf16x6 accumulator path (no bias / eval scale)")
     if stats:
-        def groups():
-            ng, rpg = C.c_int(), C.c_int()
-            check(_c3fn("_stats_groups")(N, H, W, cin, cout, C.byref(ng), C.byref(rpg)), "conv3x3 groups")
-            return ng.value, rpg.value
-        ngv, rpgv = _memo(("c3grp", _conv_math["mode"], N, H, W, cin, cout), groups)
-        part = torch.empty((ngv, cout, 2), dtype=torch.float32, device=x.device)
-        counts = torch.empty(ngv, dtype=torch.int32, device=x.device)
-        info = (ngv, rpgv, counts)
+        part, info = _stats_buffers(("c3grp", _conv_math["mode"], N, H, W, cin, cout),
+                                    lambda ng, rpg: _c3fn("_stats_groups")(N, H, W, cin, cout, ng, rpg), cout, x.device, True)
+        counts = info[2]
     if in_bn is not None:
         mean, invstd, gamma, beta, in_relu = in_bn
         check(lib().buctd_conv3x3_bf16x6_bnin(N, H, W, cin, cout, ptr(x), ptr(wp), ptr(bias), ptr(scale), ptr(shift),
@@ -676,28 +718,13 @@ def _gconv_ok(d, direction):
 def _gconv_prepared(w, kind, direction):
     """weight image of the gathered kernels, cached on the weight tensor until it changes; filters rewritten in place by
     the optimizer kernel are refreshed together by _prep_all (one launch per step)."""
-    import weakref
-    Co, Ci = _wshape(w)[0], _wshape(w)[1]
-    key = (w.data_ptr(), w._version, _weights_epoch["n"])
-    cache = getattr(w, "_buctd_gprep", None)
-    if cache is not None and cache[0] != key and cache[0][:2] == key[:2]:
-        _prep_all(w.device)           # same storage, new optimizer epoch: batch-refresh every registered image
-    if cache is None or cache[0] != key or cache[1] != kind:
-        first = cache is None
-        cache = [key, kind, None, None]
-        try:
-            w._buctd_gprep = cache
-            if first:                 # one registry entry per weight tensor, however often its cache key changes
-                _gprep_registry["weights"].append(weakref.ref(w))
-        except (AttributeError, RuntimeError, TypeError):
-            pass
-    if cache[2 + direction] is None:
+    def build():
+        Co, Ci = _wshape(w)[:2]
         nbytes = _memo(("gcpb", kind, Ci, Co, direction), lambda: int(lib().buctd_gconv_x6_prep_bytes(kind, Ci, Co, direction)))
         img = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
         check(lib().buctd_gconv_x6_prep(kind, Ci, Co, ptr(w), direction, ptr(img), stream_ptr()), "gconv_x6_prep")
-        cache[2 + direction] = img
-    _prep_wait(w.device)
-    return cache[2 + direction]
+        return img
+    return _Derived.get(w, "gc", (kind, direction), build)
 
 
 def _gconv_fwd(x, w, d, bias, scale, shift, residual, relu, stats):
@@ -711,14 +738,10 @@ def _gconv_fwd(x, w, d, bias, scale, shift, residual, relu, stats):
                                            C.c_void_p(acc.ptr), stream_ptr()), "gconv_x6_fwd_acc")
         return y, acc, ("acc",)
     if stats:
-        def groups():
-            ng, rpg = C.c_int(), C.c_int()
-            check(lib().buctd_gconv_x6_stats_groups(kind, d.N, d.H, d.W, d.Ci, d.Co, C.byref(ng), C.byref(rpg)), "gconv groups")
-            return ng.value, rpg.value
-        ngv, rpgv = _memo(("gcgrp", kind, d.N, d.H, d.W, d.Ci, d.Co), groups)
-        part = torch.empty((ngv, d.Co, 2), dtype=torch.float32, device=x.device)
-        counts = torch.empty(ngv, dtype=torch.int32, device=x.device)
-        info = (ngv, rpgv, counts)
+        part, info = _stats_buffers(("gcgrp", kind, d.N, d.H, d.W, d.Ci, d.Co),
+                                    lambda ng, rpg: lib().buctd_gconv_x6_stats_groups(kind, d.N, d.H, d.W, d.Ci, d.Co, ng, rpg),
+                                    d.Co, x.device, True)
+        counts = info[2]
     check(lib().buctd_gconv_x6_fwd(kind, d.N, d.H, d.W, d.Ci, d.Co, ptr(x), ptr(wp), ptr(bias), ptr(scale), ptr(shift),
                                    ptr(residual), int(bool(relu)), ptr(y), ptr(part), ptr(counts), stream_ptr()), "gconv_x6_fwd")
     return (y, part, info) if stats else y
@@ -781,10 +804,9 @@ def conv_fwd(x, w, bias=None, stride=1, pad=0, scale=None, shift=None, residual=
     if _gconv_ok(d, 0):
         return _gconv_fwd(x, w, d, bias, scale, shift, residual, relu, stats)
     y = torch.empty((d.N, d.Ho, d.Wo, d.Co), dtype=torch.float32, device=x.device)
-    part = None
-    info = None
+    part = info = None
     if stats and scale is None and residual is None and not relu and \
-            _memo(("thin", d.N, d.H, d.W, d.Ci, d.Co, d.R, d.S, d.stride, d.pad), lambda: lib().buctd_conv2d_fwd_thin(C.byref(d)) == 1):
+            _memo(("thin",) + _dkey(d), lambda: lib().buctd_conv2d_fwd_thin(C.byref(d)) == 1):
         # <= 4 output channels at full resolution (preNet 7x7): the thin kernel has no fused epilogue; the BatchNorm
         # partials of its 3-channel result are one cheap extra pass
         check(lib().buctd_conv2d_fwd(C.byref(d), ptr(x), ptr(w), ptr(bias), None, None, None, 0, ptr(y), None, stream_ptr()),
@@ -792,13 +814,8 @@ def conv_fwd(x, w, bias=None, stride=1, pad=0, scale=None, shift=None, residual=
         part, info = bn_stats(y)
         return y, part, info
     if stats:
-        def groups():
-            ng_, rpg_ = C.c_int(), C.c_int()
-            check(lib().buctd_conv2d_stats_groups(C.byref(d), 0, C.byref(ng_), C.byref(rpg_)), "conv2d_stats_groups")
-            return ng_, rpg_
-        ng, rpg = _memo(("c2grp", 0, d.N, d.H, d.W, d.Ci, d.Co, d.R, d.S, d.stride, d.pad), groups)
-        part = torch.empty((ng.value, d.Co, 2), dtype=torch.float32, device=x.device)
-        info = (ng.value, rpg.value)
+        part, info = _stats_buffers(("c2grp", 0) + _dkey(d),
+                                    lambda ng, rpg: lib().buctd_conv2d_stats_groups(C.byref(d), 0, ng, rpg), d.Co, x.device)
     check(lib().buctd_conv2d_fwd(C.byref(d), ptr(x), ptr(w), ptr(bias), ptr(scale), ptr(shift), ptr(residual),
                                  int(bool(relu)), ptr(y), ptr(part), stream_ptr()), "conv2d_fwd")
     return (y, part, info) if stats else y
@@ -824,16 +841,10 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, bias=None, stats=False, residual
                                          ptr(residual), ptr(dx), stream_ptr()), "gconv_x6_dgrad")
         return dx
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    part = None
-    info = None
+    part = info = None
     if stats:
-        def groups():
-            ng_, rpg_ = C.c_int(), C.c_int()
-            check(lib().buctd_conv2d_stats_groups(C.byref(d), 1, C.byref(ng_), C.byref(rpg_)), "conv2d_stats_groups")
-            return ng_, rpg_
-        ng, rpg = _memo(("c2grp", 1, d.N, d.H, d.W, d.Ci, d.Co, d.R, d.S, d.stride, d.pad), groups)
-        part = torch.empty((ng.value, d.Ci, 2), dtype=torch.float32, device=dy.device)
-        info = (ng.value, rpg.value)
+        part, info = _stats_buffers(("c2grp", 1) + _dkey(d),
+                                    lambda ng, rpg: lib().buctd_conv2d_stats_groups(C.byref(d), 1, ng, rpg), d.Ci, dy.device)
     check(lib().buctd_conv2d_dgrad(C.byref(d), ptr(dy), ptr(w), ptr(bias), ptr(dx), ptr(part), stream_ptr()),
           "conv2d_dgrad")
     if residual is not None:
@@ -1139,23 +1150,10 @@ def x6_gemm(a_image, b_image, Cout, M, N, K, *, ldc, Nc=0, gsc=0, bias=None, bia
 def _x6_weight_image(w, V, K, transposed):
     """bf16x6 image of a Linear weight w [V or K rows] as the A operand, cached on the tensor until it changes
     (version / optimizer epoch).  transposed: the logical matrix is w^T (X[v][k] = w[k][v])."""
-    key = (w.data_ptr(), w._version, _weights_epoch["n"])
-    cache = getattr(w, "_buctd_x6img", None)
-    if cache is None or cache["key"] != key:
-        cache = {"key": key}
-        try:
-            w._buctd_x6img = cache
-        except (AttributeError, RuntimeError, TypeError):
-            pass
-    tag = "t" if transposed else "n"
-    if tag not in cache:
-        ld = w.shape[1]
-        cache[tag] = x6_image(w, V, K, 0, vs=1, ks=ld) if transposed else x6_image(w, V, K, 0, vs=ld, ks=1)
-        cache[tag + "_ev"] = _new_event()
-        cache[tag + "_stream"] = torch.cuda.current_stream(w.device).cuda_stream
-    elif torch.cuda.current_stream(w.device).cuda_stream != cache[tag + "_stream"]:
-        _wait_event(torch.cuda.current_stream(w.device), cache[tag + "_ev"])
-    return cache[tag]
+    ld = w.shape[1]
+    if transposed:
+        return _Derived.get(w, "x6", "t", lambda: x6_image(w, V, K, 0, vs=1, ks=ld))
+    return _Derived.get(w, "x6", "n", lambda: x6_image(w, V, K, 0, vs=ld, ks=1))
 
 
 def fc_o_x6_ok(T, rows):
@@ -1216,11 +1214,9 @@ def bn_acc_ok(Cn):
 def bn_stats(z):
     Cn = z.shape[-1]
     rows = z.numel() // Cn
-    ng, rpg = C.c_int(), C.c_int()
-    check(lib().buctd_bn_stats_groups(rows, Cn, C.byref(ng), C.byref(rpg)), "bn_stats_groups")
-    part = torch.empty((ng.value, Cn, 2), dtype=torch.float32, device=z.device)
+    part, info = _stats_buffers(("bngrp", rows, Cn), lambda ng, rpg: lib().buctd_bn_stats_groups(rows, Cn, ng, rpg), Cn, z.device)
     check(lib().buctd_bn_stats(ptr(z), rows, Cn, ptr(part), None, None, stream_ptr()), "bn_stats")
-    return part, (ng.value, rpg.value)
+    return part, info
 
 
 def bn_apply(z, mean, invstd, gamma, beta, residual=None, relu=False):
@@ -1266,18 +1262,16 @@ def bn_fold_cached(bn, gamma, beta, eps):
     key = (gamma.data_ptr(), gamma._version, beta._version, rm.data_ptr(), rm._version, rv._version, _weights_epoch["n"],
            float(eps), getattr(bn, "_pending_batches", 0), nbt._version if nbt is not None else 0)
     cache = getattr(bn, "_buctd_fold", None)
-    cur = torch.cuda.current_stream(gamma.device)
     if cache is None or cache[0] != key:
+        _derived_rebuilds["n"] += 1
         scale, shift = bn_fold(gamma, beta, rm, rv, eps)
-        ev = _new_event()
-        cache = (key, scale, shift, ev, cur.cuda_stream, set())
+        cache = (key, scale, shift) + _produced_here(gamma.device)
         try:
             object.__setattr__(bn, "_buctd_fold", cache)
         except (AttributeError, TypeError):
-            return scale, shift
-    elif cur.cuda_stream != cache[4] and cur.cuda_stream not in cache[5]:
-        _wait_event(cur, cache[3])            # folded on another stream: order this stream behind it, once
-        cache[5].add(cur.cuda_stream)
+            pass
+    else:
+        _wait_once(gamma.device, *cache[3:])  # folded on another stream: order this stream behind it, once
     return cache[1], cache[2]
 
 

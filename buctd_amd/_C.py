@@ -177,6 +177,7 @@ SIGNATURES = {
     "buctd_conv3x3_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "buctd_conv3x3_wgrad_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "buctd_gconv_wgrad_x6_supported": (_I, [_I] * 6),
+    "buctd_gconv_wgrad_x6_plan": (_I, [_I] * 6 + [C.POINTER(C.c_int)]),
     "buctd_gconv_wgrad_x6_workspace": (_SZ, [_I] * 6),
     "buctd_gconv_wgrad_x6": (_I, [_I] * 6 + [_P, _P, _P, _I, _P, _SZ, _P]),
     "buctd_bn_apply_acc_group": (_I, [_I, C.POINTER(BnApplyItem), _P]),
@@ -246,6 +247,7 @@ SIGNATURES = {
     "buctd_gconv_x6_stats_groups": (_I, [_I] * 6 + [_PI, _PI]),
     "buctd_gconv_x6_fwd": (_I, [_I] * 6 + [_P] * 6 + [_I, _P, _P, _P, _P]),
     "buctd_gconv_x6_dgrad": (_I, [_I] * 6 + [_P] * 4 + [_P]),
+    "buctd_gconv_x6_plan": (_I, [_I] * 8 + [C.POINTER(C.c_int)]),
     "buctd_mha_fwd_bf16x6_workspace": (_SZ, [_I, _I, _I]),
     "buctd_mha_heads_fwd_bf16x6_ws": (_I, [C.POINTER(MhaArgs), _P, _SZ, _P]),
     "buctd_mha_heads_fwd_supported": (_I, [_I, _I, _I]),

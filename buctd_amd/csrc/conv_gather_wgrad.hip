@@ -292,6 +292,17 @@ extern "C" int buctd_gconv_wgrad_x6_supported(int kind, int N, int H, int W, int
   GwPlan pl;
   return gw_plan(kind, N, H, W, Ci, Co, &pl) ? 1 : 0;
 }
+/* The plan buctd_gconv_wgrad_x6 would run with (no launch): out[8] = CF (16-channel fragments per chunk), TPG (taps per
+ * group), ntg (tap groups), nsplit (K splits per chunk pair and tap group), q and rem (a split takes q k-steps, the first rem
+ * of them q + 1), ksteps (32-pixel k-steps) and Q % 32 (pixels of a ragged last k-step; 0: none). */
+extern "C" int buctd_gconv_wgrad_x6_plan(int kind, int N, int H, int W, int Ci, int Co, int* out) {
+  GwPlan pl;
+  BUCTD_CHECK_ARG(out && gw_plan(kind, N, H, W, Ci, Co, &pl),
+                  "buctd_gconv_wgrad_x6_plan: unsupported shape kind %d N%d H%d W%d Ci%d Co%d", kind, N, H, W, Ci, Co);
+  out[0] = pl.CF; out[1] = pl.TPG; out[2] = pl.ntg; out[3] = pl.nsplit; out[4] = pl.q; out[5] = pl.rem; out[6] = pl.ksteps;
+  out[7] = (int)(((long)N * pl.Ho * pl.Wo) % 32);
+  return BUCTD_OK;
+}
 extern "C" size_t buctd_gconv_wgrad_x6_workspace(int kind, int N, int H, int W, int Ci, int Co) {
   GwPlan pl;
   return gw_plan(kind, N, H, W, Ci, Co, &pl) ? pl.ws : 0;

@@ -609,15 +609,15 @@ static bool r1_ok(int kind, long rows, int cin, int cout) {
   return lds <= 150 * 1024 && (size_t)8 * cout * 16 <= (size_t)(cin / 32) * cout * R1_WROW && rows >= 65536;
 }
 
-static int r1_run(long rows, int cin, int cout, const float* x, const void* wprep, const float* bias, const float* residual, float* out,
-                  long long* stats_acc, hipStream_t st, const char* who) {
+static int r1_run(long rows, int cin, int cout, int nft, const float* x, const void* wprep, const float* bias, const float* residual,
+                  float* out, long long* stats_acc, hipStream_t st, const char* who) {
   R1Args a;
   a.x = x; a.wp = (const unsigned char*)wprep; a.bias = bias; a.res = residual; a.out = out; a.stats_acc = stats_acc;
   a.rows = rows; a.Ci = cin; a.Co = cout; a.nblocks = (int)((rows + 31) / 32);
   const size_t lds = (size_t)(cin / 32) * cout * R1_WROW + (size_t)8 * R1_STG;
   static unsigned char done[3][BUCTD_MAX_DEVICES] = {{0}};
-  void (*fn)(R1Args) = cout == 64 ? conv1x1_rows_x6_kernel<4> : cout == 128 ? conv1x1_rows_x6_kernel<8> : conv1x1_rows_x6_kernel<16>;
-  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, done[cout == 64 ? 0 : cout == 128 ? 1 : 2], who))
+  void (*fn)(R1Args) = nft == 4 ? conv1x1_rows_x6_kernel<4> : nft == 8 ? conv1x1_rows_x6_kernel<8> : conv1x1_rows_x6_kernel<16>;
+  if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(fn), 160 * 1024, done[nft == 4 ? 0 : nft == 8 ? 1 : 2], who))
     return rc;
   int grid = 256;
   if (grid * 8 > a.nblocks) grid = (a.nblocks + 7) / 8;
@@ -626,71 +626,135 @@ static int r1_run(long rows, int cin, int cout, const float* x, const void* wpre
   return BUCTD_OK;
 }
 
-static int gc_run(int kind, int dir, int N, int H, int W, int Ci, int Co, const float* src, const void* wprep, const float* bias,
-                  const float* scale, const float* shift, const float* residual, int relu, float* out, float* stats_partials,
-                  int* stats_counts, void* stream, const char* who, long long* stats_acc = nullptr) {
+// ---- routing -----------------------------------------------------------------------------------------------------------------
+// Everything a launch decides from the shape and from WHICH optional arguments it carries (never from their values): the
+// kernel, the tile plan, the epilogue, the classes and the grid.  gc_run launches what this says and buctd_gconv_x6_plan
+// reports it, so the two cannot drift apart.  The flags are part of the C interface (buctd_gconv_x6_plan).
+enum { GCF_BIAS = 1, GCF_SCALE = 2, GCF_RELU = 4, GCF_PARTIALS = 8, GCF_ACC = 16, GCF_RES = 32, GCF_ALL = 63 };
+
+struct GcRoute {
+  int route;                         // 0: gconv_x6_kernel, 1: conv1x1_rows_x6_kernel
   int Hg, Wg, SH, SWd, SC, nout;
-  BUCTD_CHECK_ARG(src && wprep && out, "%s: null tensor pointer", who);
-  BUCTD_CHECK_ARG(gc_geo(kind, dir, N, H, W, Ci, Co, &Hg, &Wg, &SH, &SWd, &SC, &nout),
+  long rows;                         // N * H * W
+  int P;                             // padded flattened positions of the tiled kernel
+  GcPlan pl;                         // route 0 ...
+  int mode;                          // -1, 0, C3M_STATS, C3M_RES
+  int ncls;
+  GcClass cls[4];
+  int tiles, ncol;
+  int nft, ksteps;                   // route 1: column fragments (the kernel instance), K = 32 steps
+};
+
+static int gc_route(int kind, int dir, int N, int H, int W, int Ci, int Co, int flags, const char* who, GcRoute* r) {
+  memset(r, 0, sizeof(GcRoute));
+  BUCTD_CHECK_ARG(gc_geo(kind, dir, N, H, W, Ci, Co, &r->Hg, &r->Wg, &r->SH, &r->SWd, &r->SC, &r->nout),
                   "%s: unsupported shape kind %d N%d H%d W%d Ci%d Co%d", who, kind, N, H, W, Ci, Co);
-  BUCTD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
-  BUCTD_CHECK_ARG((stats_partials == nullptr) == (stats_counts == nullptr), "%s: stats partials and counts go together", who);
-  BUCTD_CHECK_ARG(!(dir && stats_partials), "%s: no statistics on the data gradient", who);
-  if (!scale && !relu && !stats_partials && r1_ok(kind, (long)N * H * W, SC, nout))
-    return r1_run((long)N * H * W, SC, nout, src, wprep, bias, residual, out, stats_acc, (hipStream_t)stream, who);
-  GcPlan pl;
-  gc_plan(nout, (long)N * (Hg + 1) * (Wg + 2) + Wg + 2, &pl);
-  GcArgs a;
-  C3Args& e = a.e;
-  e.x = nullptr; e.wp = nullptr; e.out = out; e.bias = bias; e.scale = scale; e.shift = shift; e.res = residual;
-  e.stats = stats_partials; e.counts = stats_counts;
-  e.N = N; e.H = Hg; e.W = Wg; e.Ci = SC; e.Co = nout;
-  e.SW = Wg + 2; e.IB = (Hg + 1) * (Wg + 2);
-  e.P = (int)((long)N * e.IB + e.SW);
-  e.relu = relu; e.na = 0;
-  e.in_mean = e.in_invstd = e.in_gamma = e.in_beta = nullptr; e.in_relu = 0; e.col_major = 0;
-  e.bs_z = e.bs_y = e.bs_mean = e.bs_invstd = e.bs_gamma = e.bs_beta = nullptr; e.bs_part = nullptr;
-  e.stats_acc = stats_acc; e.bs_acc = nullptr;
-  memset(&e.in_acc, 0, sizeof(e.in_acc));
-  BUCTD_CHECK_ARG(!(dir && stats_acc), "%s: no statistics on the data gradient", who);
-  magic_u32((unsigned)e.IB, &e.ib_mul, &e.ib_sh);
-  magic_u32((unsigned)e.SW, &e.sw_mul, &e.sw_sh);
+  BUCTD_CHECK_ARG(!(dir && (flags & (GCF_PARTIALS | GCF_ACC))), "%s: no statistics on the data gradient", who);
+  const bool bias = flags & GCF_BIAS, scale = flags & GCF_SCALE, relu = flags & GCF_RELU, partials = flags & GCF_PARTIALS,
+             acc = flags & GCF_ACC, res = flags & GCF_RES;
+  const int SC = r->SC, nout = r->nout;
+  r->rows = (long)N * H * W;
+  if (!scale && !relu && !partials && r1_ok(kind, r->rows, SC, nout)) {
+    r->route = 1;
+    r->nft = nout / 16;
+    r->ksteps = SC / 32;
+    return BUCTD_OK;
+  }
+  const long P = (long)N * (r->Hg + 1) * (r->Wg + 2) + r->Wg + 2;
+  r->P = (int)P;
+  gc_plan(nout, P, &r->pl);
   const bool par = kind == 2 && dir;
-  e.omap = par ? 1 : 0; e.oH = H; e.oW = W; e.ost = par ? 2 : 1; e.oy0 = e.ox0 = 0;
-  a.src = src; a.wp = (const unsigned char*)wprep;
-  a.SH = SH; a.SWd = SWd; a.SC = SC; a.ss = (kind == 2 && !dir) ? 2 : 1; a.cpt = SC / 16;
-  a.ncls = gc_ncls(kind, dir);
+  const int cpt = SC / 16;
+  r->ncls = gc_ncls(kind, dir);
   long off = 0;
   int tr[GC_MAXT], ts[GC_MAXT];
-  for (int c = 0; c < 4; ++c) {
-    GcClass& k = a.cls[c];
-    k.ntaps = k.nhs = k.nsteps = 0; k.oy0 = k.ox0 = 0; k.wp_off = 0; k.pdy = k.pdx = 0u;
-    if (c >= a.ncls) continue;
+  for (int c = 0; c < r->ncls; ++c) {
+    GcClass& k = r->cls[c];
     int tdy[GC_MAXT], tdx[GC_MAXT];
     k.ntaps = gc_taps(kind, dir, c, tr, ts, tdy, tdx);
-    k.pdy = k.pdx = 0u;
     for (int t = 0; t < k.ntaps; ++t) {
       k.pdy |= (unsigned)(tdy[t] + 1) << (2 * t);
       k.pdx |= (unsigned)(tdx[t] + 1) << (2 * t);
     }
-    k.nhs = k.ntaps * a.cpt;
+    k.nhs = k.ntaps * cpt;
     k.nsteps = (k.nhs + 1) / 2;
     k.oy0 = par ? (c >> 1) : 0; k.ox0 = par ? (c & 1) : 0;
     k.wp_off = off;
     off += (long)gc_class_bytes(k.ntaps, SC, nout);
   }
-  const int tiles = (e.P + pl.BM - 1) / pl.BM, ncol = nout / pl.BN;
-  hipStream_t st = (hipStream_t)stream;
+  r->tiles = (int)((P + r->pl.BM - 1) / r->pl.BM);
+  r->ncol = nout / r->pl.BN;
   // the option sets of the train step take the straight-line epilogue (tensors below 2 GB: 32-bit byte offsets)
-  int mode = -1;
-  if (!bias && !scale && !relu && !stats_partials && !(stats_acc && residual) &&
-      (long)N * H * W * (Ci > Co ? Ci : Co) * 4 < 2147483648L)
-    mode = stats_acc ? C3M_STATS : residual ? C3M_RES : 0;
-  if (pl.NF == 3 && pl.WM == 2) gc_launch<4, 3, 2, 2>(a, tiles, ncol, st, mode);
-  else if (pl.NF == 4 && pl.WM == 2) gc_launch<4, 4, 2, 2>(a, tiles, ncol, st, mode);
-  else if (pl.NF == 4) gc_launch<2, 4, 4, 1>(a, tiles, ncol, st, mode);
-  else gc_launch<2, 3, 4, 1>(a, tiles, ncol, st, mode);
+  r->mode = -1;
+  if (!bias && !scale && !relu && !partials && !(acc && res) && (long)N * H * W * (Ci > Co ? Ci : Co) * 4 < 2147483648L)
+    r->mode = acc ? C3M_STATS : res ? C3M_RES : 0;
+  return BUCTD_OK;
+}
+
+static int gc_run(int kind, int dir, int N, int H, int W, int Ci, int Co, const float* src, const void* wprep, const float* bias,
+                  const float* scale, const float* shift, const float* residual, int relu, float* out, float* stats_partials,
+                  int* stats_counts, void* stream, const char* who, long long* stats_acc = nullptr) {
+  BUCTD_CHECK_ARG(src && wprep && out, "%s: null tensor pointer", who);
+  BUCTD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
+  BUCTD_CHECK_ARG((stats_partials == nullptr) == (stats_counts == nullptr), "%s: stats partials and counts go together", who);
+  const int flags = (bias ? GCF_BIAS : 0) | (scale ? GCF_SCALE : 0) | (relu ? GCF_RELU : 0) | (stats_partials ? GCF_PARTIALS : 0) |
+                    (stats_acc ? GCF_ACC : 0) | (residual ? GCF_RES : 0);
+  GcRoute r;
+  if (const int rc = gc_route(kind, dir, N, H, W, Ci, Co, flags, who, &r)) return rc;
+  if (r.route == 1)
+    return r1_run(r.rows, r.SC, r.nout, r.nft, src, wprep, bias, residual, out, stats_acc, (hipStream_t)stream, who);
+  const GcPlan& pl = r.pl;
+  GcArgs a;
+  C3Args& e = a.e;
+  e.x = nullptr; e.wp = nullptr; e.out = out; e.bias = bias; e.scale = scale; e.shift = shift; e.res = residual;
+  e.stats = stats_partials; e.counts = stats_counts;
+  e.N = N; e.H = r.Hg; e.W = r.Wg; e.Ci = r.SC; e.Co = r.nout;
+  e.SW = r.Wg + 2; e.IB = (r.Hg + 1) * (r.Wg + 2);
+  e.P = r.P;
+  e.relu = relu; e.na = 0;
+  e.in_mean = e.in_invstd = e.in_gamma = e.in_beta = nullptr; e.in_relu = 0; e.col_major = 0;
+  e.bs_z = e.bs_y = e.bs_mean = e.bs_invstd = e.bs_gamma = e.bs_beta = nullptr; e.bs_part = nullptr;
+  e.stats_acc = stats_acc; e.bs_acc = nullptr;
+  memset(&e.in_acc, 0, sizeof(e.in_acc));
+  magic_u32((unsigned)e.IB, &e.ib_mul, &e.ib_sh);
+  magic_u32((unsigned)e.SW, &e.sw_mul, &e.sw_sh);
+  const bool par = kind == 2 && dir;
+  e.omap = par ? 1 : 0; e.oH = H; e.oW = W; e.ost = par ? 2 : 1; e.oy0 = e.ox0 = 0;
+  a.src = src; a.wp = (const unsigned char*)wprep;
+  a.SH = r.SH; a.SWd = r.SWd; a.SC = r.SC; a.ss = (kind == 2 && !dir) ? 2 : 1; a.cpt = r.SC / 16;
+  a.ncls = r.ncls;
+  for (int c = 0; c < 4; ++c) a.cls[c] = r.cls[c];
+  hipStream_t st = (hipStream_t)stream;
+  if (pl.NF == 3 && pl.WM == 2) gc_launch<4, 3, 2, 2>(a, r.tiles, r.ncol, st, r.mode);
+  else if (pl.NF == 4 && pl.WM == 2) gc_launch<4, 4, 2, 2>(a, r.tiles, r.ncol, st, r.mode);
+  else if (pl.NF == 4) gc_launch<2, 4, 4, 1>(a, r.tiles, r.ncol, st, r.mode);
+  else gc_launch<2, 3, 4, 1>(a, r.tiles, r.ncol, st, r.mode);
   BUCTD_CHECK_LAUNCH(who);
+  return BUCTD_OK;
+}
+
+/* Which kernel, tile plan and epilogue buctd_gconv_x6_fwd / _fwd_acc / _dgrad would run for this shape when the call carries
+ * the optional arguments named by `flags` (1 bias, 2 scale / shift, 4 relu, 8 partial-sum statistics, 16 statistics
+ * accumulator, 32 residual).  No launch: the answer is gc_route's, which the launch itself goes through.  out[25] = route
+ * (0 gconv_x6_kernel, 1 conv1x1_rows_x6_kernel), MF, NF, WM, WN, BM, BN, mode (-1 general epilogue, 0 plain, 2 C3M_STATS,
+ * 4 C3M_RES), ncls, (ntaps, nhs, nsteps) of the four classes, tiles, ncol, and for route 1 (where all of the former but the
+ * route are 0) NFT and the number of K = 32 steps.  The entry points cannot express every flag set: a data gradient carries
+ * the residual only, the accumulator form the bias only. */
+extern "C" int buctd_gconv_x6_plan(int kind, int dir, int N, int H, int W, int Ci, int Co, int flags, int* out) {
+  BUCTD_CHECK_ARG(out && (dir == 0 || dir == 1) && flags >= 0 && flags <= GCF_ALL, "buctd_gconv_x6_plan: bad argument");
+  BUCTD_CHECK_ARG(!(dir && (flags & ~GCF_RES)), "buctd_gconv_x6_plan: a data gradient carries the residual only (flags %d)", flags);
+  BUCTD_CHECK_ARG(!((flags & GCF_ACC) && (flags & ~(GCF_ACC | GCF_BIAS))),
+                  "buctd_gconv_x6_plan: the accumulator form carries the bias only (flags %d)", flags);
+  GcRoute r;
+  if (const int rc = gc_route(kind, dir, N, H, W, Ci, Co, flags, "buctd_gconv_x6_plan", &r)) return rc;
+  int i = 0;
+  out[i++] = r.route;
+  out[i++] = r.pl.MF; out[i++] = r.pl.NF; out[i++] = r.pl.WM; out[i++] = r.pl.WN; out[i++] = r.pl.BM; out[i++] = r.pl.BN;
+  out[i++] = r.route ? 0 : r.mode;
+  out[i++] = r.ncls;
+  for (int c = 0; c < 4; ++c) { out[i++] = r.cls[c].ntaps; out[i++] = r.cls[c].nhs; out[i++] = r.cls[c].nsteps; }
+  out[i++] = r.tiles; out[i++] = r.ncol;
+  out[i++] = r.nft; out[i++] = r.ksteps;
   return BUCTD_OK;
 }
 

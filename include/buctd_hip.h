@@ -537,11 +537,24 @@ int buctd_gconv_x6_fwd_acc(int kind, int N, int H, int W, int Ci, int Co, const 
                            float* y, void* stats_acc, void* stream);
 int buctd_gconv_x6_dgrad(int kind, int N, int H, int W, int Ci, int Co, const float* dy, const void* wprep,
                          const float* residual, float* dx, void* stream);
+/* Which kernel, tile plan and epilogue a launch of this shape takes (host code only, no launch; computed by the routing
+ * function the launch itself goes through, so the answer cannot drift from it).  dir 0: _fwd / _fwd_acc, dir 1: _dgrad.
+ * flags: which optional arguments the call would carry - 1 bias, 2 scale / shift, 4 relu, 8 partial-sum statistics,
+ * 16 statistics accumulator (_fwd_acc: with the bias only), 32 residual (the only one a data gradient has).
+ * out[25] = route (0 = gconv_x6_kernel, 1 = conv1x1_rows_x6_kernel), MF, NF, WM, WN, BM, BN, mode (-1 general epilogue,
+ * 0 plain, 2 C3M_STATS, 4 C3M_RES of csrc/c3_lean.h), ncls, (ntaps, nhs, nsteps) of the four classes (0 beyond ncls), tiles,
+ * ncol, and for route 1 - where everything between the route and here is 0 - NFT (16-column fragments) and the number of
+ * K = 32 steps.  BUCTD_EINVAL: unsupported shape or flag set.  For tests that must know which code path a shape exercises. */
+int buctd_gconv_x6_plan(int kind, int dir, int N, int H, int W, int Ci, int Co, int flags, int* out);
 /* Weight gradient of a 1x1 (kind 1) or stride-2 3x3 pad-1 (kind 2; H, W even) convolution Ci -> Co in the bf16x6 arithmetic
  * (csrc/conv_gather_wgrad.hip): dw [Co][R][S][Ci] (+)= sum over output pixels dy (x) gathered x, x = [N][H][W][Ci], dy =
  * [N][Ho][Wo][Co].  The autograd weight gradient of the fuse-layer / transition / Bottleneck convolutions
  * (pose_hrnet.py:60-108, 187-245, 338-372); both channel counts must be multiples of 48, or both of 32. */
 int buctd_gconv_wgrad_x6_supported(int kind, int N, int H, int W, int Ci, int Co);
+/* the plan of that launch (no launch): out[8] = CF (64-, 48- or 32-channel chunk pairs: 4, 3, 2), TPG (taps per group), ntg
+ * (tap groups), nsplit (K splits), q, rem (a split takes q k-steps of 32 output pixels, the first rem of them q + 1), ksteps,
+ * and the pixels of a ragged last k-step (N * Ho * Wo % 32).  BUCTD_EINVAL: unsupported shape. */
+int buctd_gconv_wgrad_x6_plan(int kind, int N, int H, int W, int Ci, int Co, int* out);
 size_t buctd_gconv_wgrad_x6_workspace(int kind, int N, int H, int W, int Ci, int Co);
 int buctd_gconv_wgrad_x6(int kind, int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw,
                          int accumulate, void* workspace, size_t workspace_bytes, void* stream);

@@ -101,6 +101,13 @@ class SampleGeomArgs(C.Structure):      # mirrors buctd_sample_geom_args
                 [(n, C.c_double) for n in ("margin", "aspect_ratio", "scale_thre", "stride_x", "stride_y")])
 
 
+class KptMatchArgs(C.Structure):        # mirrors buctd_kpt_match_args
+    _fields_ = ([(n, C.c_int) for n in ("images", "K", "n_thr", "n_area")] + [(n, C.c_long) for n in ("dt_total", "gt_total")] +
+                [(n, C.c_void_p) for n in ("dt_offsets", "gt_offsets", "oks_offsets", "dt_kpts", "gt_kpts", "gt_area",
+                                           "gt_bbox", "gt_flags", "sigmas", "thresholds", "area_ranges", "oks",
+                                           "dt_matched", "dt_ignored")])
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -117,6 +124,7 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_long
 _F = C.c_float
+_D = C.c_double
 _U64 = C.c_uint64
 _SZ = C.c_size_t
 _PD = C.POINTER(ConvDesc)
@@ -262,6 +270,10 @@ SIGNATURES = {
     "buctd_nms_workspace": (_SZ, [_I]),
     "buctd_nms": (_I, [_P, _P, _P, _I, _I, _F, _P, _SZ, _P]),
     "buctd_cpu_nms": (_I, [_P, _I, _P, _F, _P, _P]),
+    "buctd_kpt_rescore": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P]),
+    "buctd_oks_nms_grouped": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, _I, _D, _P, _P]),
+    "buctd_coco_kpt_match_workspace": (_SZ, [_L, _I, _I]),
+    "buctd_coco_kpt_match": (_I, [C.POINTER(KptMatchArgs), _P, _SZ, _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),

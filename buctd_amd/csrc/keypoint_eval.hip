@@ -1,0 +1,278 @@
+// Keypoint evaluation on the device (core/keypoint_eval.py): the rescoring and grouped OKS NMS of the reference's
+// data set classes (lib/dataset/dataloader.py:590-634 around lib/nms/nms.py:75-124) and the per-image part of the
+// published COCO keypoint evaluation (computeOks + evaluateImg).  Everything is fp64: a match is a comparison against
+// a threshold, and the data is a few MB.
+//
+// MI355X shape of the problem: each image is a wave-sized job that exists thousands of times, so one wave64 wavefront
+// takes one image - lanes stride over the candidates of an NMS step, over the cells of the OKS matrix, and one lane
+// runs each of the (area range, threshold) greedy matchings.  These are latency kernels; nothing here is tuned.
+#include "common.h"
+#include "../../include/buctd_hip.h"
+
+#define KPT_SPACING1 2.220446049250313e-16   // np.spacing(1)
+
+// Per person: mean of the joint scores above in_vis_thre (0 if none), summed in joint order; score = mean * box score.
+__global__ __launch_bounds__(64) void kpt_rescore_kernel(int n, int K, double in_vis_thre, const float* __restrict__ preds,
+                                                         const double* __restrict__ box_in, double* __restrict__ score,
+                                                         double* __restrict__ box_score,
+                                                         double* __restrict__ keypoint_score) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= n) return;
+  double s = 0.0;
+  int valid = 0;
+  for (int j = 0; j < K; ++j) {
+    const double t = (double)preds[((long)p * K + j) * 3 + 2];
+    if (t > in_vis_thre) {
+      s = s + t;
+      ++valid;
+    }
+  }
+  if (valid != 0) s = s / valid;
+  const double b = box_in[p];
+  score[p] = s * b;
+  box_score[p] = b;
+  keypoint_score[p] = s;
+}
+
+// oks_iou of nms/nms.py:86-105 for one (head, candidate) pair; kp rows are [K][3] float32.
+__device__ __forceinline__ double nms_oks(const float* __restrict__ g, const float* __restrict__ d, double a_g, double a_d,
+                                          const double* __restrict__ sigmas, int K, int use_vis, double in_vis_thre) {
+  const double scale = (a_g + a_d) / 2 + KPT_SPACING1;
+  double sum = 0.0;
+  int cnt = 0;
+  for (int j = 0; j < K; ++j) {
+    if (use_vis && !((double)d[j * 3 + 2] > in_vis_thre)) continue;
+    const double dx = (double)d[j * 3 + 0] - (double)g[j * 3 + 0];
+    const double dy = (double)d[j * 3 + 1] - (double)g[j * 3 + 1];
+    const double var = (sigmas[j] * 2) * (sigmas[j] * 2);
+    const double e = (dx * dx + dy * dy) / var / scale / 2;
+    sum += exp(-e);
+    ++cnt;
+  }
+  return cnt > 0 ? sum / cnt : 0.0;
+}
+
+// One wavefront per image; persons [off[i], off[i+1]) are in descending score order.  The alive set is a bitmap in LDS
+// (cap_words words); a kept head clears the later candidates it overlaps by more than thresh, 64 candidates per step.
+__global__ __launch_bounds__(64) void oks_nms_grouped_kernel(int K, int cap_words, double thresh, int use_vis,
+                                                             double in_vis_thre, const int* __restrict__ off,
+                                                             const float* __restrict__ kpts, const double* __restrict__ areas,
+                                                             const double* __restrict__ sigmas, int* __restrict__ keep) {
+  extern __shared__ unsigned long long alive[];
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int base = off[img];
+  const int n_all = off[img + 1] - base;
+  const int n = min(n_all, cap_words * 64);      // persons beyond the caller's stated maximum are dropped, never indexed
+  const int words = (n + 63) >> 6;
+  for (int w = lane; w < words; w += 64) {
+    const int rest = n - w * 64;
+    alive[w] = rest >= 64 ? ~0ull : ((1ull << rest) - 1ull);
+  }
+  __syncthreads();
+  for (int a = 0; a < n; ++a) {
+    if (!((alive[a >> 6] >> (a & 63)) & 1ull)) continue;            // same address in every lane: uniform
+    const float* g = kpts + (long)(base + a) * K * 3;
+    const double a_g = areas[base + a];
+    for (int c0 = (a + 1) & ~63; c0 < n; c0 += 64) {
+      const int c = c0 + lane;
+      const unsigned long long word = alive[c0 >> 6];
+      bool dead = false;
+      if (c > a && c < n && ((word >> lane) & 1ull))
+        dead = nms_oks(g, kpts + (long)(base + c) * K * 3, a_g, areas[base + c], sigmas, K, use_vis, in_vis_thre) > thresh;
+      const unsigned long long hit = __ballot(dead);
+      __syncthreads();
+      if (lane == 0) alive[c0 >> 6] = word & ~hit;
+      __syncthreads();
+    }
+  }
+  for (int p = lane; p < n_all; p += 64) keep[base + p] = p < n ? (int)((alive[p >> 6] >> (p & 63)) & 1ull) : 0;
+}
+
+struct KptMatchArgs {
+  int K, n_thr, n_area;
+  long gt_total, dt_total;
+  const int* dt_off;
+  const int* gt_off;
+  const long* oks_off;
+  const float* dt_kpts;
+  const double* gt_kpts;
+  const double* gt_area;
+  const double* gt_bbox;
+  const int* gt_flags;
+  const double* sigmas;
+  const double* thrs;
+  const double* area_rng;
+  double* oks;
+  int* dt_matched;
+  int* dt_ignored;
+  int* gt_order;             // workspace [n_area][gt_total]
+  unsigned char* gt_taken;   // workspace [n_area * n_thr][gt_total]
+};
+
+__device__ __forceinline__ bool out_of_range(double area, const double* __restrict__ rng) {
+  return area < rng[0] || area > rng[1];
+}
+
+// One wavefront per image.  (a) the D x G OKS matrix of computeOks; (b) evaluateImg: one lane per (area range,
+// threshold) walks the detections in score order over the ground truths sorted non-ignored first.
+__global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int K = A.K;
+  const int d0 = A.dt_off[img], D = A.dt_off[img + 1] - d0;
+  const int g0 = A.gt_off[img], G = A.gt_off[img + 1] - g0;
+  if (D <= 0 || G <= 0) {
+    // no matrix: every detection is unmatched, and ignored where its own area lies outside the range
+    for (int idx = lane; idx < D * A.n_area * A.n_thr; idx += 64) {
+      const int d = idx % D, l = idx / D, a = l / A.n_thr;
+      const float* dk = A.dt_kpts + (long)(d0 + d) * K * 3;
+      double x0 = dk[0], x1 = dk[0], y0 = dk[1], y1 = dk[1];
+      for (int j = 1; j < K; ++j) {
+        x0 = fmin(x0, (double)dk[j * 3]); x1 = fmax(x1, (double)dk[j * 3]);
+        y0 = fmin(y0, (double)dk[j * 3 + 1]); y1 = fmax(y1, (double)dk[j * 3 + 1]);
+      }
+      A.dt_matched[(long)l * A.dt_total + d0 + d] = 0;
+      A.dt_ignored[(long)l * A.dt_total + d0 + d] = out_of_range((x1 - x0) * (y1 - y0), A.area_rng + 2 * a) ? 1 : 0;
+    }
+    return;
+  }
+  double* oks = A.oks + A.oks_off[img];
+  for (long idx = lane; idx < (long)D * G; idx += 64) {
+    const int d = (int)(idx / G), g = (int)(idx % G);
+    const float* dk = A.dt_kpts + (long)(d0 + d) * K * 3;
+    const double* gk = A.gt_kpts + (long)(g0 + g) * K * 3;
+    int k1 = 0;
+    for (int j = 0; j < K; ++j) k1 += gk[j * 3 + 2] > 0 ? 1 : 0;
+    const double* bb = A.gt_bbox + (long)(g0 + g) * 4;
+    const double bx0 = bb[0] - bb[2], bx1 = bb[0] + bb[2] * 2, by0 = bb[1] - bb[3], by1 = bb[1] + bb[3] * 2;
+    const double den = A.gt_area[g0 + g] + KPT_SPACING1;
+    double sum = 0.0;
+    int cnt = 0;
+    for (int j = 0; j < K; ++j) {
+      const double xd = dk[j * 3], yd = dk[j * 3 + 1];
+      double dx, dy;
+      if (k1 > 0) {
+        if (!(gk[j * 3 + 2] > 0)) continue;
+        dx = xd - gk[j * 3];
+        dy = yd - gk[j * 3 + 1];
+      } else {
+        dx = fmax(0.0, bx0 - xd) + fmax(0.0, xd - bx1);
+        dy = fmax(0.0, by0 - yd) + fmax(0.0, yd - by1);
+      }
+      const double var = (A.sigmas[j] * 2) * (A.sigmas[j] * 2);
+      sum += exp(-((dx * dx + dy * dy) / var / den / 2));
+      ++cnt;
+    }
+    oks[idx] = sum / cnt;
+  }
+  // ground truths stably sorted by the ignore flag, per area range (lane a), and the taken flags cleared
+  if (lane < A.n_area) {
+    int* ord = A.gt_order + (long)lane * A.gt_total + g0;
+    int w = 0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int g = 0; g < G; ++g) {
+        const int ig = (A.gt_flags[g0 + g] != 0 || out_of_range(A.gt_area[g0 + g], A.area_rng + 2 * lane)) ? 1 : 0;
+        if (ig == pass) ord[w++] = g;
+      }
+  }
+  for (long idx = lane; idx < (long)A.n_area * A.n_thr * G; idx += 64)
+    A.gt_taken[(idx / G) * A.gt_total + g0 + idx % G] = 0;
+  __syncthreads();
+  if (lane >= A.n_area * A.n_thr) return;
+  const int a = lane / A.n_thr;
+  const double thr = A.thrs[lane % A.n_thr];
+  const double* rng = A.area_rng + 2 * a;
+  const int* ord = A.gt_order + (long)a * A.gt_total + g0;
+  unsigned char* taken = A.gt_taken + (long)lane * A.gt_total + g0;
+  for (int d = 0; d < D; ++d) {
+    double best = fmin(thr, 1 - 1e-10);
+    int m = -1, m_ig = 0;
+    for (int gi = 0; gi < G; ++gi) {
+      const int g = ord[gi];
+      const int flags = A.gt_flags[g0 + g];
+      const int ig = (flags != 0 || out_of_range(A.gt_area[g0 + g], rng)) ? 1 : 0;
+      if (taken[g] && !(flags & 1)) continue;       // matched already and not a crowd
+      if (m > -1 && m_ig == 0 && ig == 1) break;    // a non-ignored match stands; only ignored ones follow
+      const double v = oks[(long)d * G + g];
+      if (v < best) continue;
+      best = v;
+      m = g;
+      m_ig = ig;
+    }
+    const long o = (long)lane * A.dt_total + d0 + d;
+    if (m == -1) {
+      const float* dk = A.dt_kpts + (long)(d0 + d) * K * 3;
+      double x0 = dk[0], x1 = dk[0], y0 = dk[1], y1 = dk[1];
+      for (int j = 1; j < K; ++j) {
+        x0 = fmin(x0, (double)dk[j * 3]); x1 = fmax(x1, (double)dk[j * 3]);
+        y0 = fmin(y0, (double)dk[j * 3 + 1]); y1 = fmax(y1, (double)dk[j * 3 + 1]);
+      }
+      A.dt_matched[o] = 0;
+      A.dt_ignored[o] = out_of_range((x1 - x0) * (y1 - y0), rng) ? 1 : 0;
+    } else {
+      A.dt_matched[o] = g0 + m + 1;
+      A.dt_ignored[o] = m_ig;
+      taken[m] = 1;
+    }
+  }
+}
+
+extern "C" int buctd_kpt_rescore(const float* preds, const double* box_in, int n, int K, double in_vis_thre,
+                                 double* score, double* box_score, double* keypoint_score, void* stream) {
+  BUCTD_CHECK_ARG(n >= 0 && K > 0, "buctd_kpt_rescore: bad argument");
+  if (n == 0) return BUCTD_OK;
+  BUCTD_CHECK_ARG(preds && box_in && score && box_score && keypoint_score, "buctd_kpt_rescore: null pointer");
+  hipLaunchKernelGGL(kpt_rescore_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, n, K, in_vis_thre, preds,
+                     box_in, score, box_score, keypoint_score);
+  BUCTD_CHECK_LAUNCH("buctd_kpt_rescore");
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_oks_nms_grouped(const int* offsets, int images, int max_per_image, const float* kpts,
+                                     const double* areas, const double* sigmas, int K, double thresh, int use_vis,
+                                     double in_vis_thre, int* keep, void* stream) {
+  BUCTD_CHECK_ARG(images >= 0 && K > 0 && max_per_image >= 0, "buctd_oks_nms_grouped: bad argument");
+  if (images == 0 || max_per_image == 0) return BUCTD_OK;
+  BUCTD_CHECK_ARG(offsets && kpts && areas && sigmas && keep, "buctd_oks_nms_grouped: null pointer");
+  const int cap_words = ceil_div(max_per_image, 64);
+  BUCTD_CHECK_ARG((size_t)cap_words * 8 <= 64 * 1024, "buctd_oks_nms_grouped: more than 524288 persons in one image");
+  hipLaunchKernelGGL(oks_nms_grouped_kernel, dim3(images), dim3(64), (size_t)cap_words * 8, (hipStream_t)stream, K,
+                     cap_words, thresh, use_vis, in_vis_thre, offsets, kpts, areas, sigmas, keep);
+  BUCTD_CHECK_LAUNCH("buctd_oks_nms_grouped");
+  return BUCTD_OK;
+}
+
+extern "C" size_t buctd_coco_kpt_match_workspace(long gt_total, int n_thr, int n_area) {
+  if (gt_total <= 0 || n_thr <= 0 || n_area <= 0) return 0;
+  return (size_t)gt_total * n_area * sizeof(int) + (size_t)gt_total * n_area * n_thr;
+}
+
+extern "C" int buctd_coco_kpt_match(const buctd_kpt_match_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  BUCTD_CHECK_ARG(a && a->images >= 0 && a->K > 0 && a->dt_total >= 0 && a->gt_total >= 0, "buctd_coco_kpt_match: bad argument");
+  BUCTD_CHECK_ARG(a->n_thr > 0 && a->n_area > 0 && a->n_thr * a->n_area <= 64,
+                  "buctd_coco_kpt_match: one lane per (area range, threshold): at most 64 pairs");
+  if (a->images == 0 || a->dt_total == 0) return BUCTD_OK;
+  BUCTD_CHECK_ARG(a->dt_total * (long)a->n_thr * a->n_area < (1l << 31) && a->gt_total < (1l << 31),
+                  "buctd_coco_kpt_match: table too large");
+  BUCTD_CHECK_ARG(a->dt_offsets && a->gt_offsets && a->oks_offsets && a->dt_kpts && a->sigmas && a->thresholds &&
+                      a->area_ranges && a->dt_matched && a->dt_ignored,
+                  "buctd_coco_kpt_match: null pointer");
+  BUCTD_CHECK_ARG(a->gt_total == 0 || (a->gt_kpts && a->gt_area && a->gt_bbox && a->gt_flags && a->oks),
+                  "buctd_coco_kpt_match: null ground-truth pointer");
+  const size_t need = buctd_coco_kpt_match_workspace(a->gt_total, a->n_thr, a->n_area);
+  if (need && (!workspace || workspace_bytes < need)) {
+    buctd_set_error("buctd_coco_kpt_match: workspace %zu bytes < required %zu", workspace_bytes, need);
+    return BUCTD_EWORKSPACE;
+  }
+  KptMatchArgs k;
+  k.K = a->K; k.n_thr = a->n_thr; k.n_area = a->n_area;
+  k.gt_total = a->gt_total; k.dt_total = a->dt_total;
+  k.dt_off = a->dt_offsets; k.gt_off = a->gt_offsets; k.oks_off = a->oks_offsets;
+  k.dt_kpts = a->dt_kpts; k.gt_kpts = a->gt_kpts; k.gt_area = a->gt_area; k.gt_bbox = a->gt_bbox;
+  k.gt_flags = a->gt_flags; k.sigmas = a->sigmas; k.thrs = a->thresholds; k.area_rng = a->area_ranges;
+  k.oks = a->oks; k.dt_matched = a->dt_matched; k.dt_ignored = a->dt_ignored;
+  k.gt_order = (int*)workspace;
+  k.gt_taken = (unsigned char*)workspace + (size_t)a->gt_total * a->n_area * sizeof(int);
+  hipLaunchKernelGGL(coco_kpt_match_kernel, dim3(a->images), dim3(64), 0, (hipStream_t)stream, k);
+  BUCTD_CHECK_LAUNCH("buctd_coco_kpt_match");
+  return BUCTD_OK;
+}

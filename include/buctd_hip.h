@@ -879,6 +879,58 @@ int buctd_nms(int* keep_out, int* num_out, const float* boxes, int boxes_num, in
  * order = argsort of the scores, descending, computed by the caller like the .pyx does with numpy. */
 int buctd_cpu_nms(const float* dets, int n, const int* order, float thresh, int* keep_out, int* num_out);
 
+/* ------------------------------------------------------- keypoint evaluation --- */
+/* The device part of core/keypoint_eval.py (csrc/keypoint_eval.hip): what the reference's data set classes do in
+ * evaluate() with Python loops around lib/nms/nms.py and pycocotools.COCOeval (lib/dataset/dataloader.py:590-634,
+ * 719-735).  All arithmetic is fp64.  Persons and ground truths are grouped by image with CSR offsets (int32
+ * [images + 1]); the caller groups and, within an image, sorts persons by descending score (stable). */
+/* Rescoring (dataloader.py:598-612): preds float32 [n][K][3] (x, y, joint score), box_in [n].  keypoint_score = mean of
+ * the joint scores > in_vis_thre, added in joint order (0 if none); score = keypoint_score * box score; box_score is
+ * the box score itself. */
+int buctd_kpt_rescore(const float* preds, const double* box_in, int n, int K, double in_vis_thre, double* score,
+                      double* box_score, double* keypoint_score, void* stream);
+/* Greedy OKS suppression within every image (oks_nms / oks_iou of lib/nms/nms.py:75-124): one wavefront per image
+ * walks its persons in the given (score) order; a kept person clears every later one whose OKS to it is > thresh.
+ * OKS: variances (2 sigma)^2, scale = mean of the two areas + spacing(1); use_vis != 0 counts only the joints whose
+ * score in the candidate is > in_vis_thre (OKS 0 if none).  kpts float32 [total][K][3], areas [total], sigmas [K];
+ * keep int32 [total]: 1 kept, 0 suppressed.  max_per_image must be at least the largest group (it sizes the alive
+ * bitmap in LDS, at most 524288); persons of a larger group beyond it are reported suppressed. */
+int buctd_oks_nms_grouped(const int* offsets, int images, int max_per_image, const float* kpts, const double* areas,
+                          const double* sigmas, int K, double thresh, int use_vis, double in_vis_thre, int* keep,
+                          void* stream);
+/* COCO keypoint matching, per image: (a) the D x G matrix of COCOeval.computeOks - variances (2 sigma)^2, denominator
+ * gt area + spacing(1), the visible ground-truth joints where there are any, otherwise the distance to the doubled
+ * box (x0 = bx - bw, x1 = bx + 2 bw, likewise y) - written row-major to oks + oks_offsets[image]; (b) the greedy
+ * matchings of COCOeval.evaluateImg, one per (area range, threshold) pair, at most 64 pairs.
+ * Detections: the image's kept persons in score order, already cut to the detection limit; dt_kpts float32
+ * [dt_total][K][3].  Ground truths: gt_kpts [gt_total][K][3] (x, y, v), gt_area, gt_bbox [gt_total][4] (x, y, w, h),
+ * gt_flags int32 (bit 0: iscrowd, bit 1: num_keypoints == 0; non-zero = ignored in every range).
+ * thresholds [n_thr], area_ranges [n_area][2] (lo, hi: outside = area < lo or area > hi).
+ * dt_matched / dt_ignored int32 [n_area][n_thr][dt_total]: dt_matched = 1 + the ground truth's row (0: unmatched);
+ * dt_ignored = the matched ground truth's ignore flag, or, unmatched, whether the extent box of the detection's
+ * key points (max x - min x)(max y - min y) lies outside the range.  The workspace holds the per-range ground-truth
+ * order and the per-pair taken flags, so the number of ground truths of an image is unbounded. */
+typedef struct {
+  int images, K, n_thr, n_area;
+  long dt_total, gt_total;
+  const int* dt_offsets;
+  const int* gt_offsets;
+  const long* oks_offsets; /* [images + 1], oks_offsets[i + 1] - oks_offsets[i] = D_i * G_i */
+  const float* dt_kpts;
+  const double* gt_kpts;
+  const double* gt_area;
+  const double* gt_bbox;
+  const int* gt_flags;
+  const double* sigmas;
+  const double* thresholds;
+  const double* area_ranges;
+  double* oks;
+  int* dt_matched;
+  int* dt_ignored;
+} buctd_kpt_match_args;
+size_t buctd_coco_kpt_match_workspace(long gt_total, int n_thr, int n_area);
+int buctd_coco_kpt_match(const buctd_kpt_match_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------- bf16 inference --- */
 /* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).
  * bf16 tensors are passed as raw bit patterns (uint16_t).  Activations bf16 NHWC [N][H][W][C]; a conv layer is a

@@ -274,6 +274,8 @@ SIGNATURES = {
     "buctd_oks_nms_grouped": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, _I, _D, _P, _P]),
     "buctd_coco_kpt_match_workspace": (_SZ, [_L, _I, _I]),
     "buctd_coco_kpt_match": (_I, [C.POINTER(KptMatchArgs), _P, _SZ, _P]),
+    "buctd_kpt_crowding": (_I, [_P, _I, _L, _I, _P, _P, _P, _P, _D, _P, _P, _P]),
+    "buctd_kpt_segment_ap": (_I, [_P, _I, _I, _L, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),

@@ -124,6 +124,14 @@ class KeypointEvaluator:
         self.gt_area = np.array([a['area'] for a in anns], dtype=np.float64).reshape(G)
         self.gt_flags = np.array([(1 if a.get('iscrowd', 0) else 0) | (2 if a['num_keypoints'] == 0 else 0) for a in anns],
                                  dtype=np.int32).reshape(G)
+        # what core.keypoint_analysis reads besides the tables above: image sizes (nan where the set carries none), the
+        # annotations' num_keypoints field and a stored num_overlaps (-1 where there is none)
+        self.image_wh = np.array([[im.get('width', np.nan), im.get('height', np.nan)] for im in images],
+                                 dtype=np.float64).reshape(len(images), 2)
+        self.gt_image = np.repeat(np.arange(len(images), dtype=np.int64), self.gt_counts)
+        self.gt_num_keypoints = np.array([int(a['num_keypoints']) for a in anns], dtype=np.int64).reshape(G)
+        self.gt_num_overlaps = np.array([int(a.get('num_overlaps', -1)) for a in anns], dtype=np.int64).reshape(G)
+        self.gt_has_num_overlaps = np.array(['num_overlaps' in a for a in anns], dtype=bool).reshape(G)
         kp = np.array([a['keypoints'] for a in anns], dtype=np.float64).reshape(G, self.K, 3)
         bb = np.array([a['bbox'] for a in anns], dtype=np.float64).reshape(G, 4)
         out = (self.gt_area[None, :] < AREA_RNG[:, :1]) | (self.gt_area[None, :] > AREA_RNG[:, 1:])
@@ -141,10 +149,14 @@ class KeypointEvaluator:
         except KeyError:
             raise KeyError(f"img_path entry {path!r} has no image id in the annotation set") from None
 
-    def evaluate(self, cfg, preds, output_dir, all_boxes, img_path, epoch=-1, *args, **kwargs):
+    def _kept_persons(self, preds, all_boxes, img_path):
+        """Steps 1-2 of evaluate(), shared with core.keypoint_analysis: the tables are checked, every person is rescored,
+        the persons are grouped (images by id, descending score within an image, equal scores in input order) and the
+        suppression runs within every image.  Returns a dict: preds / all_boxes as checked, person_image_id, img (image
+        position per person), order_h (input row of each grouped person), keep_h (mask over the grouped persons), offsets /
+        counts (CSR of the groups), kp_s (the grouped key points on the device) and the three score vectors on the host."""
         import torch
-        from .. import ops
-        from .._C import KptMatchArgs, check, lib, ptr, stream_ptr
+        from .._C import check, lib, ptr, stream_ptr
         preds = np.ascontiguousarray(preds, dtype=np.float32)
         all_boxes = np.asarray(all_boxes, dtype=np.float64)
         N = preds.shape[0]
@@ -158,7 +170,6 @@ class KeypointEvaluator:
         except KeyError as e:
             raise KeyError(f"image id {e.args[0]} is not in the annotation set") from None
         I, K, dev, d = len(self.image_ids), self.K, self.device, self._d
-        A, T = AREA_RNG.shape[0], IOU_THRS.shape[0]
 
         with torch.cuda.device(dev):
             st = stream_ptr()
@@ -188,36 +199,64 @@ class KeypointEvaluator:
                       "oks_nms_grouped")
             order_h = order.cpu().numpy()
             keep_h = keep_s.cpu().numpy().astype(bool)
-            score_h = score.cpu().numpy()
-            # detections: the kept persons of an image by score, at most max_dets
-            img_s = img[order_h]
-            rank = np.cumsum(keep_h) - keep_h
-            rank = rank - np.repeat(rank[offsets[:-1][counts > 0]], counts[counts > 0])
-            dt_pos = np.flatnonzero(keep_h & (rank < self.max_dets))
-            dt_counts = np.bincount(img_s[dt_pos], minlength=I)
-            dt_offsets = np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int32)
-            Dt = int(dt_pos.shape[0])
-            oks_offsets = np.concatenate([[0], np.cumsum(dt_counts * self.gt_counts)]).astype(np.int64)
-            # 3. OKS matrices + the A x T greedy matchings per image
+            return dict(preds=preds, all_boxes=all_boxes, person_image_id=person_image_id, img=img, order_h=order_h,
+                        keep_h=keep_h, offsets=offsets, counts=counts, kp_s=kp_s, score_h=score.cpu().numpy(),
+                        box_score_h=box_score.cpu().numpy(), kpt_score_h=kpt_score.cpu().numpy())
+
+    def _match(self, dt_kpts, dt_counts, gt_counts, gt=None):
+        """Step 3 of evaluate(), shared with core.keypoint_analysis: the OKS matrices and the A x T greedy matchings of
+        `images` = len(dt_counts) detection / ground-truth groups.  dt_kpts: device tensor [Dt][K][3] in group order;
+        gt: the device tables gt_kpts / gt_area / gt_bbox / gt_flags in group order (default: the evaluator's own).
+        Returns oks_offsets (host) and the device tensors oks, dt_matched, dt_ignored."""
+        import torch
+        from .. import ops
+        from .._C import KptMatchArgs, check, lib, ptr, stream_ptr
+        dev, d = self.device, self._d
+        gt = d if gt is None else gt
+        A, T = AREA_RNG.shape[0], IOU_THRS.shape[0]
+        dt_counts, gt_counts = np.asarray(dt_counts, dtype=np.int64), np.asarray(gt_counts, dtype=np.int64)
+        dt_offsets = np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int32)
+        gt_offsets = np.concatenate([[0], np.cumsum(gt_counts)]).astype(np.int32)
+        oks_offsets = np.concatenate([[0], np.cumsum(dt_counts * gt_counts)]).astype(np.int64)
+        Dt, G = int(dt_offsets[-1]), int(gt_offsets[-1])
+        with torch.cuda.device(dev):
             oks = torch.zeros(max(int(oks_offsets[-1]), 1), dtype=torch.float64, device=dev)
             dt_matched = torch.zeros((A, T, Dt), dtype=torch.int32, device=dev)
             dt_ignored = torch.zeros((A, T, Dt), dtype=torch.int32, device=dev)
             if Dt:
-                dt_kpts = kp_s[torch.as_tensor(dt_pos).to(dev)].contiguous()
                 dt_off_t = torch.as_tensor(dt_offsets).to(dev)
+                gt_off_t = torch.as_tensor(gt_offsets).to(dev)
                 oks_off_t = torch.as_tensor(oks_offsets).to(dev)
-                G = int(self.gt_offsets[-1])
                 ws = ops.workspace(lib().buctd_coco_kpt_match_workspace(G, T, A), dev)
-                m = KptMatchArgs(images=I, K=K, n_thr=T, n_area=A, dt_total=Dt, gt_total=G, dt_offsets=ptr(dt_off_t),
-                                 gt_offsets=ptr(d['gt_off']), oks_offsets=ptr(oks_off_t), dt_kpts=ptr(dt_kpts),
-                                 gt_kpts=ptr(d['gt_kpts']), gt_area=ptr(d['gt_area']), gt_bbox=ptr(d['gt_bbox']),
-                                 gt_flags=ptr(d['gt_flags']), sigmas=ptr(d['sigmas']), thresholds=ptr(d['thrs']),
-                                 area_ranges=ptr(d['area_rng']), oks=ptr(oks), dt_matched=ptr(dt_matched),
-                                 dt_ignored=ptr(dt_ignored))
-                check(lib().buctd_coco_kpt_match(C.byref(m), ptr(ws), ws.numel(), st), "coco_kpt_match")
+                m = KptMatchArgs(images=len(dt_counts), K=self.K, n_thr=T, n_area=A, dt_total=Dt, gt_total=G,
+                                 dt_offsets=ptr(dt_off_t), gt_offsets=ptr(gt_off_t), oks_offsets=ptr(oks_off_t),
+                                 dt_kpts=ptr(dt_kpts), gt_kpts=ptr(gt['gt_kpts']), gt_area=ptr(gt['gt_area']),
+                                 gt_bbox=ptr(gt['gt_bbox']), gt_flags=ptr(gt['gt_flags']), sigmas=ptr(d['sigmas']),
+                                 thresholds=ptr(d['thrs']), area_ranges=ptr(d['area_rng']), oks=ptr(oks),
+                                 dt_matched=ptr(dt_matched), dt_ignored=ptr(dt_ignored))
+                check(lib().buctd_coco_kpt_match(C.byref(m), ptr(ws), ws.numel(), stream_ptr()), "coco_kpt_match")
+        return oks_offsets, oks, dt_matched, dt_ignored
+
+    def evaluate(self, cfg, preds, output_dir, all_boxes, img_path, epoch=-1, *args, **kwargs):
+        import torch
+        p = self._kept_persons(preds, all_boxes, img_path)
+        preds, all_boxes, person_image_id = p['preds'], p['all_boxes'], p['person_image_id']
+        N, I, dev = preds.shape[0], len(self.image_ids), self.device
+        order_h, keep_h, offsets, counts, score_h = p['order_h'], p['keep_h'], p['offsets'], p['counts'], p['score_h']
+        # detections: the kept persons of an image by score, at most max_dets
+        img_s = p['img'][order_h]
+        rank = np.cumsum(keep_h) - keep_h
+        rank = rank - np.repeat(rank[offsets[:-1][counts > 0]], counts[counts > 0])
+        dt_pos = np.flatnonzero(keep_h & (rank < self.max_dets))
+        dt_counts = np.bincount(img_s[dt_pos], minlength=I)
+        dt_offsets = np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int32)
+        # 3. OKS matrices + the A x T greedy matchings per image
+        with torch.cuda.device(dev):
+            dt_kpts = p['kp_s'][torch.as_tensor(dt_pos).to(dev)].contiguous()
+            oks_offsets, oks, dt_matched, dt_ignored = self._match(dt_kpts, dt_counts, self.gt_counts)
             oks_h = oks.cpu().numpy()[:int(oks_offsets[-1])]
             dtm_h, dti_h = dt_matched.cpu().numpy(), dt_ignored.cpu().numpy()
-            box_score_h, kpt_score_h = box_score.cpu().numpy(), kpt_score.cpu().numpy()
+        box_score_h, kpt_score_h = p['box_score_h'], p['kpt_score_h']
 
         dt_rows = order_h[dt_pos]
         precision, recall = accumulate(score_h[dt_rows], dtm_h, dti_h, self.npig)

@@ -1,7 +1,8 @@
 // Keypoint evaluation on the device (core/keypoint_eval.py): the rescoring and grouped OKS NMS of the reference's
 // data set classes (lib/dataset/dataloader.py:590-634 around lib/nms/nms.py:75-124) and the per-image part of the
 // published COCO keypoint evaluation (computeOks + evaluateImg).  Everything is fp64: a match is a comparison against
-// a threshold, and the data is a few MB.
+// a threshold, and the data is a few MB.  The crowding analysis (core/keypoint_analysis.py, the reference's
+// lib/analysis/evaluation.py) adds the overlap count per ground truth and a per-segment accumulate + summarize.
 //
 // MI355X shape of the problem: each image is a wave-sized job that exists thousands of times, so one wave64 wavefront
 // takes one image - lanes stride over the candidates of an NMS step, over the cells of the OKS matrix, and one lane
@@ -216,6 +217,126 @@ __global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
   }
 }
 
+// max / min as Python's built-ins state them for two arguments (the second only where it compares strictly).
+__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
+__device__ __forceinline__ double py_min(double a, double b) { return b < a ? b : a; }
+
+// compute_iou of lib/utils/utils.py:557-588 on two (x, y, w, h) boxes: the same operations in the same order, so that
+// with -ffp-contract=off the value equals the host's bit for bit.
+__device__ __forceinline__ double box_iou(const double* __restrict__ b1, const double* __restrict__ b2) {
+  const double x1_l = b1[0], x1_r = b1[0] + b1[2], y1_t = b1[1], y1_b = b1[1] + b1[3], w1 = b1[2], h1 = b1[3];
+  const double x2_l = b2[0], x2_r = b2[0] + b2[2], y2_t = b2[1], y2_b = b2[1] + b2[3], w2 = b2[2], h2 = b2[3];
+  const double xi_l = py_max(x1_l, x2_l), xi_r = py_min(x1_r, x2_r);
+  const double yi_t = py_max(y1_t, y2_t), yi_b = py_min(y1_b, y2_b);
+  const double width = py_max(0.0, xi_r - xi_l), height = py_max(0.0, yi_b - yi_t);
+  const double a1 = w1 * h1, a2 = w2 * h2;
+  const double inter = width * height;
+  const double den = a1 + a2 - inter;
+  if (den == 0) return 0.0;
+  return inter / den;
+}
+
+// check_valid_annotations of lib/analysis/evaluation.py:132-178, one wavefront per image.  Pass 1: lanes stride over
+// the image's ground truths and write `valid`; pass 2: a valid one counts the other valid ones it overlaps.
+__global__ __launch_bounds__(64) void kpt_crowding_kernel(int K, double thresh, const int* __restrict__ off,
+                                                          const double* __restrict__ bbox, const double* __restrict__ kpts,
+                                                          const double* __restrict__ area, const double* __restrict__ image_wh,
+                                                          int* valid, int* __restrict__ num_overlaps) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int g0 = off[img], G = off[img + 1] - g0;
+  const double W = image_wh[img * 2], H = image_wh[img * 2 + 1];
+  for (int g = lane; g < G; g += 64) {
+    const double* kp = kpts + (long)(g0 + g) * K * 3;
+    double top = kp[0];
+    for (int j = 1; j < K * 3; ++j) top = py_max(top, kp[j]);
+    const double* b = bbox + (long)(g0 + g) * 4;
+    const double x1 = py_max(0.0, b[0]), y1 = py_max(0.0, b[1]);
+    const double x2 = py_min(W - 1, x1 + py_max(0.0, b[2] - 1));
+    const double y2 = py_min(H - 1, y1 + py_max(0.0, b[3] - 1));
+    valid[g0 + g] = (top != 0 && area[g0 + g] > 0 && x2 >= x1 && y2 >= y1) ? 1 : 0;
+  }
+  __syncthreads();
+  for (int g = lane; g < G; g += 64) {
+    int n = -1;
+    if (valid[g0 + g]) {
+      n = 0;
+      for (int h = 0; h < G; ++h) {
+        if (h == g || !valid[g0 + h]) continue;
+        const int lo = min(g, h), hi = max(g, h);                   // compute_ious fills [i][j] for i < j and mirrors it
+        if (box_iou(bbox + (long)(g0 + lo) * 4, bbox + (long)(g0 + hi) * 4) > thresh) ++n;
+      }
+    }
+    num_overlaps[g0 + g] = n;
+  }
+}
+
+#define KPT_SEG_MAX 64
+
+// COCOeval accumulate + summarize for one segment per wavefront (core/keypoint_eval.py: accumulate, summarize).  Lane
+// l = a * n_thr + t owns the (area range, threshold) pair of the matching kernel's lane l: cumulative tp / fp over the
+// segment's detections (already in descending score order), the precision envelope from the right, the left
+// searchsorted of every recall threshold.  Then lanes 0-9 form the ten figures, adding over t in index order.
+__global__ __launch_bounds__(64) void kpt_segment_ap_kernel(int max_len, long dt_total, int n_area, int n_thr, int n_rec,
+                                                            int t_half, int t_three_q, const int* __restrict__ seg_off,
+                                                            const int* __restrict__ dt_matched,
+                                                            const int* __restrict__ dt_ignored, const int* __restrict__ npig,
+                                                            const double* __restrict__ rec_thrs, double* __restrict__ stats,
+                                                            double* __restrict__ recall) {
+  __shared__ double pr[KPT_SEG_MAX][64];          // [detection][lane]: a lane's column, no bank shared within a half-wave
+  __shared__ unsigned char tps[KPT_SEG_MAX][64];
+  __shared__ double lane_pr[64], lane_rc[64];     // per pair: sum of its n_rec precision values, its recall; -1 = not counted
+  const int seg = blockIdx.x, lane = threadIdx.x;
+  const int d0 = seg_off[seg];
+  const int D = min(seg_off[seg + 1] - d0, min(max_len, KPT_SEG_MAX));
+  const bool active = lane < n_area * n_thr;
+  const int a = lane / n_thr, t = lane % n_thr;
+  double p_sum = -1.0, rc_last = -1.0;
+  const int np = active ? npig[(long)seg * n_area + a] : 0;
+  if (active && np != 0) {
+    const int* m = dt_matched + (long)lane * dt_total + d0;
+    const int* ig = dt_ignored + (long)lane * dt_total + d0;
+    int tp = 0, fp = 0;
+    for (int d = 0; d < D; ++d) {
+      const bool matched = m[d] != 0, ignored = ig[d] != 0;
+      tp += (matched && !ignored) ? 1 : 0;
+      fp += (!matched && !ignored) ? 1 : 0;
+      tps[d][lane] = (unsigned char)tp;
+      pr[d][lane] = (double)tp / ((double)fp + (double)tp + KPT_SPACING1);
+    }
+    for (int d = D - 1; d > 0; --d)
+      if (pr[d][lane] > pr[d - 1][lane]) pr[d - 1][lane] = pr[d][lane];
+    rc_last = D > 0 ? (double)tp / (double)np : 0.0;
+    p_sum = 0.0;
+    int at = 0;                                   // recall thresholds ascend and rc does not descend: one walk
+    for (int r = 0; r < n_rec; ++r) {
+      const double thr = rec_thrs[r];
+      while (at < D && (double)tps[at][lane] / (double)np < thr) ++at;
+      if (at < D) p_sum = p_sum + pr[at][lane];
+    }
+  }
+  lane_pr[lane] = p_sum;
+  lane_rc[lane] = rc_last;
+  if (active) recall[((long)seg * n_thr + t) * n_area + a] = rc_last;
+  __syncthreads();
+  if (lane >= 10) return;
+  // figure f: precision (f < 5) or recall; all / one threshold; area range 0 (all), 1 (medium), 2 (large)
+  const int f = lane % 5;
+  const bool is_pr = lane < 5;
+  const int ar = f == 3 ? 1 : f == 4 ? 2 : 0;
+  const int t_lo = f == 1 ? t_half : f == 2 ? t_three_q : 0;
+  const int t_hi = (f == 1 || f == 2) ? t_lo + 1 : n_thr;
+  double sum = 0.0;
+  long cnt = 0;
+  for (int tt = t_lo; tt < t_hi; ++tt) {
+    const double v = is_pr ? lane_pr[ar * n_thr + tt] : lane_rc[ar * n_thr + tt];
+    if (v > -1) {
+      sum = sum + v;
+      cnt += is_pr ? n_rec : 1;
+    }
+  }
+  stats[(long)seg * 10 + lane] = cnt > 0 ? sum / (double)cnt : -1.0;
+}
+
 extern "C" int buctd_kpt_rescore(const float* preds, const double* box_in, int n, int K, double in_vis_thre,
                                  double* score, double* box_score, double* keypoint_score, void* stream) {
   BUCTD_CHECK_ARG(n >= 0 && K > 0, "buctd_kpt_rescore: bad argument");
@@ -274,5 +395,42 @@ extern "C" int buctd_coco_kpt_match(const buctd_kpt_match_args* a, void* workspa
   k.gt_taken = (unsigned char*)workspace + (size_t)a->gt_total * a->n_area * sizeof(int);
   hipLaunchKernelGGL(coco_kpt_match_kernel, dim3(a->images), dim3(64), 0, (hipStream_t)stream, k);
   BUCTD_CHECK_LAUNCH("buctd_coco_kpt_match");
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_kpt_crowding(const int* gt_offsets, int images, long gt_total, int K, const double* gt_bbox,
+                                  const double* gt_kpts, const double* gt_area, const double* image_wh, double iou_thresh,
+                                  int* valid, int* num_overlaps, void* stream) {
+  BUCTD_CHECK_ARG(images >= 0 && gt_total >= 0 && K > 0, "buctd_kpt_crowding: bad argument");
+  if (images == 0 || gt_total == 0) return BUCTD_OK;
+  BUCTD_CHECK_ARG(gt_total * (long)K * 3 < (1l << 31), "buctd_kpt_crowding: table too large");
+  BUCTD_CHECK_ARG(gt_offsets && gt_bbox && gt_kpts && gt_area && image_wh && valid && num_overlaps,
+                  "buctd_kpt_crowding: null pointer");
+  hipLaunchKernelGGL(kpt_crowding_kernel, dim3(images), dim3(64), 0, (hipStream_t)stream, K, iou_thresh, gt_offsets, gt_bbox,
+                     gt_kpts, gt_area, image_wh, valid, num_overlaps);
+  BUCTD_CHECK_LAUNCH("buctd_kpt_crowding");
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_kpt_segment_ap(const int* seg_offsets, int segments, int max_seg_len, long dt_total,
+                                    const int* dt_matched, const int* dt_ignored, int n_area, int n_thr, const int* npig,
+                                    const double* rec_thrs, int n_rec, int t_half, int t_three_q, double* stats,
+                                    double* recall, void* stream) {
+  BUCTD_CHECK_ARG(segments >= 0 && max_seg_len >= 0 && dt_total >= 0 && n_rec >= 0, "buctd_kpt_segment_ap: bad argument");
+  BUCTD_CHECK_ARG(n_thr > 0 && n_area > 0 && n_thr * n_area <= 64,
+                  "buctd_kpt_segment_ap: one lane per (area range, threshold): at most 64 pairs");
+  BUCTD_CHECK_ARG(n_area >= 3 && t_half >= 0 && t_half < n_thr && t_three_q >= 0 && t_three_q < n_thr,
+                  "buctd_kpt_segment_ap: the figures need the area ranges all, medium, large and two threshold indices");
+  BUCTD_CHECK_ARG(max_seg_len <= KPT_SEG_MAX, "buctd_kpt_segment_ap: a segment holds at most 64 detections");
+  BUCTD_CHECK_ARG(n_rec <= 128, "buctd_kpt_segment_ap: at most 128 recall thresholds");
+  BUCTD_CHECK_ARG(dt_total * (long)n_thr * n_area < (1l << 31), "buctd_kpt_segment_ap: table too large");
+  if (segments == 0) return BUCTD_OK;
+  BUCTD_CHECK_ARG(seg_offsets && npig && stats && recall && (n_rec == 0 || rec_thrs),
+                  "buctd_kpt_segment_ap: null pointer");
+  BUCTD_CHECK_ARG(dt_total == 0 || max_seg_len == 0 || (dt_matched && dt_ignored),
+                  "buctd_kpt_segment_ap: null match table");
+  hipLaunchKernelGGL(kpt_segment_ap_kernel, dim3(segments), dim3(64), 0, (hipStream_t)stream, max_seg_len, dt_total, n_area,
+                     n_thr, n_rec, t_half, t_three_q, seg_offsets, dt_matched, dt_ignored, npig, rec_thrs, stats, recall);
+  BUCTD_CHECK_LAUNCH("buctd_kpt_segment_ap");
   return BUCTD_OK;
 }

@@ -930,6 +930,29 @@ typedef struct {
 } buctd_kpt_match_args;
 size_t buctd_coco_kpt_match_workspace(long gt_total, int n_thr, int n_area);
 int buctd_coco_kpt_match(const buctd_kpt_match_args* a, void* workspace, size_t workspace_bytes, void* stream);
+/* Crowding of the ground truths (check_valid_annotations, lib/analysis/evaluation.py:132-178), one wavefront per image.
+ * valid[g] = the largest of the 3K key point values is not 0, area > 0, and the box cut to the image
+ * (x1 = max(0, x), x2 = min(width - 1, x1 + max(0, w - 1)), likewise y) has x2 >= x1 and y2 >= y1.
+ * num_overlaps[g] = the number of other valid ground truths of the image whose IoU with g is > iou_thresh, -1 where g
+ * is not valid; the IoU is compute_iou of lib/utils/utils.py:557-588 on the raw (x, y, w, h) boxes, operation by
+ * operation (0 where the denominator is 0).  gt_bbox [gt_total][4], gt_kpts [gt_total][K][3], gt_area [gt_total],
+ * image_wh [images][2] (width, height), all fp64; valid / num_overlaps int32 [gt_total]. */
+int buctd_kpt_crowding(const int* gt_offsets, int images, long gt_total, int K, const double* gt_bbox,
+                       const double* gt_kpts, const double* gt_area, const double* image_wh, double iou_thresh, int* valid,
+                       int* num_overlaps, void* stream);
+/* COCOeval accumulate + summarize for `segments` independent small evaluations, one wavefront each, one lane per
+ * (area range, threshold) pair.  seg_offsets int32 [segments + 1] into the detection axis of dt_matched / dt_ignored
+ * ([n_area][n_thr][dt_total] as buctd_coco_kpt_match writes them); a segment's detections are in descending score
+ * order.  max_seg_len must be at least the longest segment and at most 64 (detections beyond it are not read).
+ * npig int32 [segments][n_area]: non-ignored ground truths per area range; rec_thrs [n_rec], n_rec <= 128.
+ * Per pair: rc = tp / npig, pr = tp / (fp + tp + spacing(1)), the precision envelope from the right, the precision at
+ * the left searchsorted position of every recall threshold (0 past the end); -1 where npig == 0; recall 0 and
+ * precision 0 for a segment without detections.  stats [segments][10]: the ten figures of COCOeval.summarize for key
+ * points (AP, AP at thresholds t_half / t_three_q, AP of area ranges 1 and 2, the same five for AR), each the mean of
+ * the entries > -1, added in index order, or -1 where none counts.  recall [segments][n_thr][n_area]. */
+int buctd_kpt_segment_ap(const int* seg_offsets, int segments, int max_seg_len, long dt_total, const int* dt_matched,
+                         const int* dt_ignored, int n_area, int n_thr, const int* npig, const double* rec_thrs, int n_rec,
+                         int t_half, int t_three_q, double* stats, double* recall, void* stream);
 
 /* ------------------------------------------------------------- bf16 inference --- */
 /* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).

@@ -276,6 +276,11 @@ SIGNATURES = {
     "buctd_coco_kpt_match": (_I, [C.POINTER(KptMatchArgs), _P, _SZ, _P]),
     "buctd_kpt_crowding": (_I, [_P, _I, _L, _I, _P, _P, _P, _P, _D, _P, _P, _P]),
     "buctd_kpt_segment_ap": (_I, [_P, _I, _I, _L, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    # condition records (csrc/conditions.hip)
+    "buctd_pose_boxes": (_I, [_P, _I, _I, _I, _P, _D, _P, _P, _P]),
+    "buctd_match_boxes": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "buctd_group_max_iou": (_I, [_P, _I, _P, _I, _P, _P, _P, _P]),
+    "buctd_group_near_list": (_I, [_P, _I, _P, _P, _P, _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),

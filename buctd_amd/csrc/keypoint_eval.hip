@@ -8,6 +8,7 @@
 // takes one image - lanes stride over the candidates of an NMS step, over the cells of the OKS matrix, and one lane
 // runs each of the (area range, threshold) greedy matchings.  These are latency kernels; nothing here is tuned.
 #include "common.h"
+#include "box_iou.h"
 #include "../../include/buctd_hip.h"
 
 #define KPT_SPACING1 2.220446049250313e-16   // np.spacing(1)
@@ -215,25 +216,6 @@ __global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
       taken[m] = 1;
     }
   }
-}
-
-// max / min as Python's built-ins state them for two arguments (the second only where it compares strictly).
-__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ double py_min(double a, double b) { return b < a ? b : a; }
-
-// compute_iou of lib/utils/utils.py:557-588 on two (x, y, w, h) boxes: the same operations in the same order, so that
-// with -ffp-contract=off the value equals the host's bit for bit.
-__device__ __forceinline__ double box_iou(const double* __restrict__ b1, const double* __restrict__ b2) {
-  const double x1_l = b1[0], x1_r = b1[0] + b1[2], y1_t = b1[1], y1_b = b1[1] + b1[3], w1 = b1[2], h1 = b1[3];
-  const double x2_l = b2[0], x2_r = b2[0] + b2[2], y2_t = b2[1], y2_b = b2[1] + b2[3], w2 = b2[2], h2 = b2[3];
-  const double xi_l = py_max(x1_l, x2_l), xi_r = py_min(x1_r, x2_r);
-  const double yi_t = py_max(y1_t, y2_t), yi_b = py_min(y1_b, y2_b);
-  const double width = py_max(0.0, xi_r - xi_l), height = py_max(0.0, yi_b - yi_t);
-  const double a1 = w1 * h1, a2 = w2 * h2;
-  const double inter = width * height;
-  const double den = a1 + a2 - inter;
-  if (den == 0) return 0.0;
-  return inter / den;
 }
 
 // check_valid_annotations of lib/analysis/evaluation.py:132-178, one wavefront per image.  Pass 1: lanes stride over

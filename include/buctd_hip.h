@@ -954,6 +954,46 @@ int buctd_kpt_segment_ap(const int* seg_offsets, int segments, int max_seg_len, 
                          const int* dt_ignored, int n_area, int n_thr, const int* npig, const double* rec_thrs, int n_rec,
                          int t_half, int t_three_q, double* stats, double* recall, void* stream);
 
+/* ------------------------------------------------------- condition records --- */
+/* The device part of dataset/conditions.py (csrc/conditions.hip): from a bottom-up model's poses to the records the
+ * sample pipeline consumes - what the reference does with Python loops in data_preprocessing/match_coco_cond.py:79-103
+ * and lib/dataset/dataloader.py:213-241, 335-393.  All arithmetic is fp64, operation by operation as the reference
+ * states it, so the values equal the host's bit for bit; inputs are finite.  Groups (the poses / annotations of an
+ * image) are CSR offsets, int32 [images + 1]; one wavefront takes one image and its lanes stride over the members, so
+ * a group may have any size.  No function allocates or synchronises. */
+#define BUCTD_POSE_BOX_ALL_POINTS 0
+#define BUCTD_POSE_BOX_NONZERO 1
+/* Boxes of n poses [n][K][3] (x, y, anything), one thread per pose.
+ * BUCTD_POSE_BOX_ALL_POINTS (calc_bboxes_from_keypoints, match_coco_cond.py:19-30): min / max of x and of y over the
+ *   joints with joint_mask[pose][joint] != 0 (int32 [n][K]; NULL: every joint), negative corners set to 0; boxes[pose]
+ *   = x1, y1, x2, y2.  margin is not read.
+ * BUCTD_POSE_BOX_NONZERO (dataloader.py:357-361): min / max of the x != 0 and, separately, of the y != 0; boxes[pose]
+ *   = x, y, w, h = xmin - margin, ymin - margin, (xmax + margin) - (xmin - margin), likewise h.  joint_mask is not read.
+ * status[pose] = 1 and a zero box where there is no x or no y to take a minimum over (the reference raises), else 0. */
+int buctd_pose_boxes(const double* poses, int n, int K, int form, const int* joint_mask, double margin, double* boxes,
+                     int* status, void* stream);
+/* For every annotation the prediction of the same image with the largest _get_iou (match_coco_cond.py:33-50, on
+ * x1 y1 x2 y2 boxes; ties go to the lowest row, and if every IoU is 0 that is the image's first prediction, as
+ * np.argmax has it).  matched int32 [gt total]: the row of the prediction in pred_boxes, or -1 for an image without
+ * predictions or an annotation with gt_status != 0 (gt_status may be NULL); best_iou [gt total]: its IoU, 0 with -1. */
+int buctd_match_boxes(const int* gt_offsets, const int* pred_offsets, int images, const double* gt_boxes,
+                      const int* gt_status, const double* pred_boxes, int* matched, double* best_iou, void* stream);
+#define BUCTD_GROUP_IOU_TEST 0
+#define BUCTD_GROUP_IOU_TRAIN 1
+/* Per member of a group, over the x y w h boxes of the group:
+ * BUCTD_GROUP_IOU_TEST (dataloader.py:368-372): max_iou = the largest JointsDataset.compute_iou with another member
+ *   (0 where its denominator is 0), 0 for a single member; status 0; near_count is not written.
+ * BUCTD_GROUP_IOU_TRAIN (dataloader.py:234-241): calc_bbox_overlap with every member, itself included; max_iou = the
+ *   largest overlap that is != 1 in a group of more than one member (0 if none is left, where the reference raises),
+ *   else 0; near_count[member] (may be NULL) = the number of overlaps > 0; a zero union (the reference divides by it)
+ *   counts as overlap 0 and sets status[member] = 2. */
+int buctd_group_max_iou(const int* offsets, int images, const double* boxes, int form, double* max_iou, int* status,
+                        int* near_count, void* stream);
+/* The near lists of the train form: near_offsets int64 [members + 1] is the prefix sum of near_count; member i's rows
+ * (positions in `boxes`) of the members it overlaps by > 0 go to near_index[near_offsets[i] ...] in ascending order. */
+int buctd_group_near_list(const int* offsets, int images, const double* boxes, const long* near_offsets,
+                          int* near_index, void* stream);
+
 /* ------------------------------------------------------------- bf16 inference --- */
 /* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).
  * bf16 tensors are passed as raw bit patterns (uint16_t).  Activations bf16 NHWC [N][H][W][C]; a conv layer is a

@@ -281,6 +281,10 @@ SIGNATURES = {
     "buctd_match_boxes": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "buctd_group_max_iou": (_I, [_P, _I, _P, _I, _P, _P, _P, _P]),
     "buctd_group_near_list": (_I, [_P, _I, _P, _P, _P, _P]),
+    # debug pictures (csrc/vis.hip)
+    "buctd_vis_minmax": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
+    "buctd_vis_heatmap_grid": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "buctd_vis_joint_grid": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..utils.transforms import flip_hm, flip_merge_device
+from ..utils.vis import save_debug_images
 from .evaluate import pck_from_coords
 from .inference import DeferredFinalPreds, get_final_preds
 
@@ -200,9 +201,9 @@ def train(config, train_loader, model, criterion, optimizer, epoch, output_dir, 
 
 
 def _save_debug_images(config, input, meta, target, pred, output, prefix, output_dir=None):
-    """Debug JPEG grids (reference utils/vis.py:416-472) need cv2 / torchvision, which the target image lacks;
-    they are outside the hot path - the hook stays so that callers do not break."""
-    logger.debug('debug image dump skipped (%s)', prefix)
+    """Debug picture grids (reference utils/vis.py:416-472), rendered on the device by utils/vis.py and written as PNG;
+    returns at once unless DEBUG.DEBUG."""
+    save_debug_images(config, input, meta, target, pred, output, prefix, output_dir=output_dir or '')
 
 
 # ------------------------------------------------------------------------------------------ validate ----

@@ -994,6 +994,49 @@ int buctd_group_max_iou(const int* offsets, int images, const double* boxes, int
 int buctd_group_near_list(const int* offsets, int images, const double* boxes, const long* near_offsets,
                           int* near_index, void* stream);
 
+/* ------------------------------------------------------------ debug pictures --- */
+/* The pictures of utils/vis.py (csrc/vis.hip), rendered on the device into uint8 RGB; what the reference does with
+ * cv2 / torchvision on fp32 host copies (utils/vis.py:75-141, 269-332).  The batch image is fp32 [B][3][H][W] given by
+ * its four element strides sb, sc, sh, sw, so NCHW and channels-last tensors and views both work.  Every value is an
+ * integer expression of bytes or the fp32 expression written here, one operation after the other (the library is built
+ * without contraction).  No function allocates or synchronises; a null pointer (where none is allowed), an extent < 1
+ * or an `out` that is not 4-byte aligned returns BUCTD_EINVAL before any launch.
+ *
+ * image byte of a value v: u = (v - lo) / ((hi - lo) + 1e-5f), then u * 255.0f clamped to [0, 255] and truncated; lo
+ * and hi are read from lohi[0], lohi[1] in device memory.  lohi NULL: u = v (normalize=False).
+ * bgr != 0: the image's channels are B, G, R (DATASET.COLOR_RGB false) and are swapped, so `out` is RGB either way. */
+/* lohi[0] = the smallest, lohi[1] = the largest value of the image (finite values).  Two launches. */
+int buctd_vis_minmax(const float* img, int B, int H, int W, long sb, long sc, long sh, long sw, float* lohi,
+                     void* stream);
+/* save_batch_heatmaps: out uint8 [B*Hh][(K+1)*Wh][3].  Row block i is image i; column block 0 is the image shrunk to
+ * Hh x Wh, column block j+1 is joint j.  heatmaps fp32 [B][K][Hh][Wh]; peaks fp32 [B][K][2] = (x, y) in heat-map
+ * pixels, as the argmax decode writes them.
+ *   shrunken image: bilinear, half-pixel centres, fixed-point weights, on the image bytes.  Per axis
+ *     fx = (x + 0.5f) * ((float)W / (float)Wh) - 0.5f, x0 = floorf(fx), a = fx - x0; x0 < 0: x0 = 0, a = 0;
+ *     x0 >= W - 1: x0 = W - 1, a = 0, the right tap is x0 itself; wa = (int)rintf(a * 2048.0f), likewise wb in y;
+ *     byte = ((p00*(2048-wa) + p01*wa)*(2048-wb) + (p10*(2048-wa) + p11*wa)*wb + (1 << 21)) >> 22.
+ *   heat byte: h * 255.0f clamped to [0, 255], truncated.  colour of a heat byte, on t = byte / 255.0f:
+ *     r, g, b = clamp(1.5f - fabsf(4t - 3 | 2 | 1), 0, 1), each stored as (int)floorf(c * 255.0f + 0.5f).
+ *   tile j+1 = (7 * colour + 3 * background) / 10 per channel in integers.
+ *   marker of joint j: the four pixels at Manhattan distance 1 from ((int)px, (int)py), clipped to the tile, pure red.
+ *     The markers are drawn onto the shrunken image joint after joint: the background of tile j+1 carries the markers
+ *     of the joints 0..j (blended), joint j's own marker lies on top unblended, column block 0 carries all K. */
+int buctd_vis_heatmap_grid(const float* img, int B, int H, int W, long sb, long sc, long sh, long sw, const float* lohi,
+                           const float* heatmaps, int K, int Hh, int Wh, const float* peaks, int bgr, uint8_t* out,
+                           void* stream);
+/* save_batch_image_with_joints: the make_grid picture of the batch, xmaps = min(nrow, B) cells per row, ymaps =
+ * ceil(B / xmaps) rows, out uint8 [ymaps*(H+padding)+padding][xmaps*(W+padding)+padding][3]; image k sits at row
+ * (k / xmaps)*(H+padding)+padding, column (k % xmaps)*(W+padding)+padding; padding and unused cells are 0, the rest
+ * image bytes.  Marks per joint, in joint order, later ones painting over earlier ones, clipped to the cell's H x W:
+ *   pred [B][K][2] where pred_vis [B][K] != 0: the disc dx*dx + dy*dy <= 8, red;
+ *   gt where gt_vis != 0: a + with arms of 2 pixels, blue;
+ *   cond where cond_vis > 0 and both coordinates > 0: an x with arms of 2 pixels, green (cond and cond_vis may both
+ *   be NULL).  Positions are fp32 input pixels, truncated toward zero. */
+int buctd_vis_joint_grid(const float* img, int B, int H, int W, long sb, long sc, long sh, long sw, const float* lohi,
+                         int K, const float* pred, const float* pred_vis, const float* gt, const float* gt_vis,
+                         const float* cond, const float* cond_vis, int nrow, int padding, int bgr, uint8_t* out,
+                         void* stream);
+
 /* ------------------------------------------------------------- bf16 inference --- */
 /* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).
  * bf16 tensors are passed as raw bit patterns (uint16_t).  Activations bf16 NHWC [N][H][W][C]; a conv layer is a

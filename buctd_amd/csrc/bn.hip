@@ -200,60 +200,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 // block = 256 threads laid out as (rows 256/CT) x (CT column threads), CT = min(C,64) rounded;
 // simple layout: thread handles channel c = t % CW, row lane = t / CW.
 #define BWD_ROWS 64
-// Vector path (C % 4 == 0, C/4 <= 256): thread = (row lane, 4-channel group); 16-byte loads of dy, y, z.
-__global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* __restrict__ dy,
-                                                                const float* __restrict__ y,
-                                                                const float* __restrict__ z,
-                                                                const float* __restrict__ mean,
-                                                                const float* __restrict__ invstd,
-                                                                const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, int relu, long rows,
-                                                                int C, float* __restrict__ part) {
-  __shared__ f32x4 sm[2][256];
-  const int c4n = C >> 2;
-  const int rl = 256 / c4n;
-  const int tc = threadIdx.x % c4n, tr = threadIdx.x / c4n;
-  const long r0 = (long)blockIdx.x * BWD_ROWS;
-  long r1 = r0 + BWD_ROWS;
-  if (r1 > rows) r1 = rows;
-  f32x4 s1 = (f32x4){0.f, 0.f, 0.f, 0.f}, s2 = s1;
-  if (tr < rl) {
-    const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[tc];
-    const f32x4 is = reinterpret_cast<const f32x4*>(invstd)[tc];
-    f32x4 sc = is, be = is;
-    if (relu && !y) {   // mask recomputed exactly as bn_apply formed its output (no residual in the forward)
-      sc = is * reinterpret_cast<const f32x4*>(gamma)[tc];
-      be = reinterpret_cast<const f32x4*>(beta)[tc];
-    }
-    for (long r = r0 + tr; r < r1; r += rl) {
-      const long o = r * c4n + tc;
-      f32x4 g = reinterpret_cast<const f32x4*>(dy)[o];
-      const f32x4 zz = reinterpret_cast<const f32x4*>(z)[o];
-      if (relu) {
-        f32x4 yy;
-        if (y) yy = reinterpret_cast<const f32x4*>(y)[o];
-        else yy = (zz - mu) * sc + be;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (!(yy[j] > 0.f)) g[j] = 0.f;
-      }
-      s1 += g;
-      s2 += g * (zz - mu) * is;
-    }
-  }
-  sm[0][threadIdx.x] = s1;
-  sm[1][threadIdx.x] = s2;
-  __syncthreads();
-  if (tr == 0) {
-    for (int k = 1; k < rl; ++k) {
-      s1 += sm[0][k * c4n + tc];
-      s2 += sm[1][k * c4n + tc];
-    }
-    reinterpret_cast<f32x4*>(part + ((long)blockIdx.x * 2 + 0) * C)[tc] = s1;
-    reinterpret_cast<f32x4*>(part + ((long)blockIdx.x * 2 + 1) * C)[tc] = s2;
-  }
-}
-
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             const float* __restrict__ z,
                                                             const float* __restrict__ mean,

@@ -39,6 +39,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.helpers import c3_cases as T
+from tests.helpers.guard_bands import SENTINEL, banded, untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -496,23 +497,6 @@ def test_weight_gradient_against_fp64(x6, dev, case):
 
 
 # ---- guard bands -----------------------------------------------------------------------------------------------------------
-SENTINEL = -12345.678
-
-
-def banded(t, dev, shape, fill=float("nan")):
-    """a copy of t (device) in the middle of a larger allocation filled with `fill`: >= 2 * SW + 3 rows of it on either side"""
-    W, Cn = shape[2], t.shape[-1]
-    pad = (2 * (W + 1) + 3 + 5) * Cn
-    big = torch.full((2 * pad + t.numel(),), fill, dtype=torch.float32, device=dev)
-    view = big[pad:pad + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view, big, pad
-
-
-def untouched(big, pad, n):
-    return bool((big[:pad] == SENTINEL).all()) and bool((big[pad + n:] == SENTINEL).all())
-
-
 @pytest.mark.parametrize("opt", [o for o in T.OPTION_SETS if o != "general"])
 @pytest.mark.parametrize("shape", T.GUARD_CASES, ids=T.case_id)
 def test_inputs_between_nan_bands(x6, dev, shape, opt):

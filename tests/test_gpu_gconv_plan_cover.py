@@ -48,7 +48,8 @@ import torch.nn.functional as F
 
 from tests.helpers import gconv_cases as T
 # the operand generator, the BatchNorm stand-in and the guard-band mechanics of the 3x3 module (shared, not copied)
-from tests.test_gpu_conv3x3_plan_cover import SENTINEL, _Bn, banded, hard_operands, in_fp32, untouched, x6  # noqa: F401
+from tests.helpers.guard_bands import SENTINEL, banded, untouched
+from tests.test_gpu_conv3x3_plan_cover import _Bn, hard_operands, in_fp32, x6  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

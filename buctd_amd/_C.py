@@ -84,6 +84,12 @@ class MhaArgs(C.Structure):            # mirrors buctd_mha_args
                 [(n, C.c_void_p) for n in ("dq", "dk", "dv")] + [(n, C.c_int) for n in ("lddq", "lddk", "lddv")])
 
 
+class AttnRowsArgs(C.Structure):       # mirrors buctd_attn_rows_args
+    _fields_ = ([(n, C.c_int) for n in ("B", "T", "h", "dh", "R")] + [("q", C.c_void_p), ("k", C.c_void_p)] +
+                [("ldq", C.c_int), ("ldk", C.c_int), ("rows", C.c_void_p), ("scale", C.c_float), ("out", C.c_void_p),
+                 ("out_heads", C.c_void_p)])
+
+
 class RefineArgs(C.Structure):          # mirrors buctd_refine_args
     _fields_ = ([(n, C.c_void_p) for n in ("coords", "maxvals", "offset", "center", "scale", "box_score", "items",
                                            "cond_trunc", "cond_joints", "status", "hist_preds", "hist_score",
@@ -267,6 +273,8 @@ SIGNATURES = {
     "buctd_mha_heads_bwd": (_I, [C.POINTER(MhaArgs), _U64, _P, _SZ, _P]),
     "buctd_mha_heads_fwd_train_dseed": (_I, [C.POINTER(MhaArgs), _P, _P]),
     "buctd_mha_heads_bwd_dseed": (_I, [C.POINTER(MhaArgs), _P, _P, _SZ, _P]),
+    "buctd_attn_rows_supported": (_I, [_I, _I, _I]),
+    "buctd_attn_rows": (_I, [C.POINTER(AttnRowsArgs), _P]),
     "buctd_nms_workspace": (_SZ, [_I]),
     "buctd_nms": (_I, [_P, _P, _P, _I, _I, _F, _P, _SZ, _P]),
     "buctd_cpu_nms": (_I, [_P, _I, _P, _F, _P, _P]),

@@ -3,6 +3,8 @@
 -> (+16 condition channels) -> post-norm Transformer encoder with a sine position embedding -> 1x1 head.
 Same constructor, state_dict keys (incl. self_attn.in_proj_weight / out_proj) and init; tokens are kept
 batch-major [B, T, d] (the flattened NHWC tensor) instead of the reference's [T, B, d] - same math, no transposes.
+Attention maps (return_atten_map, and TransPoseH.attention_maps for the dependency areas of chosen tokens) come from
+ops.attention_rows: rows of the soft-max matrix computed from the projected q | k, beside the unchanged attention output.
 """
 import copy
 import math
@@ -28,9 +30,24 @@ class MultiheadAttention(nn.Module):
         torch.nn.init.constant_(self.in_proj_bias, 0.0)
         torch.nn.init.constant_(self.out_proj.bias, 0.0)
 
-    def forward(self, qin, src):
-        """q = k = qin (src + pos), v = src; returns the attention output [B, T, d]."""
+    # a list while TransPoseH.attention_maps runs: every forward leaves its projected q | k [B, T, 2d] there
+    qk_sink = None
+
+    def check_map_mode(self):
+        if self.training and float(self.dropout) > 0.0:
+            raise NotImplementedError("attention maps are the eval-mode soft-max weights: a training-mode layer with "
+                                      f"attention dropout p = {self.dropout} would return dropped-out weights; call "
+                                      ".eval() or build the layer with dropout 0")
+
+    def forward(self, qin, src, rows=None, need_map=False):
+        """q = k = qin (src + pos), v = src; returns the attention output [B, T, d].  need_map: also the head-averaged
+        soft-max weights of the query tokens `rows` (int32 [B, R] on the device; None: all, [B, T, T]), from the same
+        projected q | k - the output itself takes the route it takes without the map."""
+        if need_map:
+            self.check_map_mode()
         qk, v = ops_seq.InProjection.apply(qin, src, self.in_proj_weight, self.in_proj_bias)
+        if self.qk_sink is not None:
+            self.qk_sink.append(qk.detach())
         p_eff = float(self.dropout) if self.training else 0.0
         needs_grad = torch.is_grad_enabled() and (qk.requires_grad or v.requires_grad)
         if p_eff == 0.0 and not needs_grad and ops.mha_fused_ok(qk.shape[1], self.embed_dim, self.num_heads):
@@ -43,6 +60,8 @@ class MultiheadAttention(nn.Module):
             # shapes the fused kernels do not take (T not a multiple of 64, head width not a multiple of 16):
             # materialised soft-max with the same counter-hash dropout
             out = ops.PositionAttention.apply(qk, None, v, self.num_heads, float(self.dropout), self.training)
+        if need_map:
+            return self.out_proj(out), ops.attention_rows(qk.detach(), rows, self.num_heads)
         return self.out_proj(out)
 
 
@@ -50,8 +69,9 @@ class TransformerEncoderLayer(nn.Module):
     def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu", normalize_before=False,
                  return_atten_map=False):
         super().__init__()
-        if activation != "relu" or normalize_before or return_atten_map:
-            raise NotImplementedError("TransPoseH builds post-norm ReLU layers without attention-map output")
+        if activation != "relu" or normalize_before:
+            raise NotImplementedError("TransPoseH builds post-norm ReLU layers")
+        self.return_atten_map = return_atten_map
         self.self_attn = MultiheadAttention(d_model, nhead, dropout=dropout)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.dropout = torch.nn.Dropout(dropout)
@@ -61,16 +81,22 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout1 = torch.nn.Dropout(dropout)
         self.dropout2 = torch.nn.Dropout(dropout)
 
-    def forward(self, src, pos=None):
+    def forward(self, src, pos=None, rows=None):
+        """return_atten_map: -> (src, att_map [B, R, T]) with the rows of the query tokens `rows` (None: [B, T, T])"""
         qin = src if pos is None else ops_seq.AddPos.apply(src, pos)
-        src2 = self.self_attn(qin, src)
+        att_map = None
+        if self.return_atten_map:
+            src2, att_map = self.self_attn(qin, src, rows=rows, need_map=True)
+        else:
+            src2 = self.self_attn(qin, src)
         src2 = ops_seq.Dropout.apply(src2, float(self.dropout1.p), self.training)
         src = ops_seq.AddLayerNorm.apply(src, src2, self.norm1)
         ff = self.linear1(src, relu=True)
         ff = ops_seq.Dropout.apply(ff, float(self.dropout.p), self.training)
         ff = self.linear2(ff)
         ff = ops_seq.Dropout.apply(ff, float(self.dropout2.p), self.training)
-        return ops_seq.AddLayerNorm.apply(src, ff, self.norm2)
+        src = ops_seq.AddLayerNorm.apply(src, ff, self.norm2)
+        return (src, att_map) if self.return_atten_map else src
 
 
 class TransformerEncoder(nn.Module):
@@ -85,13 +111,40 @@ class TransformerEncoder(nn.Module):
             if p.dim() > 1:
                 torch.nn.init.xavier_uniform_(p)
 
-    def forward(self, src, pos=None):
+    def forward(self, src, pos=None, rows=None):
+        """return_atten_map: -> (out, maps [layers, B, R, T]); rows=None is the reference's [layers, B, T, T]"""
+        maps = []
         for layer in self.layers:
-            src = layer(src, pos=pos)
+            if self.return_atten_map:
+                # as in the reference, the layers are built with the flag too and return (src, att_map)
+                src, att_map = layer(src, pos=pos, rows=rows)
+                maps.append(att_map)
+            else:
+                src = layer(src, pos=pos)
             pos = None if self.pe_only_at_begin else pos
         if self.norm is not None:
             raise NotImplementedError("TransPoseH never sets a final encoder norm")
-        return src
+        return (src, torch.stack(maps)) if self.return_atten_map else src
+
+
+def query_rows(query, batch, h_tok, w_tok, device):
+    """(x, y) points in heat-map pixels [B, Q, 2], host or device -> int32 [B, Q] token indices y * w_tok + x on `device`;
+    coordinates are truncated towards zero (the reference's .astype(int)), a point outside the grid becomes -1."""
+    pts = torch.as_tensor(query)
+    if pts.dim() != 3 or pts.shape[0] != batch or pts.shape[2] != 2 or pts.shape[1] < 1:
+        raise ValueError(f"attention_maps: query points must be [B = {batch}, Q >= 1, 2] (x, y), got {tuple(pts.shape)}")
+    if pts.dtype == torch.bool or pts.is_complex():
+        raise ValueError(f"attention_maps: query points must be numbers, got {pts.dtype}")
+    pts = pts.detach().to(device)
+    if pts.is_floating_point():
+        # NaN compares false everywhere below; the clamp keeps huge values inside int64 (and outside every grid)
+        xy = pts.double().clamp(-2.0 ** 40, 2.0 ** 40).trunc()
+        x, y = xy[..., 0], xy[..., 1]
+    else:
+        x, y = pts[..., 0].to(torch.int64), pts[..., 1].to(torch.int64)
+    inside = (x >= 0) & (x < w_tok) & (y >= 0) & (y < h_tok)
+    x, y = (torch.where(inside, v, torch.zeros_like(v)).to(torch.int64) for v in (x, y))
+    return torch.where(inside, y * w_tok + x, torch.full_like(x, -1)).to(torch.int32).contiguous()
 
 
 class TransPoseH(HRNetTrunk):
@@ -165,6 +218,48 @@ class TransPoseH(HRNetTrunk):
         pos = None if self.pos_embedding is None else self.pos_embedding.view(h * w, c)
         tokens = self.global_encoder(tokens, pos=pos)
         return ops.ToNCHW.apply(self.final_layer(tokens.view(b, h, w, c)))
+
+    def attention_maps(self, x, query="pred"):
+        """Dependency areas: which tokens the query tokens attend to, per encoder layer -> (heatmaps, maps, rows).
+        query  "pred": one row per joint, at the arg-max of that joint's output heat-map (a joint whose maximum is <= 0
+                       gets index -1 and an all-zero map);
+               [B, Q, 2] (x, y) in heat-map pixels, host or device, truncated like the reference's .astype(int) (a point
+                       outside the grid: -1);
+               None:   every token - the full map.
+        heatmaps is forward(x) in eval mode; maps is [layers, B, Q, h_tok, w_tok] (the token grid is the heat-map grid), or
+        [layers, B, T, T] for the full map; rows the int32 [B, Q] token indices y * w_tok + x used (None for the full map).
+        Runs in eval mode under no_grad: the forward keeps each layer's projected q | k ([B, T, 2d]) and the rows kernel
+        runs per layer afterwards, since "pred" knows its rows only once the heat-maps exist."""
+        attns = [layer.self_attn for layer in self.global_encoder.layers]
+        modes = [(m, m.training) for m in self.modules()]
+        sink = []
+        self.eval()
+        try:
+            for a in attns:
+                a.qk_sink = sink
+            with torch.no_grad():
+                heatmaps = self.forward(x)
+                b, _, h, w = heatmaps.shape
+                if len(sink) != len(attns) or any(qk.shape[1] != h * w for qk in sink):
+                    raise RuntimeError("attention_maps: the encoder's token grid is not the heat-map grid")
+                if query is None:
+                    rows = None
+                elif isinstance(query, str):
+                    if query != "pred":
+                        raise ValueError(f"attention_maps: query is 'pred', a [B, Q, 2] array or None, not {query!r}")
+                    _, maxvals, idx = ops.argmax_decode(heatmaps.contiguous())
+                    rows = torch.where(maxvals.view(idx.shape) > 0, idx, torch.full_like(idx, -1))
+                else:
+                    rows = query_rows(query, b, h, w, heatmaps.device)
+                maps = torch.stack([ops.attention_rows(qk, rows, a.num_heads) for qk, a in zip(sink, attns)])
+                if rows is not None:
+                    maps = maps.view(len(attns), b, rows.shape[1], h, w)
+        finally:
+            for a in attns:
+                a.qk_sink = None
+            for m, was in modes:
+                m.training = was
+        return heatmaps, maps, rows
 
     def init_weights(self, pretrained="", print_load_info=False):
         init_weights_hrnet(self, pretrained)

@@ -2426,6 +2426,47 @@ def mha_fwd(qk, v, scale=None, h=1, k=None):
     return out
 
 
+def attention_rows(qk, rows=None, h=1, k=None, scale=None, per_head=False):
+    """Chosen rows of the attention matrix (attn_rows.hip): mean over the h heads of softmax_j(scale * q_r . k_j), eval mode.
+    Operands as mha_fwd: packed qk [B, T, 2d] = q | k (k=None), or q and k [B, T, d] as contiguous tensors or channel slices.
+    rows: int32 device tensor [B, R] of token indices (an index outside [0, T) gives a row of exact zeros), or None for
+    every row (the full T x T map).  -> [B, R, T], and with per_head also the heads' own rows [B, h, R, T].  No autograd."""
+    if torch.is_grad_enabled() and (qk.requires_grad or (k is not None and k.requires_grad)):
+        raise _C.BuctdHipError("attention_rows has no backward: call it under torch.no_grad() or on detached tensors")
+    if qk.dim() != 3 or (k is not None and k.dim() != 3):
+        raise _C.BuctdHipError("attention_rows: q | k (or q and k) must be [B, T, channels]")
+    h = int(h)
+    hd = qk.shape[2] // 2 if k is None else qk.shape[2]
+    if h < 1 or (k is None and qk.shape[2] % 2) or hd % h:
+        raise _C.BuctdHipError("attention_rows: h >= 1 divides the width, and the packed form holds q | k of equal widths")
+    B, T = qk.shape[0], qk.shape[1]
+    # operand placement as mha_fwd's (_mha_rows: row strides, one copy where the layout asks for it)
+    q, ldq = _mha_rows(qk, T, "attention_rows q")
+    if k is None:
+        k, ldk, kp = q, ldq, q.data_ptr() + 4 * hd
+    else:
+        if tuple(k.shape) != (B, T, hd):
+            raise _C.BuctdHipError("attention_rows: q and k must have the same token count and width")
+        k, ldk = _mha_rows(k, T, "attention_rows k")
+        kp = k.data_ptr()
+    if rows is None:
+        R = T
+    else:
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[0] != B or rows.device != qk.device:
+            raise _C.BuctdHipError("attention_rows: rows must be an int32 [B, R] tensor on the operands' device")
+        rows = _contig(rows)
+        R = rows.shape[1]
+    a = _C.AttnRowsArgs()
+    a.B, a.T, a.h, a.dh, a.R = B, T, h, hd // h, R
+    a.q, a.k, a.ldq, a.ldk = ptr(q), kp, ldq, ldk
+    a.rows, a.scale = ptr(rows), (1.0 / math.sqrt(hd // h)) if scale is None else float(scale)
+    out = torch.empty((B, R, T), dtype=torch.float32, device=qk.device)
+    heads = torch.empty((B, h, R, T), dtype=torch.float32, device=qk.device) if per_head else None
+    a.out, a.out_heads = ptr(out), ptr(heads)
+    check(lib().buctd_attn_rows(C.byref(a), stream_ptr()), "attention_rows")
+    return (out, heads) if per_head else out
+
+
 def mha_train_ok(T, d, h=1):
     """True when the fused training attention (attn_mha_train.hip: forward with dropout + lse, flash-style backward) covers
     T tokens of total width d in h heads."""

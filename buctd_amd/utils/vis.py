@@ -130,6 +130,26 @@ def save_batch_heatmaps(batch_image, batch_heatmaps, file_name, normalize=True, 
     write_png(file_name, render_batch_heatmaps(batch_image, batch_heatmaps, normalize, bgr).cpu().numpy())
 
 
+def render_batch_attention_maps(batch_image, maps_of_one_layer, bgr=True):
+    """Dependency areas of one encoder layer (TransPoseH.attention_maps(...)[1][layer], [B, K, h_tok, w_tok]) as the
+    heat-map grid of render_batch_heatmaps: every row of the attention matrix is divided by its own maximum on the device
+    (an all-zero row - an undetected joint - stays zero), so each tile uses the whole colour range."""
+    img = _image(batch_image)
+    m = maps_of_one_layer
+    if not (torch.is_tensor(m) and m.dim() == 4 and m.dtype == torch.float32 and m.size(0) == img.size(0)):
+        raise _C.BuctdHipError("vis: the attention maps of a layer must be a fp32 [B, K, h_tok, w_tok] tensor with the "
+                               "image's batch size")
+    ptr(m)              # refuses host tensors
+    m = m.detach()
+    top = m.amax(dim=(2, 3), keepdim=True)
+    m = m / torch.where(top > 0, top, torch.ones_like(top))
+    return render_batch_heatmaps(img, m, True, bgr)
+
+
+def save_batch_attention_maps(batch_image, maps_of_one_layer, file_name, bgr=True):
+    write_png(file_name, render_batch_attention_maps(batch_image, maps_of_one_layer, bgr).cpu().numpy())
+
+
 def save_batch_image_with_joints(batch_image, batch_joints, batch_joints_vis, meta, file_name, nrow=8, padding=2,
                                  bgr=True):
     """reference utils/vis.py:75-141."""

@@ -681,6 +681,26 @@ int buctd_mha_heads_fwd_train_dseed(const buctd_mha_args* a, const uint64_t* see
 int buctd_mha_heads_bwd_dseed(const buctd_mha_args* a, const uint64_t* seed, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* Chosen rows of the attention matrix (the encoder's return_atten_map, transpose_h.py:110-150, 168-243), eval mode:
+ *     out[b][r][j] = 1/h sum_head softmax_j(scale * q[rows[b][r]] . k[j])
+ * straight from the projected q | k, nothing T x T unless every row is asked for.  Max-subtracted soft-max, products on
+ * the exact fp32 MFMA in the contraction order of buctd_mha_heads_fwd, the head mean formed in head order by one lane per
+ * element: two runs, duplicate rows, and a row query against the full map are bit-identical.
+ * Any T >= 1, h >= 1, dh % 4 == 0, dh <= 128; q, k, out, out_heads 16-byte aligned, ldq / ldk multiples of 4 and >= h dh.
+ * A row index outside [0, T) is no error: that row is written as exact zeros (an undetected joint). */
+typedef struct buctd_attn_rows_args {
+  int B, T, h, dh, R;               /* R query rows per image */
+  const float* q; const float* k;   /* as buctd_mha_args: head i = columns [i dh, (i+1) dh) */
+  int ldq, ldk;                     /* row strides in floats; images T*ld apart */
+  const int* rows;                  /* device, [B][R] token index of each query row;
+                                       NULL: R == T and row r is token r (the full map) */
+  float scale;
+  float* out;                       /* [B][R][T]  mean over heads of softmax_j(scale q_r . k_j) */
+  float* out_heads;                 /* optional [B][h][R][T], NULL ok */
+} buctd_attn_rows_args;
+int buctd_attn_rows_supported(int T, int h, int dh);
+int buctd_attn_rows(const buctd_attn_rows_args* a, void* stream);
+
 /* ------------------------------------------------------- sample pipeline --- */
 /* Person crop of the per-sample pipeline (dataset/JointsDataset.py:287-294): cv2.warpAffine(img_u8, M, (w, h),
  * flags=INTER_LINEAR) restated bit for bit (OpenCV's fixed-point bilinear, BORDER_CONSTANT 0), fused with

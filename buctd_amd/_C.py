@@ -232,6 +232,7 @@ SIGNATURES = {
     "buctd_dropout_dseed": (_I, [_P, _P, _L, _F, _P, _P]),
     "buctd_dropout_seed_fill": (_I, [_P, _I, _U64, _U64, _P]),
     "buctd_attn_smallqk_supported": (_I, [_I, _I, _I]),
+    "buctd_attn_smallqk_plan": (_I, [_I, _I, _I, _I, _F, _I, _PI]),
     "buctd_attn_smallqk_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _F, _F, _U64, _I, _P, _P, _P, _P]),
     "buctd_attn_smallqk_bwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _U64, _I, _P, _P, _P, _P, _P]),
     "buctd_attn_smallqk_fwd_dseed": (_I, [_I, _I, _I, _I, _P, _P, _P, _F, _F, _P, _I, _P, _P, _P, _P]),

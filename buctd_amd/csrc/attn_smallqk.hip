@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(SeededArgs<AttnArgs,
   }
   dpart += __shfl_xor(dpart, 16, 64);
   dpart += __shfl_xor(dpart, 32, 64);
-  if (kq == 0) p.dvec[rowbase + r0 + i16] = dpart;
+  if (NP != 2 && kq == 0) p.dvec[rowbase + r0 + i16] = dpart;
   // A operand: dO[row r0 + i16][32 kk + 8 kq .. +7]
   bf16x8 aa[NK][NP];
 #pragma unroll
@@ -358,6 +358,17 @@ __global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(SeededArgs<AttnArgs,
   for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
     for (int r = 0; r < R4; ++r) dq[rg][r] = 0.f;
+  // two pieces: D is formed from the SAME dP the kernel multiplies with, D = sum_j Pd_ij dP_ij (in exact arithmetic equal to
+  // dO . O), and dq' = sum_j P g k' - D sum_j P k'.  The product error of dP (2^-16) is then common to both terms of dS =
+  // P (g - D); against the exact dO . O it survives the cancellation of a peaked row 1 / (1 - p) times enlarged.
+  constexpr int RB = NP == 2 ? R4 : 1;
+  float pk[4][RB], dsum[4];
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) {
+    dsum[rg] = 0.f;
+#pragma unroll
+    for (int r = 0; r < RB; ++r) pk[rg][r] = 0.f;
+  }
   // byte offset of this lane's 8 channels inside a tile row (clamped for the zero-padded tail of the last step)
   int boff[NK];
 #pragma unroll
@@ -409,20 +420,38 @@ __global__ __launch_bounds__(256) void attn_bwd_q_b3_kernel(SeededArgs<AttnArgs,
         const float pv = __builtin_amdgcn_exp2f(dotr<R4>(qrow[rg], kv) - mrow[rg]) * lrow[rg];
         float gg = dp4[rg];
         if (DROP) gg *= keepf(rkrow[rg], cks[j], p.thr, p.inv_keep);
-        const float ds = pv * (gg - drow[rg]);
+        if (NP == 2) {
+          const float pg = pv * gg;
+          dsum[rg] += pg;
 #pragma unroll
-        for (int r = 0; r < R4; ++r) dq[rg][r] += ds * kv[r];
+          for (int r = 0; r < R4; ++r) {
+            dq[rg][r] += pg * kv[r];
+            pk[rg][r < RB ? r : 0] += pv * kv[r];
+          }
+        } else {
+          const float ds = pv * (gg - drow[rg]);
+#pragma unroll
+          for (int r = 0; r < R4; ++r) dq[rg][r] += ds * kv[r];
+        }
       }
     }
   }
 #pragma unroll
-  for (int rg = 0; rg < 4; ++rg)
+  for (int rg = 0; rg < 4; ++rg) {
+    if (NP == 2) {
+      float d = dsum[rg];
+      d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64); d += __shfl_xor(d, 8, 64);
+      if (i16 == 0) p.dvec[rowbase + r0 + kq * 4 + rg] = d;
+#pragma unroll
+      for (int r = 0; r < R4; ++r) dq[rg][r] -= d * pk[rg][r < RB ? r : 0];     // linear: each lane subtracts its share
+    }
 #pragma unroll
     for (int r = 0; r < R4; ++r) {
       float v = dq[rg][r];
       v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
       if (i16 == 0) p.out[(rowbase + r0 + kq * 4 + rg) * R4 + r] = v * p.scale;
     }
+  }
 }
 
 // dk' / dV pass.  dP (queries as rows) per 16 x 16 block as in attn_bwd_kv_kernel; two such blocks give, per lane,
@@ -756,14 +785,53 @@ static bool attn_shape_ok(int T, int R4, int C) {
 
 extern "C" int buctd_attn_smallqk_supported(int T, int R4, int C) { return attn_shape_ok(T, R4, C) ? 1 : 0; }
 
+// flag of the C ABI -> pieces per operand: 0 fp32 MFMA kernels, 1 -> two bf16 pieces, 2 -> three (bf16x6; its 192-channel
+// tile rows would need 77 KB of static LDS, so that width stays on the fp32 kernels)
+static int attn_split_mode(int flag, int C) { return flag == 2 ? (C <= 128 ? 3 : 0) : (flag ? 2 : 0); }
+
+// The routing, stated once: what a call launches.  attn_smallqk_fwd / _bwd, attn_dispatch and attn_launch read it and
+// buctd_attn_smallqk_plan reports it, so the query cannot drift from the launch.
+struct AttnRoute {
+  int split;    // kernel family: 0 = attn_{fwd,bwd_q,bwd_kv}_kernel (fp32 MFMA), 1 = the _b3 kernels (split-bf16 operands)
+  int R4, CF;   // template arguments of the family's kernels (CF = C / 16)
+  int pieces;   // bf16 pieces per operand: 0 (fp32 family), 2 or 3
+  int stats;    // the forward runs attn_stats_kernel<R4> first (the split forward keeps the statistics itself)
+  int drop;     // DROP
+  int dseed;    // DSEED: the kernels read the seed from device memory (without dropout the seed is not read: value kernels)
+};
+// B: images of the launch (1 for the query: the size limit is the only thing B decides)
+static int attn_route(const char* who, long B, int T, int R4, int C, int flag, float p_drop, bool dseed, AttnRoute* r) {
+  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "%s: unsupported T=%d R4=%d C=%d", who, T, R4, C);
+  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f && B * T < 2147483647L, "%s: bad p_drop / size", who);
+  const int pieces = attn_split_mode(flag, C);
+  r->split = pieces && R4 <= 8;        // wider contractions take the fp32 kernels in every math mode
+  r->R4 = R4;
+  r->CF = C / 16;
+  r->pieces = r->split ? pieces : 0;
+  r->stats = !r->split;
+  r->drop = p_drop > 0.f;
+  r->dseed = r->drop && dseed;
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_attn_smallqk_plan(int T, int R4, int C, int flag, float p_drop, int dseed, int* out) {
+  BUCTD_CHECK_ARG(out, "buctd_attn_smallqk_plan: null argument");
+  memset(out, 0, BUCTD_ATTN_SMALLQK_PLAN_INTS * sizeof(int));
+  AttnRoute r;
+  const int rc = attn_route("buctd_attn_smallqk_plan", 1, T, R4, C, flag, p_drop, dseed != 0, &r);
+  if (rc != BUCTD_OK) return rc;
+  out[0] = r.split; out[1] = r.R4; out[2] = r.CF; out[3] = r.pieces; out[4] = r.stats; out[5] = r.drop; out[6] = r.dseed;
+  return BUCTD_OK;
+}
+
 template <int R4, int CF, bool DSEED>
-static void attn_launch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
+static void attn_launch(int which, const AttnRoute& rt, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
   const AttnArgs& a = kernel_args(ka);     // without dropout the seed is not read: the value kernels run
   const dim3 grid(a.T / 64, B);
-  const bool drop = a.p_drop > 0.f;
+  const bool drop = rt.drop;
 #define ATTN_SPLIT(kern)                                                                                         \
   do {                                                                                                           \
-    if (a.b3 == 3) {                                                                                             \
+    if (rt.pieces == 3) {                                                                                        \
       if (drop) hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, true, 3, DSEED>), grid, dim3(256), 0, st, ka);    \
       else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 3, false>), grid, dim3(256), 0, st, a);         \
     } else {                                                                                                     \
@@ -771,14 +839,14 @@ static void attn_launch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B,
       else hipLaunchKernelGGL((kern<R4 <= 8 ? R4 : 4, CF, false, 2, false>), grid, dim3(256), 0, st, a);         \
     }                                                                                                            \
   } while (0)
-  if (which == 1 && a.b3 && R4 <= 8) {
+  if (which == 1 && rt.split) {
     ATTN_SPLIT(attn_fwd_b3_kernel);
   } else if (which == 1) {
     if (drop) hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, true, DSEED>), grid, dim3(256), 0, st, ka);
     else hipLaunchKernelGGL((attn_fwd_kernel<R4, CF, false, false>), grid, dim3(256), 0, st, a);
-  } else if (which == 2 && a.b3 && R4 <= 8) {
+  } else if (which == 2 && rt.split) {
     ATTN_SPLIT(attn_bwd_q_b3_kernel);
-  } else if (which == 3 && a.b3 && R4 <= 8) {
+  } else if (which == 3 && rt.split) {
     ATTN_SPLIT(attn_bwd_kv_b3_kernel);
 #undef ATTN_SPLIT
   } else if (which == 2) {
@@ -790,19 +858,21 @@ static void attn_launch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B,
   }
 }
 template <int R4, bool DSEED>
-static void attn_dispatch_c(int which, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
-  switch (kernel_args(ka).C) {
-    case 16: attn_launch<R4, 1, DSEED>(which, ka, B, st); break;
-    case 32: attn_launch<R4, 2, DSEED>(which, ka, B, st); break;
-    case 48: attn_launch<R4, 3, DSEED>(which, ka, B, st); break;
-    case 64: attn_launch<R4, 4, DSEED>(which, ka, B, st); break;
-    case 96: attn_launch<R4, 6, DSEED>(which, ka, B, st); break;
-    case 128: attn_launch<R4, 8, DSEED>(which, ka, B, st); break;
-    default: attn_launch<R4, 12, DSEED>(which, ka, B, st); break;
+static void attn_dispatch_c(int which, const AttnRoute& rt, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
+  switch (rt.CF * 16) {
+    case 16: attn_launch<R4, 1, DSEED>(which, rt, ka, B, st); break;
+    case 32: attn_launch<R4, 2, DSEED>(which, rt, ka, B, st); break;
+    case 48: attn_launch<R4, 3, DSEED>(which, rt, ka, B, st); break;
+    case 64: attn_launch<R4, 4, DSEED>(which, rt, ka, B, st); break;
+    case 96: attn_launch<R4, 6, DSEED>(which, rt, ka, B, st); break;
+    case 128: attn_launch<R4, 8, DSEED>(which, rt, ka, B, st); break;
+    default: attn_launch<R4, 12, DSEED>(which, rt, ka, B, st); break;
   }
 }
+// which: 0 statistics, 1 forward, 2 dq', 3 dk' / dV
 template <bool DSEED>
-static void attn_dispatch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int R4, int B, hipStream_t st) {
+static void attn_dispatch(int which, const AttnRoute& rt, const SeededArgs<AttnArgs, DSEED>& ka, int B, hipStream_t st) {
+  const int R4 = rt.R4;
   if (which == 0) {
     const AttnArgs& a = kernel_args(ka);
     const dim3 grid(ceil_div(a.T, 256), B);
@@ -812,15 +882,11 @@ static void attn_dispatch(int which, const SeededArgs<AttnArgs, DSEED>& ka, int 
     else hipLaunchKernelGGL((attn_stats_kernel<20>), grid, dim3(256), 0, st, a);
     return;
   }
-  if (R4 == 4) attn_dispatch_c<4, DSEED>(which, ka, B, st);
-  else if (R4 == 8) attn_dispatch_c<8, DSEED>(which, ka, B, st);
-  else if (R4 == 16) attn_dispatch_c<16, DSEED>(which, ka, B, st);
-  else attn_dispatch_c<20, DSEED>(which, ka, B, st);
+  if (R4 == 4) attn_dispatch_c<4, DSEED>(which, rt, ka, B, st);
+  else if (R4 == 8) attn_dispatch_c<8, DSEED>(which, rt, ka, B, st);
+  else if (R4 == 16) attn_dispatch_c<16, DSEED>(which, rt, ka, B, st);
+  else attn_dispatch_c<20, DSEED>(which, rt, ka, B, st);
 }
-
-// flag of the C ABI -> pieces per operand: 0 fp32 MFMA kernels, 1 -> two bf16 pieces, 2 -> three (bf16x6; its 192-channel
-// tile rows would need 77 KB of static LDS, so that width stays on the fp32 kernels)
-static int attn_split_mode(int flag, int C) { return flag == 2 ? (C <= 128 ? 3 : 0) : (flag ? 2 : 0); }
 
 static AttnArgs attn_args(int T, int C, float scale, float p_drop, uint64_t seed) {
   AttnArgs a;
@@ -842,16 +908,17 @@ static int attn_smallqk_fwd(const char* who, int B, int T, int R4, int C, const 
                             float scale, float p_drop, SeedArg<DSEED> seed, int bf16x3, float* out, float* m, float* linv,
                             void* stream) {
   BUCTD_CHECK_ARG(q && k && v && out && m && linv && B > 0 && seed_ok(seed), "%s: null argument", who);
-  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "%s: unsupported T=%d R4=%d C=%d", who, T, R4, C);
-  BUCTD_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f && (long)B * T < 2147483647L, "%s: bad p_drop / size", who);
+  AttnRoute rt;
+  const int rc = attn_route(who, B, T, R4, C, bf16x3, p_drop, DSEED, &rt);
+  if (rc != BUCTD_OK) return rc;
   SeededArgs<AttnArgs, DSEED> ka = attn_args(T, C, scale, p_drop, seed);
   AttnArgs& a = kernel_args(ka);
-  a.q = q; a.k = k; a.v = v; a.m = m; a.linv = linv; a.out = out; a.b3 = attn_split_mode(bf16x3, C);
-  if (!(a.b3 && R4 <= 8)) {            // the bf16x3 forward kernel computes the soft-max statistics on the fly
-    attn_dispatch<DSEED>(0, ka, R4, B, (hipStream_t)stream);
+  a.q = q; a.k = k; a.v = v; a.m = m; a.linv = linv; a.out = out; a.b3 = rt.pieces;
+  if (rt.stats) {
+    attn_dispatch<DSEED>(0, rt, ka, B, (hipStream_t)stream);
     BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_fwd(stats)");
   }
-  attn_dispatch<DSEED>(1, ka, R4, B, (hipStream_t)stream);
+  attn_dispatch<DSEED>(1, rt, ka, B, (hipStream_t)stream);
   BUCTD_CHECK_LAUNCH(who);
   return BUCTD_OK;
 }
@@ -863,16 +930,18 @@ static int attn_smallqk_bwd(const char* who, int B, int T, int R4, int C, const 
                             void* stream) {
   BUCTD_CHECK_ARG(q && k && v && o && dout && m && linv && dq && dk && dv && dvec_workspace && B > 0 && seed_ok(seed),
                   "%s: null argument", who);
-  BUCTD_CHECK_ARG(attn_shape_ok(T, R4, C), "%s: unsupported T=%d R4=%d C=%d", who, T, R4, C);
+  AttnRoute rt;
+  const int rc = attn_route(who, B, T, R4, C, bf16x3, p_drop, DSEED, &rt);
+  if (rc != BUCTD_OK) return rc;
   SeededArgs<AttnArgs, DSEED> ka = attn_args(T, C, scale, p_drop, seed);
   AttnArgs& a = kernel_args(ka);
   a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout;
-  a.m = const_cast<float*>(m); a.linv = const_cast<float*>(linv); a.dvec = dvec_workspace; a.b3 = attn_split_mode(bf16x3, C);
+  a.m = const_cast<float*>(m); a.linv = const_cast<float*>(linv); a.dvec = dvec_workspace; a.b3 = rt.pieces;
   a.out = dq;
-  attn_dispatch<DSEED>(2, ka, R4, B, (hipStream_t)stream);
+  attn_dispatch<DSEED>(2, rt, ka, B, (hipStream_t)stream);
   BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(q)");
   a.out = dk; a.out2 = dv;
-  attn_dispatch<DSEED>(3, ka, R4, B, (hipStream_t)stream);
+  attn_dispatch<DSEED>(3, rt, ka, B, (hipStream_t)stream);
   BUCTD_CHECK_LAUNCH("buctd_attn_smallqk_bwd(kv)");
   return BUCTD_OK;
 }

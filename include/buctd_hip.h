@@ -427,6 +427,17 @@ int buctd_softmax_dropout_bwd_dseed(const float* dpd, const float* p, long rows,
  * buctd_conv3x3_bf16x3), 2 = three pieces, six MFMAs per product (fp32 class, as buctd_conv3x3_bf16x6; C <= 128).
  * R4 <= 8 only; wider contractions silently use the fp32 kernels. */
 int buctd_attn_smallqk_supported(int T, int R4, int C);
+/* What buctd_attn_smallqk_fwd / _bwd (dseed = 0) or their _dseed forms (dseed != 0) would launch for these arguments: no
+ * launch, no device (the query and the launches call the same routing function).  flag is their bf16x3 argument.
+ * out[BUCTD_ATTN_SMALLQK_PLAN_INTS]:
+ *   [0] kernel family   0 = fp32 MFMA kernels, 1 = split-bf16 kernels
+ *   [1] R4  [2] CF = C / 16       the template arguments of the family's kernels
+ *   [3] bf16 pieces per operand   0 (fp32 family), 2 or 3
+ *   [4] the forward runs the separate statistics pass (the split forward keeps the statistics itself)
+ *   [5] DROP   [6] DSEED          dropout kernels; seed read from device memory (without dropout: the value kernels)
+ * Returns what the launches return for a shape or p_drop they refuse (out is then all zero). */
+#define BUCTD_ATTN_SMALLQK_PLAN_INTS 7
+int buctd_attn_smallqk_plan(int T, int R4, int C, int flag, float p_drop, int dseed, int* out);
 int buctd_attn_smallqk_fwd(int B, int T, int R4, int C, const float* q, const float* k, const float* v, float scale,
                            float p_drop, uint64_t seed, int bf16x3, float* out, float* m, float* linv, void* stream);
 /* dq/dk: [B][T][R4] gradients of q'/k'; dv: [B][T][C]; dvec_workspace: B*T floats. */

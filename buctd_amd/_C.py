@@ -114,6 +114,23 @@ class KptMatchArgs(C.Structure):        # mirrors buctd_kpt_match_args
                                            "dt_matched", "dt_ignored")])
 
 
+class VisCanvas(C.Structure):           # mirrors buctd_vis_canvas (one row of the canvas table in device memory)
+    _fields_ = [("base", C.c_void_p), ("row_stride", C.c_long), ("H", C.c_int), ("W", C.c_int)]
+
+
+class VisPoseArgs(C.Structure):         # mirrors buctd_vis_pose_args
+    _fields_ = ([(n, C.c_void_p) for n in ("canvases", "person_offsets", "persons", "joints", "skeleton", "palette",
+                                           "tiles")] +
+                [(n, C.c_int) for n in ("C", "P", "K", "L", "n_palette", "n_tiles", "canvas_h_max", "canvas_w_max",
+                                        "style", "thickness", "radius")] +
+                [("score_thresh", C.c_float), ("alpha256", C.c_int)])
+
+
+# BUCTD_VIS_POSE_* of the header
+VIS_POSE_PLAIN, VIS_POSE_PRETTY = 0, 1
+VIS_POSE_TILE_W, VIS_POSE_TILE_H, VIS_POSE_CHUNK = 64, 16, 256
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -294,6 +311,8 @@ SIGNATURES = {
     "buctd_vis_minmax": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _P]),
     "buctd_vis_heatmap_grid": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "buctd_vis_joint_grid": (_I, [_P, _I, _I, _I, _L, _L, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    # pose overlays (csrc/vis_pose.hip)
+    "buctd_vis_pose_overlay": (_I, [C.POINTER(VisPoseArgs), _P]),
     "buctd_argmax_decode_refined": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_argmax_decode_dark": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gaussian_target": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),

@@ -1068,6 +1068,71 @@ int buctd_vis_joint_grid(const float* img, int B, int H, int W, long sb, long sc
                          const float* cond, const float* cond_vis, int nrow, int padding, int bgr, uint8_t* out,
                          void* stream);
 
+/* Pose overlays (csrc/vis_pose.hip): the skeletons of any number of persons drawn onto any number of uint8 RGB
+ * canvases of different sizes, in place, in one launch - what the reference does with cv2.line / cv2.circle person after
+ * person (tools/vis.py:plot_keypoints, lib/utils/vis.py:vis_keypoints).  Every table lies in device memory.
+ *
+ * Joint.  Joint j of person p is joints[(p*K + j)*3 ...] = x, y, score.  It counts only if x, y and score are finite
+ * and score > score_thresh.  Its pixel is ((int)x + dx, (int)y + dy), truncation toward zero, (dx, dy) the person's
+ * offset; a pixel coordinate outside [-8192, 8191] makes the joint absent.
+ * End point.  A limb is (a0, a1, b0, b1, colour): end A is the floor midpoint of the pixels of the joints a0 and a1,
+ * (xa0 + xa1) >> 1 and (ya0 + ya1) >> 1 with an arithmetic shift, valid if both joints count (a0 == a1: a plain joint);
+ * end B likewise.  colour is a row of the palette or -1 for the person's colour.  A limb with a joint index outside
+ * [0, K) or a colour outside [-1, n_palette) is not drawn.
+ *
+ * Coverage of pixel X, exact in 64-bit integers.  Coordinates lie in [-8192, 8191], so a difference is below 2^14, a
+ * dot product below 2^29, and with thickness, radius <= 16384 every product below stays under 2^62.
+ *   segment P-Q of thickness t: 4 d^2 <= t^2, d the distance from X to the segment.  v = Q - P, w = X - P, c1 = w.v,
+ *     c2 = v.v;  c1 <= 0: 4 |w|^2 <= t^2;  c1 >= c2: 4 |X - Q|^2 <= t^2;  else 4 (|w|^2 c2 - c1^2) <= t^2 c2.
+ *     P == Q is the first case.
+ *   disc of radius r at Z: |X - Z|^2 <= r^2.
+ *   ring of radius r and thickness t at Z: (2r - t)^2 <= 4 |X - Z|^2 <= (2r + t)^2, the lower bound dropped when 2r <= t.
+ *
+ * Paint order: persons in table order (canvas c owns the persons person_offsets[c] .. person_offsets[c+1] - 1), and
+ * within a person
+ *   BUCTD_VIS_POSE_PLAIN (plot_keypoints): a ring (radius, thickness) at every counting joint in joint order, then the
+ *     segment of every limb whose two ends are valid, in table order; all in the person's colour.
+ *   BUCTD_VIS_POSE_PRETTY (vis_keypoints): per limb in table order the segment if both ends are valid, then the disc
+ *     (radius) at A if valid, then at B if valid, all three in the limb's colour.
+ * The last primitive that covers a pixel decides its colour.  A primitive covers only pixels inside the person's clip
+ * rectangle [x0, x1) x [y0, y1) (canvas pixels) and the canvas.
+ * Blend of a covered pixel, per channel: (img * (256 - alpha256) + colour * alpha256 + 128) >> 8.  No other byte is
+ * written: uncovered pixels, the bytes of a row beyond 3*W and a canvas without persons keep their bits, and alpha256 = 0
+ * writes nothing.
+ *
+ * One workgroup draws one BUCTD_VIS_POSE_TILE_W x BUCTD_VIS_POSE_TILE_H tile; `tiles` lists them as (canvas, tile
+ * column, tile row) and is filled by the caller from the canvas sizes it knows (a canvas needs no tile where nobody is
+ * drawn; a tile listed twice is an error of the caller).  A workgroup examines its canvas's primitives
+ * BUCTD_VIS_POSE_CHUNK at a time.  Entries of `tiles` and person ranges that point outside the tables, and canvases
+ * larger than canvas_h_max x canvas_w_max or with row_stride < 3*W, draw nothing. */
+#define BUCTD_VIS_POSE_PLAIN 0
+#define BUCTD_VIS_POSE_PRETTY 1
+#define BUCTD_VIS_POSE_TILE_W 64
+#define BUCTD_VIS_POSE_TILE_H 16
+#define BUCTD_VIS_POSE_CHUNK 256
+typedef struct buctd_vis_canvas {
+  uint8_t* base;     /* pixel (x, y), channel c at base[y*row_stride + 3*x + c] */
+  long row_stride;   /* bytes, >= 3*W */
+  int H, W;          /* 1 .. 8192 */
+} buctd_vis_canvas;
+typedef struct buctd_vis_pose_args {
+  const buctd_vis_canvas* canvases;   /* [C] */
+  const int* person_offsets;          /* [C+1], ascending, person_offsets[C] <= P */
+  const int* persons;                 /* [P][7]: dx, dy, clip x0, y0, x1, y1, colour r | g << 8 | b << 16 */
+  const float* joints;                /* [P][K][3] */
+  const int* skeleton;                /* [L][5]: a0, a1, b0, b1, colour */
+  const uint8_t* palette;             /* [n_palette][3] r, g, b; may be NULL with n_palette 0 */
+  const int* tiles;                   /* [n_tiles][3]: canvas, tile column, tile row */
+  int C, P, K, L, n_palette, n_tiles;
+  int canvas_h_max, canvas_w_max;     /* the largest H and W of the canvas table, <= 8192 */
+  int style, thickness, radius;       /* thickness 1 .. 16384, radius 0 .. 16384 */
+  float score_thresh;
+  int alpha256;                       /* 0 .. 256 */
+} buctd_vis_pose_args;
+/* One launch, none when P or n_tiles is 0.  BUCTD_EINVAL before any launch: a NULL table, C < 1, P < 0, n_tiles < 0,
+ * K or L outside 1 .. 64, n_palette < 0, an unknown style, thickness, radius, alpha256 or canvas_*_max out of range. */
+int buctd_vis_pose_overlay(const buctd_vis_pose_args* a, void* stream);
+
 /* ------------------------------------------------------------- bf16 inference --- */
 /* Eval forward of the HRNet / preNet networks in bf16 storage (csrc/conv_bf16.hip, buctd_amd/ops_bf16.py).
  * bf16 tensors are passed as raw bit patterns (uint16_t).  Activations bf16 NHWC [N][H][W][C]; a conv layer is a

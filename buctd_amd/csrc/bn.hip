@@ -426,6 +426,26 @@ extern "C" size_t buctd_bn_bwd_workspace(long rows, int C) {
   return (size_t)(nchunks * 2 * C + 2 * C) * sizeof(float);
 }
 
+// finalize (fp64 merge of `nparts` partial (s1, s2) sums [nparts][2][C] into s [2][C], dgamma / dbeta) + apply (dz, optional
+// dres): everything of a BatchNorm backward after its reduction pass.  who_finalize / who_apply name the two launches in
+// the caller's error messages
+static int bn_bwd_tail(const char* who_finalize, const char* who_apply, const float* dy, const float* y, const float* z, const float* mean, const float* invstd,
+                       const float* gamma, const float* beta, int relu, long rows, int C, const float* part, int nparts,
+                       float* s, float* dz, float* dres, float* dgamma, float* dbeta, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, part, nparts, C, s, dgamma, dbeta, accumulate);
+  BUCTD_CHECK_LAUNCH(who_finalize);
+  const long total = rows * C;
+  const float inv_rows = 1.0f / (float)rows;
+  if (C % 4 == 0)
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(stream_grid(total / 4)), dim3(256), 0, st, dy, y, z, mean,
+                       invstd, gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(stream_grid(total)), dim3(256), 0, st, dy, y, z, mean, invstd,
+                       gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
+  BUCTD_CHECK_LAUNCH(who_apply);
+  return BUCTD_OK;
+}
+
 extern "C" int buctd_bn_bwd(const float* dy, const float* y, const float* z, const float* mean, const float* invstd,
                             const float* gamma, const float* beta, int relu, long rows, int C, float* dz, float* dres,
                             float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes,
@@ -452,23 +472,12 @@ extern "C" int buctd_bn_bwd(const float* dy, const float* y, const float* z, con
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nchunks), dim3(256), 0, st, dy, y, z, mean, invstd, gamma, beta, relu, rows,
                        C, part);
   BUCTD_CHECK_LAUNCH("buctd_bn_bwd(reduce)");
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, (const float*)part, nchunks, C, s,
-                     dgamma, dbeta, accumulate);
-  BUCTD_CHECK_LAUNCH("buctd_bn_bwd(finalize)");
-  const long total = rows * C;
-  const float inv_rows = 1.0f / (float)rows;
-  if (C % 4 == 0)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(stream_grid(total / 4)), dim3(256), 0, st, dy, y, z, mean,
-                       invstd, gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(stream_grid(total)), dim3(256), 0, st, dy, y, z, mean, invstd,
-                       gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
-  BUCTD_CHECK_LAUNCH("buctd_bn_bwd(apply)");
-  return BUCTD_OK;
+  return bn_bwd_tail("buctd_bn_bwd(finalize)", "buctd_bn_bwd(apply)", dy, y, z, mean, invstd, gamma, beta, relu, rows, C, part,
+                     nchunks, s, dz, dres, dgamma, dbeta, accumulate, st);
 }
 
-/* The rest of buctd_bn_bwd when the reduction pass already happened elsewhere (buctd_conv3x3_bf16x6_bnstat: the data
- * gradient that produced dy formed the partial sums on its way out): part = [nparts][2][C] partial (s1, s2) sums.
+/* The rest of buctd_bn_bwd when the reduction pass already happened elsewhere: part = [nparts][2][C] partial (s1, s2) sums
+ * over any grouping of the rows, from any producer (the sums buctd_bn_bwd's own reduction forms per row range).
  * workspace: 2 * C floats.  Finalize (fp64 merge, dgamma / dbeta) + apply (dz, optional dres), as buctd_bn_bwd. */
 extern "C" int buctd_bn_bwd_from_partials(const float* dy, const float* y, const float* z, const float* mean,
                                           const float* invstd, const float* gamma, const float* beta, int relu, long rows,
@@ -482,20 +491,9 @@ extern "C" int buctd_bn_bwd_from_partials(const float* dy, const float* y, const
     buctd_set_error("buctd_bn_bwd_from_partials: workspace %zu bytes < required %zu", workspace_bytes, (size_t)2 * C * sizeof(float));
     return BUCTD_EWORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
-  float* s = (float*)workspace;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, part, nparts, C, s, dgamma, dbeta, accumulate);
-  BUCTD_CHECK_LAUNCH("buctd_bn_bwd_from_partials(finalize)");
-  const long total = rows * C;
-  const float inv_rows = 1.0f / (float)rows;
-  if (C % 4 == 0)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(stream_grid(total / 4)), dim3(256), 0, st, dy, y, z, mean,
-                       invstd, gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(stream_grid(total)), dim3(256), 0, st, dy, y, z, mean, invstd,
-                       gamma, beta, (const float*)s, relu, total, C, inv_rows, dz, dres);
-  BUCTD_CHECK_LAUNCH("buctd_bn_bwd_from_partials(apply)");
-  return BUCTD_OK;
+  return bn_bwd_tail("buctd_bn_bwd_from_partials(finalize)", "buctd_bn_bwd_from_partials(apply)", dy, y, z, mean, invstd, gamma,
+                     beta, relu, rows, C, part, nparts, (float*)workspace, dz, dres, dgamma, dbeta, accumulate,
+                     (hipStream_t)stream);
 }
 
 extern "C" int buctd_bn_fold(const float* gamma, const float* beta, const float* running_mean,

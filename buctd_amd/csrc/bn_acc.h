@@ -148,7 +148,7 @@ __device__ __forceinline__ void bnacc_running(const BnFwdStat& s, double rows, f
 
 // What a consumer of forward statistics needs besides the accumulator: written once per launch by ONE workgroup.
 struct BnAccFwd {
-  const long long* acc;      // null: the consumer takes mean / invstd from memory as before
+  const long long* acc;      // null: the consumer applies no BatchNorm to its input
   double rows;               // values per channel
   float eps, momentum;
   float* mean_out;           // [C] (+ invstd_out [C]): the statistics in the form the backward kernels read

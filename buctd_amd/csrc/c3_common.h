@@ -44,9 +44,8 @@ struct C3Args {
   int relu, na;        // na: 32-row groups of the staged tile = ceil((BM + 2*SW + 2) / 32)
   // optional BatchNorm(+ReLU) of the PRODUCER applied to the input while it is staged (bf16x6 kernel only): the input
   // tensor is the producer's raw convolution output z and the kernel consumes relu((z - mean) * (invstd * gamma) + beta),
-  // the exact expression of bn_apply_kernel - the normalised tensor never exists in HBM
-  const float* in_mean;
-  const float* in_invstd;
+  // the exact expression of bn_apply_kernel - the normalised tensor never exists in HBM.  mean and invstd come from the
+  // producer's accumulator (in_acc below)
   const float* in_gamma;
   const float* in_beta;
   int in_relu;
@@ -55,25 +54,24 @@ struct C3Args {
   // output map of the gathered kernels (conv_gather_x6.hip; omap = 0: the H x W grid itself): grid pixel (y, x) is written
   // to pixel (y * ost + oy0, x * ost + ox0) of an oH x oW tensor - the parity classes of a stride-2 data gradient
   int omap, oH, oW, ost, oy0, ox0;
-  // optional by-product of a DATA-GRADIENT launch (conv3x3.hip only): the reduction pass of the BatchNorm backward that
-  // consumes this launch's output g = out (after the residual was added) - per row group the partial sums
+  // optional by-product of a DATA-GRADIENT launch (conv3x3.hip only; on where bs_acc is set): the reduction pass of the
+  // BatchNorm backward that consumes this launch's output g = out (after the residual was added) - the sums
   //   s1[c] = sum_rows m * g,   s2[c] = sum_rows m * g * (z - mean[c]) * invstd[c],   m = ReLU mask of the BatchNorm's
   // forward output (bs_y > 0 where given, else rebuilt as (z - mean) * (invstd * gamma) + beta > 0, bn_apply's expression)
-  // - exactly the sums of bn_bwd_reduce2_kernel, formed while the tile is on its way out instead of by a kernel that
-  // reads g, z and y again.  bs_part: [groups][2][Co] floats, groups as the forward statistics (bx * WM + wave_m).
+  // - the terms of bn_bwd_reduce2_kernel, formed while the tile is on its way out instead of by a kernel that
+  // reads g, z and y again, and added to the accumulator bs_acc below.
   const float* bs_z;
   const float* bs_y;
   const float* bs_mean;
   const float* bs_invstd;
   const float* bs_gamma;
   const float* bs_beta;
-  float* bs_part;
-  // The same two by-products as exact integer accumulators (bn_acc.h) instead of per-group partials: the consumer of the
+  // Statistics as exact integer accumulators (bn_acc.h) instead of per-group partials: the consumer of the
   // statistics decodes two numbers per channel in its prologue and no finalize launch sits between the two kernels.
   //   stats_acc: forward statistics (sum z, sum z^2) of this launch's output;  bs_acc: the BatchNorm-backward sums above.
   long long* stats_acc;
   long long* bs_acc;
-  // in_acc.acc != null: the producer's statistics (in_mean / in_invstd) are decoded from ITS accumulator in this launch's
+  // in_acc.acc != null: the producer's statistics (mean / invstd) are decoded from ITS accumulator in this launch's
   // prologue; the workgroup of tile (0, 0) also writes them out (in_acc.mean_out / invstd_out, running statistics)
   BnAccFwd in_acc;
 };
@@ -245,7 +243,7 @@ __device__ __forceinline__ void c3_epilogue(const C3Args& p, f32x4 (&acc)[MF][NF
       }
     }
   }
-  // BatchNorm-backward partial sums of the outgoing tile (C3Args::bs_part).  Item k of a lane has column quad
+  // BatchNorm-backward sums of the outgoing tile (C3Args::bs_acc).  Item k of a lane has column quad
   // c4 = (lane + 64 k) % (NF * 4): NACC distinct quads per lane, one accumulator pair each.
   constexpr int Q4 = NF * 4;
   constexpr int NACC = (64 % Q4 == 0) ? 1 : 3;       // NF = 3: 64 = 4 mod 12 -> three quads per lane; else one
@@ -253,7 +251,7 @@ __device__ __forceinline__ void c3_epilogue(const C3Args& p, f32x4 (&acc)[MF][NF
   f32x4 bs1[NACC], bs2[NACC];
 #pragma unroll
   for (int j = 0; j < NACC; ++j) bs1[j] = bs2[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const bool bs_on = p.bs_part != nullptr || p.bs_acc != nullptr;
+  const bool bs_on = p.bs_acc != nullptr;
   const bool bs_rebuild = bs_on && p.bs_y == nullptr;
   // Every wave stages through ITS OWN slice of LDS (stg, rowoff) and the LDS executes one wave's operations in order, so
   // the passes need no workgroup barrier - only the compiler must keep the stores in front of the loads (wave_barrier).
@@ -361,30 +359,21 @@ __device__ __forceinline__ void c3_epilogue(const C3Args& p, f32x4 (&acc)[MF][NF
           a2 += red[(j * 64 + l) * 2 + 1];
         }
       }
-      if (p.bs_part) {
-        float* dst = p.bs_part + ((long)grp * 2) * p.Co + ncol0 + lane * 4;
-        *reinterpret_cast<f32x4*>(dst) = a1;
-        *reinterpret_cast<f32x4*>(dst + p.Co) = a2;
-      }
-      if (p.bs_acc) {
-        // [wave_m][BN] pairs: the wave's fp32 sums of its rows, channel by channel
+      // [wave_m][BN] pairs: the wave's fp32 sums of its rows, channel by channel
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          exch[wave_m * (WN * NF * 16) + wave_n * NF * 16 + lane * 4 + j] = make_double2((double)a1[j], (double)a2[j]);
-      }
+      for (int j = 0; j < 4; ++j)
+        exch[wave_m * (WN * NF * 16) + wave_n * NF * 16 + lane * 4 + j] = make_double2((double)a1[j], (double)a2[j]);
     }
-    if (p.bs_acc) {
-      __syncthreads();
-      if (t < WN * NF * 16) {
-        double a1 = 0.0, a2 = 0.0;
+    __syncthreads();
+    if (t < WN * NF * 16) {
+      double a1 = 0.0, a2 = 0.0;
 #pragma unroll
-        for (int w = 0; w < WM; ++w) {
-          const double2 v = exch[w * (WN * NF * 16) + t];
-          a1 += v.x;
-          a2 += v.y;
-        }
-        bnacc_add(p.bs_acc, p.Co, bnacc_shard(), n0 + t, a1, a2);
+      for (int w = 0; w < WM; ++w) {
+        const double2 v = exch[w * (WN * NF * 16) + t];
+        a1 += v.x;
+        a2 += v.y;
       }
+      bnacc_add(p.bs_acc, p.Co, bnacc_shard(), n0 + t, a1, a2);
     }
   }
 }

@@ -239,7 +239,7 @@ __device__ __forceinline__ void c3x6_tile(const C3Args& p, unsigned char* smem, 
   const int i16 = lane & 15, g = lane >> 4;
   const int wave_m = wave % WM, wave_n = wave / WM;
   const int p0 = bx * BM, n0 = by * BN;
-  const bool in_bn = p.in_mean != nullptr || p.in_acc.acc != nullptr;
+  const bool in_bn = p.in_acc.acc != nullptr;
   const int halo = p.SW + 1;
   const int c4 = (t % CPR) * 4, prow = t / CPR;
 
@@ -386,26 +386,18 @@ __device__ __forceinline__ void c3x6_tile(const C3Args& p, unsigned char* smem, 
   if constexpr (BPF) load_b(0, bn);
   if constexpr (BPF2) load_b(last_step > 0 ? 1 : 0, bn2);
   if (in_bn) {
-    // the producer's BatchNorm as (mean, invstd * gamma, beta) per input channel, under the first chunk's loads: from the
-    // arrays a finalize launch left, or decoded from the producer's accumulator (bn_acc.h) - then tile (0, 0) also
-    // leaves mean / invstd for the backward kernels and updates the running statistics
+    // the producer's BatchNorm as (mean, invstd * gamma, beta) per input channel, under the first chunk's loads: decoded
+    // from the producer's accumulator (bn_acc.h); tile (0, 0) also leaves mean / invstd for the backward kernels and
+    // updates the running statistics
     for (int c = t; c < p.Ci; c += 256) {
-      float m, is;
-      if (p.in_acc.acc) {
-        const BnFwdStat st = bnacc_fwd_stat(p.in_acc.acc, p.Ci, c, p.in_acc.rows, p.in_acc.eps);
-        m = st.mean;
-        is = st.invstd;
-        if (bx == 0 && by == 0) {
-          p.in_acc.mean_out[c] = m;
-          p.in_acc.invstd_out[c] = is;
-          if (p.in_acc.rmean) bnacc_running(st, p.in_acc.rows, p.in_acc.momentum, p.in_acc.rmean, p.in_acc.rvar, c);
-        }
-      } else {
-        m = p.in_mean[c];
-        is = p.in_invstd[c];
+      const BnFwdStat st = bnacc_fwd_stat(p.in_acc.acc, p.Ci, c, p.in_acc.rows, p.in_acc.eps);
+      if (bx == 0 && by == 0) {
+        p.in_acc.mean_out[c] = st.mean;
+        p.in_acc.invstd_out[c] = st.invstd;
+        if (p.in_acc.rmean) bnacc_running(st, p.in_acc.rows, p.in_acc.momentum, p.in_acc.rmean, p.in_acc.rvar, c);
       }
-      bntab[c] = m;
-      bntab[p.Ci + c] = is * p.in_gamma[c];
+      bntab[c] = st.mean;
+      bntab[p.Ci + c] = st.invstd * p.in_gamma[c];
       bntab[2 * p.Ci + c] = p.in_beta[c];
     }
     __syncthreads();
@@ -764,9 +756,9 @@ static int c3_prep(int np, int Ci, int Co, const float* w, int flip, void* wprep
 // x: [N][H][W][Ci] -> y: [N][H][W][Co], wprep from the matching prep call.  Forward: prep(Ci, Co, w, 0).
 // Data gradient of a forward conv (CiF -> CoF): x = dy ([N][H][W][CoF]), y = dx ([N][H][W][CiF]), i.e. this call's
 // Ci = CoF, Co = CiF, and wprep = prep(CiF, CoF, w, 1).
-struct C3InBn { const float* mean; const float* invstd; const float* gamma; const float* beta; int relu; };
+struct C3InBn { const float* gamma; const float* beta; int relu; };
 // BatchNorm-backward reduction as a by-product of a data-gradient launch (C3Args::bs_*)
-struct C3BwdStat { const float* z; const float* y; const float* mean; const float* invstd; const float* gamma; const float* beta; float* part; long long* acc; };
+struct C3BwdStat { const float* z; const float* y; const float* mean; const float* invstd; const float* gamma; const float* beta; long long* acc; };
 // accumulator forms (bn_acc.h): the launch's own forward statistics, and the input BatchNorm's statistics decoded in the prologue
 struct C3Acc { long long* stats_acc; const buctd_bn_acc_in* in; };
 
@@ -802,14 +794,8 @@ static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, 
   a.x = x; a.wp = (const unsigned char*)wprep; a.out = y; a.bias = bias; a.scale = scale; a.shift = shift;
   a.res = residual; a.stats = stats_partials; a.counts = stats_counts;
   a.relu = relu;
-  a.in_mean = a.in_invstd = a.in_gamma = a.in_beta = nullptr;
+  a.in_gamma = a.in_beta = nullptr;
   a.in_relu = 0;
-  if (in_bn && in_bn->mean) {
-    BUCTD_CHECK_ARG(np == 3 && in_bn->invstd && in_bn->gamma && in_bn->beta,
-                    "buctd_conv3x3: fused input BatchNorm needs the bf16x6 kernel and all four statistics arrays");
-    a.in_mean = in_bn->mean; a.in_invstd = in_bn->invstd; a.in_gamma = in_bn->gamma; a.in_beta = in_bn->beta;
-    a.in_relu = in_bn->relu;
-  }
   a.stats_acc = nullptr; a.bs_acc = nullptr;
   memset(&a.in_acc, 0, sizeof(a.in_acc));
   if (accs) {
@@ -817,7 +803,7 @@ static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, 
     a.stats_acc = accs->stats_acc;
     if (accs->in && accs->in->acc) {
       const buctd_bn_acc_in& i = *accs->in;
-      BUCTD_CHECK_ARG(in_bn && !in_bn->mean && in_bn->gamma && in_bn->beta && i.rows > 0 && i.mean_out && i.invstd_out &&
+      BUCTD_CHECK_ARG(in_bn && in_bn->gamma && in_bn->beta && i.rows > 0 && i.mean_out && i.invstd_out &&
                           (i.running_mean == nullptr) == (i.running_var == nullptr),
                       "buctd_conv3x3: input BatchNorm from an accumulator needs gamma, beta, rows, mean_out and invstd_out");
       a.in_gamma = in_bn->gamma; a.in_beta = in_bn->beta; a.in_relu = in_bn->relu;
@@ -826,12 +812,11 @@ static int c3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, 
     }
   }
   a.bs_z = a.bs_y = a.bs_mean = a.bs_invstd = a.bs_gamma = a.bs_beta = nullptr;
-  a.bs_part = nullptr;
-  if (bst && (bst->part || bst->acc)) {
+  if (bst && bst->acc) {
     BUCTD_CHECK_ARG(np == 3 && bst->z && bst->mean && bst->invstd && (bst->y || (bst->gamma && bst->beta)),
                     "buctd_conv3x3: the BatchNorm-backward by-product needs the bf16x6 kernel, z, mean, invstd and y or gamma + beta");
     a.bs_z = bst->z; a.bs_y = bst->y; a.bs_mean = bst->mean; a.bs_invstd = bst->invstd; a.bs_gamma = bst->gamma;
-    a.bs_beta = bst->beta; a.bs_part = bst->part; a.bs_acc = bst->acc;
+    a.bs_beta = bst->beta; a.bs_acc = bst->acc;
   }
   return BUCTD_OK;
 }
@@ -848,7 +833,7 @@ static int c3_lean_mask(int m) {
 static int c3_lean_mode(const C3Args& a) {
   // (tensors are addressed through buffer descriptors with 32-bit byte offsets, pad rows by an offset beyond 2 GB)
   if ((long)a.N * a.H * a.W * (a.Ci > a.Co ? a.Ci : a.Co) * 4 >= 2147483648L) return -1;
-  if (a.bias || a.scale || a.shift || a.relu || a.stats || a.counts || a.bs_part || a.omap || a.in_mean || a.in_invstd) return -1;
+  if (a.bias || a.scale || a.shift || a.relu || a.stats || a.counts || a.omap) return -1;
   if (a.in_acc.acc && (!a.in_gamma || !a.in_beta)) return -1;
   int m = 0;
   if (a.in_acc.acc) m |= C3M_IN_BN;
@@ -999,40 +984,22 @@ extern "C" int buctd_conv3x3_bf16x6(int N, int H, int W, int Ci, int Co, const f
                                     int relu, float* y, float* stats_partials, int* stats_counts, void* stream) {
   return c3_run(3, N, H, W, Ci, Co, x, wprep, bias, scale, shift, residual, relu, y, stats_partials, stats_counts, stream);
 }
-extern "C" int buctd_conv3x3_bf16x6_bnin(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep,
-                                         const float* bias, const float* scale, const float* shift,
-                                         const float* residual, int relu, float* y, float* stats_partials,
-                                         int* stats_counts, const float* in_mean, const float* in_invstd,
-                                         const float* in_gamma, const float* in_beta, int in_relu, void* stream) {
-  C3InBn b{in_mean, in_invstd, in_gamma, in_beta, in_relu};
-  return c3_run(3, N, H, W, Ci, Co, x, wprep, bias, scale, shift, residual, relu, y, stats_partials, stats_counts, stream, &b);
-}
-
-/* Data gradient of a 3x3 convolution (buctd_conv3x3_bf16x6 on the flipped image, residual = the skip gradient) that also
- * forms the reduction pass of the BatchNorm backward consuming its output g = dx: per row group (the groups of
- * buctd_conv3x3_bf16x6_stats_groups(N, H, W, Ci, Co)) s1 = sum m g, s2 = sum m g zhat with m the ReLU mask of that
- * BatchNorm's forward output (bn_y > 0 where given, else rebuilt from bn_z with gamma / beta) - bn_part [groups][2][Co],
- * the input of buctd_bn_bwd_from_partials.  Replaces the separate pass over g, z and y (bn.hip: bn_bwd_reduce2_kernel). */
-extern "C" int buctd_conv3x3_bf16x6_bnstat(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep,
-                                           const float* residual, float* y, const float* bn_z, const float* bn_y,
-                                           const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
-                                           const float* bn_beta, float* bn_part, void* stream) {
-  C3BwdStat b{bn_z, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, bn_part, nullptr};
-  BUCTD_CHECK_ARG(bn_part, "buctd_conv3x3_bf16x6_bnstat: null partials pointer");
-  return c3_run(3, N, H, W, Ci, Co, x, wprep, nullptr, nullptr, nullptr, residual, 0, y, nullptr, nullptr, stream, nullptr,
-                &b);
-}
 
 /* The accumulator forms (include/buctd_hip.h: "BatchNorm statistics without finalize launches").
  * buctd_conv3x3_bf16x6_acc: forward convolution whose output statistics go to stats_acc (may be null) and whose input may
  * be the raw output of a producing convolution, normalised on the fly with that producer's statistics - decoded from ITS
  * accumulator (in_bn: acc + rows + eps, gamma, beta) in the prologue; tile (0, 0) writes mean / invstd out and updates the
- * running statistics.  buctd_conv3x3_bf16x6_bnstat_acc: the data gradient with the BatchNorm-backward sums as accumulator. */
+ * running statistics.
+ * buctd_conv3x3_bf16x6_bnstat_acc: data gradient of a 3x3 convolution (buctd_conv3x3_bf16x6 on the flipped image, residual =
+ * the skip gradient) that also forms the reduction pass of the BatchNorm backward consuming its output g = dx:
+ * s1 = sum m g, s2 = sum m g zhat with m the ReLU mask of that BatchNorm's forward output (bn_y > 0 where given, else rebuilt
+ * from bn_z with gamma / beta), added to the accumulator bn_acc - the input of buctd_bn_bwd_acc.  Replaces the separate pass
+ * over g, z and y (bn.hip: bn_bwd_reduce2_kernel). */
 extern "C" int buctd_conv3x3_bf16x6_acc(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep,
                                         const float* residual, int relu, float* y, void* stats_acc,
                                         const buctd_bn_acc_in* in_bn, const float* in_gamma, const float* in_beta, int in_relu,
                                         void* stream) {
-  C3InBn b{nullptr, nullptr, in_gamma, in_beta, in_relu};
+  C3InBn b{in_gamma, in_beta, in_relu};
   C3Acc a{(long long*)stats_acc, in_bn};
   BUCTD_CHECK_ARG(!in_bn || in_bn->acc, "buctd_conv3x3_bf16x6_acc: in_bn without an accumulator");
   return c3_run(3, N, H, W, Ci, Co, x, wprep, nullptr, nullptr, nullptr, residual, relu, y, nullptr, nullptr, stream,
@@ -1042,7 +1009,7 @@ extern "C" int buctd_conv3x3_bf16x6_bnstat_acc(int N, int H, int W, int Ci, int 
                                                const float* residual, float* y, const float* bn_z, const float* bn_y,
                                                const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                                const float* bn_beta, void* bn_acc, void* stream) {
-  C3BwdStat b{bn_z, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, nullptr, (long long*)bn_acc};
+  C3BwdStat b{bn_z, bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta, (long long*)bn_acc};
   BUCTD_CHECK_ARG(bn_acc, "buctd_conv3x3_bf16x6_bnstat_acc: null accumulator");
   return c3_run(3, N, H, W, Ci, Co, x, wprep, nullptr, nullptr, nullptr, residual, 0, y, nullptr, nullptr, stream, nullptr,
                 &b);
@@ -1054,8 +1021,8 @@ extern "C" int buctd_conv3x3_bf16x6_bnstat_acc(int N, int H, int W, int Ci, int 
 static int c3_group_fill(int n, const buctd_c3_conv* convs, C3Args* a, C3Plan* pl) {
   for (int k = 0; k < n; ++k) {
     const buctd_c3_conv& c = convs[k];
-    C3InBn ib{nullptr, nullptr, c.in_gamma, c.in_beta, c.in_relu};
-    C3BwdStat bs{c.bn_z, c.bn_y, c.bn_mean, c.bn_invstd, c.bn_gamma, c.bn_beta, nullptr, (long long*)c.bn_acc};
+    C3InBn ib{c.in_gamma, c.in_beta, c.in_relu};
+    C3BwdStat bs{c.bn_z, c.bn_y, c.bn_mean, c.bn_invstd, c.bn_gamma, c.bn_beta, (long long*)c.bn_acc};
     C3Acc ac{(long long*)c.stats_acc, c.in_bn};
     BUCTD_CHECK_ARG(!c.in_bn || c.in_bn->acc, "buctd_conv3x3_bf16x6_group: in_bn without an accumulator");
     const int rc = c3_fill(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.wprep, nullptr, nullptr, nullptr, c.residual, c.relu, c.y,

@@ -712,8 +712,8 @@ static int gc_run(int kind, int dir, int N, int H, int W, int Ci, int Co, const 
   e.SW = r.Wg + 2; e.IB = (r.Hg + 1) * (r.Wg + 2);
   e.P = r.P;
   e.relu = relu; e.na = 0;
-  e.in_mean = e.in_invstd = e.in_gamma = e.in_beta = nullptr; e.in_relu = 0; e.col_major = 0;
-  e.bs_z = e.bs_y = e.bs_mean = e.bs_invstd = e.bs_gamma = e.bs_beta = nullptr; e.bs_part = nullptr;
+  e.in_gamma = e.in_beta = nullptr; e.in_relu = 0; e.col_major = 0;
+  e.bs_z = e.bs_y = e.bs_mean = e.bs_invstd = e.bs_gamma = e.bs_beta = nullptr;
   e.stats_acc = stats_acc; e.bs_acc = nullptr;
   memset(&e.in_acc, 0, sizeof(e.in_acc));
   magic_u32((unsigned)e.IB, &e.ib_mul, &e.ib_sh);

@@ -660,14 +660,10 @@ def _conv3x3_bf16x3(x, w, flip, cin, cout, bias, scale, shift, residual, relu, s
     wp = _conv3x3_prepared(w, flip)
     y = torch.empty((N, H, W, cout), dtype=torch.float32, device=x.device)
     part = counts = info = None
-    acc_mode = (_conv_math["mode"] == "bf16x6" and bias is None and scale is None
-                and (stats == "acc" or isinstance(in_bn, BnAccInput)))
-    if acc_mode:
+    if _conv_math["mode"] == "bf16x6" and bias is None and scale is None and (stats == "acc" or in_bn is not None):
         # statistics as integer accumulators (csrc/bn_acc.h): no partials, no finalize launch
         acc = AccRef(cout, x.device) if stats else None
-        st = in_bn.struct() if isinstance(in_bn, BnAccInput) else None
-        if in_bn is not None and st is None:
-            raise _C.BuctdHipError("conv3x3: the accumulator path takes its input BatchNorm as a BnAccInput")
+        st = in_bn.struct() if in_bn is not None else None
         check(lib().buctd_conv3x3_bf16x6_acc(N, H, W, cin, cout, ptr(x), ptr(wp), ptr(residual), int(bool(relu)), ptr(y),
                                              C.c_void_p(acc.ptr) if acc is not None else None,
                                              C.byref(st) if st is not None else None,
@@ -675,19 +671,10 @@ def _conv3x3_bf16x3(x, w, flip, cin, cout, bias, scale, shift, residual, relu, s
                                              ptr(in_bn.beta) if st is not None else None,
                                              int(bool(in_bn.relu)) if st is not None else 0, stream_ptr()), "conv3x3_bf16x6_acc")
         return (y, acc, ("acc",)) if stats else y
-    if isinstance(in_bn, BnAccInput):
-        raise _C.BuctdHipError("conv3x3: BnAccInput needs the bf16x6 accumulator path (no bias / eval scale)")
     if stats:
         part, info = _stats_buffers(("c3grp", _conv_math["mode"], N, H, W, cin, cout),
                                     lambda ng, rpg: _c3fn("_stats_groups")(N, H, W, cin, cout, ng, rpg), cout, x.device, True)
         counts = info[2]
-    if in_bn is not None:
-        mean, invstd, gamma, beta, in_relu = in_bn
-        check(lib().buctd_conv3x3_bf16x6_bnin(N, H, W, cin, cout, ptr(x), ptr(wp), ptr(bias), ptr(scale), ptr(shift),
-                                              ptr(residual), int(bool(relu)), ptr(y), ptr(part), ptr(counts), ptr(mean),
-                                              ptr(invstd), ptr(gamma), ptr(beta), int(bool(in_relu)), stream_ptr()),
-              "conv3x3_bf16x6_bnin")
-        return (y, part, info) if stats else y
     check(_c3fn("")(N, H, W, cin, cout, ptr(x), ptr(wp), ptr(bias), ptr(scale), ptr(shift),
                     ptr(residual), int(bool(relu)), ptr(y), ptr(part), ptr(counts), stream_ptr()),
           "conv3x3 (split bf16)")
@@ -776,7 +763,7 @@ def native_chain_ok(x_shape):
 
 def bn_in_fusable(x_shape, w):
     """True when a 3x3/s1/p1 convolution of this shape can apply its producer's BatchNorm(+ReLU) while staging its
-    input (bf16x6 kernel): conv_fwd(..., in_bn=...) and conv_wgrad(..., x_bn=...)."""
+    input (bf16x6 kernel): conv_fwd(..., in_bn=BnAccInput) and conv_wgrad(..., x_bn=(mean, invstd, gamma, beta, relu))."""
     if _conv_math["mode"] != "bf16x6" or not _FUSE_BN_IN:
         return False
     ws = _wshape(w)
@@ -790,15 +777,18 @@ def bn_in_fusable(x_shape, w):
 
 def conv_fwd(x, w, bias=None, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False, stats=False,
              in_bn=None):
-    """in_bn = (mean, invstd, gamma, beta, relu) or a BnAccInput: x is the raw output of the producing convolution and its
-    BatchNorm (+ReLU) is applied while the input is staged (only where bn_in_fusable() says so).
+    """in_bn = a BnAccInput: x is the raw output of the producing convolution and its BatchNorm (+ReLU), with the statistics
+    decoded from the producer's accumulator, is applied while the input is staged (only where bn_in_fusable() says so, and
+    without bias / eval scale).
     stats: True -> (y, Welford partials, info) for bn_finalize; "acc" -> (y, AccRef, ("acc",)) where the kernel supports the
     accumulator form (csrc/bn_acc.h: no finalize launch), the partials form elsewhere."""
     _f32(x, "conv input")
     weight_rsc(w)
     d = conv_desc(x.shape, _wshape(w), stride, pad)
-    if in_bn is not None and not (_conv_math["mode"] == "bf16x6" and _bf16x3_ok(d)):
-        raise _C.BuctdHipError("conv_fwd: in_bn needs the bf16x6 3x3 kernel (check bn_in_fusable first)")
+    if in_bn is not None and not (isinstance(in_bn, BnAccInput) and _conv_math["mode"] == "bf16x6" and _bf16x3_ok(d)
+                                  and bias is None and scale is None):
+        raise _C.BuctdHipError("conv_fwd: in_bn must be a BnAccInput and needs the bf16x6 3x3 kernel without bias / eval scale "
+                               "(check bn_in_fusable first)")
     if _bf16x3_ok(d):
         return _conv3x3_bf16x3(x, w, 0, d.Ci, d.Co, bias, scale, shift, residual, relu, stats, in_bn)
     if _gconv_ok(d, 0):
@@ -1583,6 +1573,22 @@ def _count_batch(bn):
     bn.count_batch() if hasattr(bn, "count_batch") else bn.num_batches_tracked.add_(1)
 
 
+def _bn_train(z, part, info, bn, residual, relu, training):
+    """Batch-statistics BatchNorm (+residual) (+ReLU) of a convolution output z whose statistics the convolution returned as
+    (part, info): -> (y, mean, invstd).  Accumulator form: the apply kernel decodes them, no finalize launch; partials form:
+    bn_finalize + bn_apply.  Either updates the running statistics where bn tracks them and `training`; the caller counts the
+    batch."""
+    Cn = z.shape[-1]
+    rows = z.numel() // Cn
+    if info[0] == "acc":
+        bnin = BnAccInput(part, rows, bn, training)
+        return bn_apply_acc(z, bnin, residual, relu), bnin.mean, bnin.invstd
+    track = bn.track_running_stats and training
+    mean, invstd = bn_finalize(part, info, rows, Cn, bn.eps, 0.1 if bn.momentum is None else bn.momentum,
+                               bn.running_mean if track else None, bn.running_var if track else None)
+    return bn_apply(z, mean, invstd, bn.weight, bn.bias, residual, relu), mean, invstd
+
+
 class ConvBnAct(torch.autograd.Function):
     """conv (+bias) -> BatchNorm2d -> (+residual) -> (ReLU), train or eval mode.
 
@@ -1596,23 +1602,12 @@ class ConvBnAct(torch.autograd.Function):
         eps = bn.eps
         ctx.meta = (bn, conv_w, conv_b, relu, stride, pad, training, transposed_shape, tuple(x.shape))
         if training or bn.running_mean is None:
-            momentum = 0.1 if bn.momentum is None else bn.momentum
             if transposed_shape is None:
                 z, part, info = conv_fwd(x, conv_w, conv_b, stride, pad, stats="acc")
             else:
                 z, part, info = conv_dgrad(x, conv_w, transposed_shape, stride, pad, bias=conv_b, stats="acc")
-            Cn = z.shape[-1]
-            rows = z.numel() // Cn
-            track = bn.track_running_stats and training
-            if info[0] == "acc":
-                bnin = BnAccInput(part, rows, bn, training)
-                y = bn_apply_acc(z, bnin, residual, relu)
-                mean, invstd = bnin.mean, bnin.invstd
-            else:
-                mean, invstd = bn_finalize(part, info, rows, Cn, eps, momentum,
-                                           bn.running_mean if track else None, bn.running_var if track else None)
-                y = bn_apply(z, mean, invstd, gamma, beta, residual, relu)
-            if track:
+            y, mean, invstd = _bn_train(z, part, info, bn, residual, relu, training)
+            if bn.track_running_stats and training:
                 _count_batch(bn)
             ctx.has_res = residual is not None
             # without a residual the ReLU mask is rebuilt from z in the backward kernels: y is not kept (nor re-read)
@@ -1804,33 +1799,18 @@ class BasicBlockFn(torch.autograd.Function):
             return _chain_forward(ctx, x, [(w1, bn1, w2, bn2)])
         ctx.native = False
         z1, part, info = conv_fwd(x, w1, None, 1, 1, stats="acc")
-        Cn = z1.shape[-1]
-        rows = z1.numel() // Cn
         y1 = None
-        if info[0] == "acc":
-            # statistics as accumulators: the consumer of a BatchNorm decodes them, no finalize launch
-            bnin1 = BnAccInput(part, rows, bn1, True, relu=True)
-            if fuse:
-                z2, part2, info2 = conv_fwd(z1, w2, None, 1, 1, stats="acc", in_bn=bnin1)
-            else:
-                y1 = bn_apply_acc(z1, bnin1, None, True)
-                z2, part2, info2 = conv_fwd(y1, w2, None, 1, 1, stats="acc")
-            bnin2 = BnAccInput(part2, rows, bn2, True)
-            y = bn_apply_acc(z2, bnin2, x, True)
-            mean1, invstd1, mean2, invstd2 = bnin1.mean, bnin1.invstd, bnin2.mean, bnin2.invstd
+        if fuse:
+            # bn_in_fusable: the bf16x6 mode, where a bias-free 3x3 convolution returns its statistics as an accumulator -
+            # conv2 decodes it (and leaves mean1 / invstd1 for the backward), no finalize launch
+            assert info[0] == "acc", "bn_in_fusable() without accumulator statistics"
+            bnin1 = BnAccInput(part, z1.numel() // z1.shape[-1], bn1, True, relu=True)
+            z2, part2, info2 = conv_fwd(z1, w2, None, 1, 1, stats="acc", in_bn=bnin1)
+            mean1, invstd1 = bnin1.mean, bnin1.invstd
         else:
-            def fin(bn, part, info):
-                track = bn.track_running_stats
-                return bn_finalize(part, info, rows, Cn, bn.eps, 0.1 if bn.momentum is None else bn.momentum,
-                                   bn.running_mean if track else None, bn.running_var if track else None)
-            mean1, invstd1 = fin(bn1, part, info)
-            if fuse:
-                z2, part2, info2 = conv_fwd(z1, w2, None, 1, 1, stats=True, in_bn=(mean1, invstd1, bn1.weight, bn1.bias, True))
-            else:
-                y1 = bn_apply(z1, mean1, invstd1, bn1.weight, bn1.bias, None, True)
-                z2, part2, info2 = conv_fwd(y1, w2, None, 1, 1, stats=True)
-            mean2, invstd2 = fin(bn2, part2, info2)
-            y = bn_apply(z2, mean2, invstd2, bn2.weight, bn2.bias, x, True)
+            y1, mean1, invstd1 = _bn_train(z1, part, info, bn1, None, True, True)
+            z2, part2, info2 = conv_fwd(y1, w2, None, 1, 1, stats="acc")
+        y, mean2, invstd2 = _bn_train(z2, part2, info2, bn2, x, True, True)
         for bn in (bn1, bn2):
             if bn.track_running_stats:
                 _count_batch(bn)

@@ -107,28 +107,19 @@ int buctd_conv3x3_bf16x6_prep(int Ci, int Co, const float* w, int flip, void* wp
 int buctd_conv3x3_bf16x6(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* bias,
                          const float* scale, const float* shift, const float* residual, int relu, float* y,
                          float* stats_partials, int* stats_counts, void* stream);
-/* buctd_conv3x3_bf16x6 with the BatchNorm(+ReLU) of the PRODUCING layer applied to the input while it is staged: x is
- * the producer's raw convolution output z, the kernel convolves relu((z - mean) * (invstd * gamma) + beta) - bitwise
- * what buctd_bn_apply would have written - so the tensor between bn1/relu and conv2 of a BasicBlock
- * (pose_hrnet.py:44-49) never exists in HBM.  in_* are [Ci] arrays. */
-int buctd_conv3x3_bf16x6_bnin(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* bias,
-                              const float* scale, const float* shift, const float* residual, int relu, float* y,
-                              float* stats_partials, int* stats_counts, const float* in_mean, const float* in_invstd,
-                              const float* in_gamma, const float* in_beta, int in_relu, void* stream);
-/* Data gradient of a 3x3 convolution (buctd_conv3x3_bf16x6 on the flip = 1 image; residual = the skip gradient, NULL ok)
- * that also forms the REDUCTION pass of the BatchNorm backward consuming its output g = y: per row group (the groups of
- * buctd_conv3x3_bf16x6_stats_groups(N, H, W, Ci, Co)) s1 = sum m g, s2 = sum m g (z - mean) invstd, with m the ReLU mask of
- * that BatchNorm's forward output (bn_y > 0 where given, else rebuilt from bn_z as (z - mean)(invstd gamma) + beta > 0) -
- * bn_part [groups][2][Co] floats, the input of buctd_bn_bwd_from_partials.  What autograd does with three more passes over
- * g, z and y (the sum reductions of native_batch_norm_backward, pose_hrnet.py:41-57). */
-int buctd_conv3x3_bf16x6_bnstat(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* residual,
-                                float* y, const float* bn_z, const float* bn_y, const float* bn_mean, const float* bn_invstd,
-                                const float* bn_gamma, const float* bn_beta, float* bn_part, void* stream);
 /* The accumulator forms (see "BatchNorm statistics without finalize launches" below).
  * _acc: forward convolution whose output statistics are added to stats_acc (NULL: none) and whose input may be the raw
- * output of the producing convolution, normalised while it is staged with THAT layer's statistics decoded from its
- * accumulator (in_bn != NULL: with in_gamma / in_beta / in_relu; the launch's first tile writes mean / invstd out and updates
- * the running statistics).  _bnstat_acc: buctd_conv3x3_bf16x6_bnstat with the sums added to the accumulator bn_acc. */
+ * output z of the producing convolution, normalised while it is staged with THAT layer's statistics decoded from its
+ * accumulator (in_bn != NULL: with in_gamma / in_beta / in_relu, [Ci] arrays): the kernel convolves
+ * relu((z - mean) * (invstd * gamma) + beta) - bitwise what buctd_bn_apply would have written - so the tensor between
+ * bn1/relu and conv2 of a BasicBlock (pose_hrnet.py:44-49) never exists in HBM.  The launch's first tile writes mean / invstd
+ * out and updates the running statistics.
+ * _bnstat_acc: data gradient of a 3x3 convolution (buctd_conv3x3_bf16x6 on the flip = 1 image; residual = the skip gradient,
+ * NULL ok) that also forms the REDUCTION pass of the BatchNorm backward consuming its output g = y: s1 = sum m g,
+ * s2 = sum m g (z - mean) invstd, with m the ReLU mask of that BatchNorm's forward output (bn_y > 0 where given, else rebuilt
+ * from bn_z as (z - mean)(invstd gamma) + beta > 0), added to the accumulator bn_acc - the input of buctd_bn_bwd_acc.  What
+ * autograd does with three more passes over g, z and y (the sum reductions of native_batch_norm_backward,
+ * pose_hrnet.py:41-57). */
 struct buctd_bn_acc_in_;
 int buctd_conv3x3_bf16x6_acc(int N, int H, int W, int Ci, int Co, const float* x, const void* wprep, const float* residual,
                              int relu, float* y, void* stats_acc, const struct buctd_bn_acc_in_* in_bn, const float* in_gamma,
@@ -216,7 +207,8 @@ int buctd_conv3x3_wgrad_bf16x6_plan(int N, int H, int W, int Ci, int Co, int* ou
 size_t buctd_conv3x3_wgrad_bf16x6_workspace(int N, int H, int W, int Ci, int Co);
 int buctd_conv3x3_wgrad_bf16x6(int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw,
                                int accumulate, void* workspace, size_t workspace_bytes, void* stream);
-/* the weight gradient with the same on-the-fly BatchNorm(+ReLU) of its X operand (x = the producer's raw output) */
+/* the weight gradient with the on-the-fly BatchNorm(+ReLU) of buctd_conv3x3_bf16x6_acc applied to its X operand (x = the
+ * producer's raw output z), from the [Ci] arrays x_mean / x_invstd that forward launch wrote out */
 int buctd_conv3x3_wgrad_bf16x6_bnin(int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw,
                                     int accumulate, const float* x_mean, const float* x_invstd, const float* x_gamma,
                                     const float* x_beta, int x_relu, void* workspace, size_t workspace_bytes,
@@ -297,8 +289,9 @@ size_t buctd_bn_bwd_workspace(long rows, int C);
 int buctd_bn_bwd(const float* dy, const float* y, const float* z, const float* mean, const float* invstd,
                  const float* gamma, const float* beta, int relu, long rows, int C, float* dz, float* dres,
                  float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
-/* The rest of buctd_bn_bwd when the reduction pass already happened (buctd_conv3x3_bf16x6_bnstat): part = [nparts][2][C]
- * partial (s1, s2) sums -> fp64 merge, dgamma / dbeta, then dz (and dres).  workspace: 2 * C floats. */
+/* The rest of buctd_bn_bwd when the reduction pass already happened: part = [nparts][2][C] partial (s1, s2) sums over any
+ * grouping of the rows, from any producer (the sums buctd_bn_bwd's own reduction forms per row range) -> fp64 merge,
+ * dgamma / dbeta, then dz (and dres).  workspace: 2 * C floats. */
 int buctd_bn_bwd_from_partials(const float* dy, const float* y, const float* z, const float* mean, const float* invstd,
                                const float* gamma, const float* beta, int relu, long rows, int C, const float* part,
                                int nparts, float* dz, float* dres, float* dgamma, float* dbeta, int accumulate,

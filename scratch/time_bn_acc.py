@@ -27,7 +27,6 @@ for (N, H, W, Cn) in ((32, 96, 72, 48), (32, 48, 36, 96), (32, 24, 18, 192), (32
     res["fwd partials"] = timeit(lambda: ops.conv_fwd(x, w, None, 1, 1, stats=True))
     res["fwd acc"] = timeit(lambda: ops.conv_fwd(x, w, None, 1, 1, stats="acc"))
     res["finalize"] = timeit(lambda: ops.bn_finalize(part, info, rows, Cn, 1e-5, 0.1, bn.running_mean, bn.running_var))
-    res["fwd bnin arrays + partials"] = timeit(lambda: ops.conv_fwd(z, w, None, 1, 1, stats=True, in_bn=(mean, invstd, bn.weight, bn.bias, True)))
     z1, acc1, _ = ops.conv_fwd(x, w, None, 1, 1, stats="acc")
     bi = ops.BnAccInput(acc1, rows, bn, True)
     res["fwd bnin acc + acc"] = timeit(lambda: ops.conv_fwd(z, w, None, 1, 1, stats="acc", in_bn=bi))

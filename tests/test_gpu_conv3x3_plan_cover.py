@@ -27,10 +27,7 @@ convolution ratios all come from the hard-operands case, random-normal cases sta
   RES|BS_Y      6.28e-07 / 6.80e-07                            1.1e-07 / 9.1e-08    1.2e-07 / 1.1e-07    1.8e-07 / 1.3e-07
   wgrad         3.78e-07 / 7.38e-07
 (every BatchNorm-backward figure is below the 5e-6 floor of its bar).  Wall time of the module: 45-52 s (255 tests; test_gpu_conv3x3_split.py:
-6 s on the same machine - the difference is the twelve model shapes at batch 32 and their fp64 references).
-
-The partial-sum form buctd_conv3x3_bf16x6_bnstat has no caller left in block.hip / ops.py (the block path uses the accumulator
-form only); it is not exercised here."""
+6 s on the same machine - the difference is the twelve model shapes at batch 32 and their fp64 references)."""
 import ctypes as C
 import math
 

@@ -413,10 +413,15 @@ __global__ __launch_bounds__(256) void gaussian_target_kernel(const float* __res
   const long row = blockIdx.x;
   const float jx = joints[row * 3 + 0], jy = joints[row * 3 + 1];
   float wgt = vis[row];
-  const int tmp = (int)(sigma * 3.f);
+  // tmp_size = sigma * 3 stays a float in the reference: with sigma = 1.5 the patch is 10 wide, ul and br are truncated
+  // toward zero one by one, and the patch's centre is its column size // 2 counted from ul - which is mu only while
+  // mu - tmp did not truncate upward (a whole tmp, or ul >= 0)
+  const float tmp = sigma * 3.f;
   // int() truncates toward zero, exactly like the reference
   const int mu_x = (int)(jx / stride_x + 0.5f), mu_y = (int)(jy / stride_y + 0.5f);
-  const int ulx = mu_x - tmp, uly = mu_y - tmp, brx = mu_x + tmp + 1, bry = mu_y + tmp + 1;
+  const int ulx = (int)((float)mu_x - tmp), uly = (int)((float)mu_y - tmp);
+  const int brx = (int)((float)mu_x + tmp + 1.f), bry = (int)((float)mu_y + tmp + 1.f);
+  const float c0 = floorf((2.f * tmp + 1.f) * 0.5f);
   const bool outside = ulx >= Wh || uly >= Hh || brx < 0 || bry < 0;
   if (outside) wgt = 0.f;
   const bool paint = !outside && wgt > 0.5f;
@@ -425,7 +430,7 @@ __global__ __launch_bounds__(256) void gaussian_target_kernel(const float* __res
     const int y = i / Wh, x = i - y * Wh;
     float v = 0.f;
     if (paint && x >= ulx && x < brx && y >= uly && y < bry) {
-      const float dx = (float)(x - mu_x), dy = (float)(y - mu_y);
+      const float dx = (float)(x - ulx) - c0, dy = (float)(y - uly) - c0;
       v = expf(-(dx * dx + dy * dy) * inv2s2);
     }
     target[row * Hh * Wh + i] = v;

@@ -105,7 +105,15 @@ class FlatParams:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) semantics on the flat arena."""
+    """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) semantics on the flat arena.
+
+    One step counter for the whole arena, and every step updates the whole arena: a parameter without a gradient is stepped
+    with a zero gradient.  While its moments are zero that leaves it bit-unchanged (frozen parameters, modules that are
+    constructed but never called, the alignment padding) - the same as torch.optim.Adam, which skips it.  A parameter that
+    gains or loses its gradient in the middle of a run differs from torch: torch counts the steps of each parameter on its
+    own (its bias corrections start at that parameter's first gradient) and leaves a parameter alone whenever its gradient
+    is None, while here the bias corrections follow the arena's counter and the moments of a parameter that lost its
+    gradient keep decaying into it."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None):
         if not isinstance(flat, FlatParams):

@@ -512,3 +512,54 @@ def test_fused_sgd_skips_parameters_without_gradient(dev):
     for (n, p), q in zip(net.named_parameters(), twin.parameters()):
         assert (p.detach() - q.detach().cpu()).abs().max().item() <= 1e-6 * max(1.0, p.abs().max().item()), n
     assert torch.equal(twin.frozen.detach().cpu(), frozen0) and torch.equal(twin.unused.weight.detach().cpu(), unused0)
+
+
+def test_fused_adam_leaves_parameters_without_gradient_alone(dev):
+    """The Adam twin of the test above.  engine.FusedAdam steps the whole arena, a parameter without a gradient with a zero
+    gradient: with zero moments that must leave frozen parameters, constructed-but-unused modules and the arena's alignment
+    padding bit-unchanged over three steps, while every other parameter follows torch.optim.Adam on the CPU.  (A parameter
+    that gains or loses its gradient mid-run would differ from torch's per-parameter step count: FusedAdam's docstring.)"""
+    import copy
+    from buctd_amd import engine
+    torch.manual_seed(6)
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.a = torch.nn.Conv2d(3, 8, 3)
+            self.frozen = torch.nn.Parameter(torch.randn(7, 5), requires_grad=False)
+            self.unused = torch.nn.Linear(6, 3)
+            self.odd = torch.nn.Parameter(torch.randn(9))
+            self.b = torch.nn.Conv2d(8, 4, 1)
+
+    net = Net()
+    twin = copy.deepcopy(net).to(dev)
+    ref = torch.optim.Adam(net.parameters(), lr=1e-3)
+    flat = engine.FlatParams(twin)
+    fused = engine.FusedAdam(flat, lr=1e-3)
+    before = {n: p.detach().clone() for n, p in net.named_parameters()}
+    arena0 = flat.flat.clone()
+    padding = torch.ones(flat.numel, dtype=torch.bool, device=dev)
+    for q in flat.params:
+        s, e = flat.span(q)
+        padding[s:e] = False
+    assert int(padding.sum()) >= 4, "7 x 5, 9 and 3 elements do not fill whole 16-byte pieces"
+    idle = ("frozen", "unused")
+    for it in range(3):
+        ref.zero_grad()
+        fused.zero_grad()
+        for (n, p), q in zip(net.named_parameters(), twin.parameters()):
+            if n.startswith(idle):
+                continue
+            g = torch.randn_like(p)
+            p.grad = g.clone()
+            q.grad = g.to(dev)
+        ref.step()
+        fused.step()
+    for (n, p), q in zip(net.named_parameters(), twin.parameters()):
+        if n.startswith(idle):
+            assert torch.equal(q.detach().cpu(), before[n]) and torch.equal(p.detach(), before[n]), n
+        else:
+            assert not torch.equal(p.detach(), before[n]), n
+            assert (p.detach() - q.detach().cpu()).abs().max().item() <= 1e-6 * max(1.0, p.abs().max().item()), n
+    assert torch.equal(flat.flat[padding], arena0[padding]) and not fused.exp_avg[padding].any(), "the alignment padding moved"

@@ -229,6 +229,7 @@ SIGNATURES = {
     "buctd_scale": (_I, [_P, _P, _F, _P, _L, _P]),
     "buctd_copy_channels": (_I, [_P, _L, _I, _I, _P, _I, _I, _I, _P]),
     "buctd_add_bcast": (_I, [_P, _P, _P, _L, _L, _P]),
+    "buctd_batch_sum": (_I, [_P, _L, _L, _P, _I, _P]),
     "buctd_relu_bwd": (_I, [_P, _P, _P, _L, _P]),
     "buctd_colsum_workspace": (_SZ, [_L, _I]),
     "buctd_colsum": (_I, [_P, _L, _I, _P, _I, _P, _SZ, _P]),

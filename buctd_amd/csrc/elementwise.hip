@@ -108,6 +108,43 @@ extern "C" int buctd_add_bcast(const float* a, const float* v, float* out, long 
   return BUCTD_OK;
 }
 
+// out[i] (+)= sum_b x[b][i]  (gradient of a learnable position embedding: the transpose of add_bcast).  A thread owns its
+// outputs and adds the rows in ascending b - out first when accumulating - so the bits depend neither on the grid nor on
+// V (f32x4 lanes are independent sums).  BS_ROWS independent row loads are in flight per thread; x is read once.
+#define BS_ROWS 8
+template <typename V>
+__global__ __launch_bounds__(256) void batch_sum_kernel(const V* __restrict__ x, long batch, long n, V* __restrict__ out,
+                                                        int accumulate) {
+  const long step = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
+    V s = V{};
+    if (accumulate) s = out[i];
+    const V* p = x + i;
+    long b = 0;
+    for (; b + BS_ROWS <= batch; b += BS_ROWS) {
+      V r[BS_ROWS];
+#pragma unroll
+      for (int k = 0; k < BS_ROWS; ++k) r[k] = p[(b + k) * n];
+#pragma unroll
+      for (int k = 0; k < BS_ROWS; ++k) s += r[k];
+    }
+    for (; b < batch; ++b) s += p[b * n];
+    out[i] = s;
+  }
+}
+extern "C" int buctd_batch_sum(const float* x, long batch, long n, float* out, int accumulate, void* stream) {
+  BUCTD_CHECK_ARG(x && out && batch > 0 && n > 0, "buctd_batch_sum: bad argument");
+  // rows start at multiples of n floats: 16-byte loads need n % 4 == 0 besides the aligned bases
+  if (n % 4 == 0 && ((uintptr_t)x | (uintptr_t)out) % 16 == 0)
+    hipLaunchKernelGGL(batch_sum_kernel<f32x4>, dim3(stream_grid(n / 4)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const f32x4*>(x), batch, n / 4, reinterpret_cast<f32x4*>(out), accumulate);
+  else
+    hipLaunchKernelGGL(batch_sum_kernel<float>, dim3(stream_grid(n)), dim3(256), 0, (hipStream_t)stream, x, batch, n, out,
+                       accumulate);
+  BUCTD_CHECK_LAUNCH("buctd_batch_sum");
+  return BUCTD_OK;
+}
+
 extern "C" int buctd_add(const float* a, const float* b, float* out, long n, int relu, void* stream) {
   BUCTD_CHECK_ARG(a && out && n > 0, "buctd_add: bad argument");
   hipLaunchKernelGGL(add_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, relu);

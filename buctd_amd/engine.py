@@ -89,8 +89,8 @@ class FlatParams:
     def grad_runs(self):
         """Contiguous [start, end) element runs of the arena that cover exactly the parameters holding a gradient right now
         (p.grad is not None) - torch.optim skips every other parameter entirely (no weight decay, no momentum), e.g.
-        TransPose's frozen pos_embedding (transpose_h.py:129) and constructed-but-unused modules.  One run when every
-        parameter has a gradient (the usual case)."""
+        TransPose's frozen sine pos_embedding (transpose_h.py:129; a learnable one has a gradient like any weight) and
+        constructed-but-unused modules.  One run when every parameter has a gradient (the usual case)."""
         runs = []
         for p in self.params:
             if p.grad is None:

@@ -1,6 +1,6 @@
 """BUCTD-TransPose-H on the MI355X engine - drop-in for reference lib/models/transpose_h.py
 (TransformerEncoder 110-150, TransformerEncoderLayer 168-243, TransPoseH 419-714): HRNet stages 1-3 -> 1x1 reduce
--> (+16 condition channels) -> post-norm Transformer encoder with a sine position embedding -> 1x1 head.
+-> (+16 condition channels) -> post-norm Transformer encoder with a sine, learnable or no position embedding -> 1x1 head.
 Same constructor, state_dict keys (incl. self_attn.in_proj_weight / out_proj) and init; tokens are kept
 batch-major [B, T, d] (the flattened NHWC tensor) instead of the reference's [T, B, d] - same math, no transposes.
 Attention maps (return_atten_map, and TransPoseH.attention_maps for the dependency areas of chosen tokens) come from
@@ -83,7 +83,7 @@ class TransformerEncoderLayer(nn.Module):
 
     def forward(self, src, pos=None, rows=None):
         """return_atten_map: -> (src, att_map [B, R, T]) with the rows of the query tokens `rows` (None: [B, T, T])"""
-        qin = src if pos is None else ops_seq.AddPos.apply(src, pos)
+        qin = src if pos is None else ops_seq.add_pos(src, pos)
         att_map = None
         if self.return_atten_map:
             src2, att_map = self.self_attn(qin, src, rows=rows, need_map=True)
@@ -114,6 +114,7 @@ class TransformerEncoder(nn.Module):
     def forward(self, src, pos=None, rows=None):
         """return_atten_map: -> (out, maps [layers, B, R, T]); rows=None is the reference's [layers, B, T, T]"""
         maps = []
+        ops_seq.AddPos.begin(pos)       # a learnable embedding counts its uses per forward pass (once-per-backward gradient)
         for layer in self.layers:
             if self.return_atten_map:
                 # as in the reference, the layers are built with the flag too and return (src, att_map)

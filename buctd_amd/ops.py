@@ -352,9 +352,10 @@ _grad_arena = None
 
 
 def set_grad_arena(arena):
-    """arena(param) -> preallocated grad view (or None). Installed by engine.FlatParams."""
+    """arena(param) -> preallocated grad view (or None). Installed by engine.FlatParams.  Returns the arena it replaces."""
     global _grad_arena
-    _grad_arena = arena
+    old, _grad_arena = _grad_arena, arena
+    return old
 
 
 _grad_ready_cb = None
@@ -362,9 +363,11 @@ _grad_ready_cb = None
 
 def set_grad_ready_callback(cb):
     """cb(param) is invoked right after the kernels that finalise param.grad were enqueued
-    (engine.DataParallel uses it to start the bucket's all-reduce while backward continues)."""
+    (engine.DataParallel uses it to start the bucket's all-reduce while backward continues).  Returns the callback it
+    replaces."""
     global _grad_ready_cb
-    _grad_ready_cb = cb
+    old, _grad_ready_cb = _grad_ready_cb, cb
+    return old
 
 
 def grad_done(*params):

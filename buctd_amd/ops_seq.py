@@ -49,18 +49,83 @@ class ConcatChannels(torch.autograd.Function):
         return da, db
 
 
+def batch_sum(x, out, accumulate):
+    """out (+)= x summed over its leading (batch) dimension, rows added in ascending order"""
+    n = out.numel()
+    check(lib().buctd_batch_sum(ptr(x), x.numel() // n, n, ptr(out), int(accumulate), stream_ptr()), "batch_sum")
+
+
+class _PosUses:
+    """The AddPos nodes of one forward pass that owe a trainable embedding a gradient piece."""
+
+    def __init__(self):
+        self.nodes = 0      # AddPos nodes of the pass
+        self.done = 0       # ... that have added their piece in the backward under way
+
+
 class AddPos(torch.autograd.Function):
-    """tokens [B,T,d] + pos [T,d] (sine embedding: a constant, no gradient - transpose_h.py:507-511)."""
+    """tokens [B,T,d] + pos (T*d values: [T,d] or the reference's [T,1,d] parameter, transpose_h.py:494-511).
+
+    The sine embedding is a constant and takes no gradient.  A learnable one (`pos` is the parameter itself, or a view of
+    it) is added in every encoder layer, so its gradient is a sum over layers and images.  It goes through the
+    parameter-gradient sink like every other one: each node's backward adds its batch sum to ops.grad_target(param) - the
+    first piece of a backward overwrites or accumulates as grad_target says, the later ones accumulate - and the node that
+    adds the last piece of its forward pass (layer 0's: backward runs the layers in reverse) calls ops.grad_done(param),
+    once.  The pieces are counted per forward pass: forward() joins the parameter's open count when it will need the
+    gradient (add_pos() keeps no_grad forwards out), begin() (the encoder's forward) and the first backward of a pass
+    close it, so a forward that is never backpropagated leaves nothing behind.  A further backward through a retained graph
+    adds and reports again; one backward through two forward passes of the same parameter reports it twice.
+    engine.DataParallel answers both like any second write to a counted gradient."""
+
+    @staticmethod
+    def begin(pos):
+        """a new forward pass starts: the AddPos nodes that follow are counted on their own"""
+        if pos is not None and pos.requires_grad:
+            _pos_param(pos)._pos_uses = None
 
     @staticmethod
     def forward(ctx, x, pos):
+        ctx.uses = None
+        if ctx.needs_input_grad[1]:
+            param = _pos_param(pos)
+            if not (param.is_leaf and param.is_contiguous() and param.numel() == pos.numel()
+                    and param.data_ptr() == pos.data_ptr() and pos.is_contiguous()):
+                raise ValueError("AddPos: a trainable position embedding is the parameter itself or a contiguous view of "
+                                 "all of it")
+            uses = getattr(param, "_pos_uses", None)
+            if uses is None:
+                uses = param._pos_uses = _PosUses()
+            uses.nodes += 1
+            ctx.param, ctx.uses = param, uses
         return add_bcast(x, pos)
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError("learnable position embeddings are not used by any BUCTD recipe")
+        uses = ctx.uses
+        if uses is None:
+            return dy, None
+        param = ctx.param
+        if getattr(param, "_pos_uses", None) is uses:
+            param._pos_uses = None              # this pass is being backpropagated: the next forward counts anew
+        g, acc = ops.grad_target(param)
+        batch_sum(dy.contiguous(), g, acc)
+        uses.done += 1
+        if uses.done == uses.nodes:
+            uses.done = 0                       # a second backward through a retained graph is counted, and reported, again
+            ops.grad_done(param)
         return dy, None
+
+
+def _pos_param(pos):
+    return pos if pos._base is None else pos._base
+
+
+def add_pos(x, pos):
+    """AddPos as the modules call it: under no_grad a trainable embedding is a constant (a Function's forward cannot tell,
+    it always runs with gradients off) and is not counted"""
+    if pos.requires_grad and not torch.is_grad_enabled():
+        pos = pos.detach()
+    return AddPos.apply(x, pos)
 
 
 class Dropout(torch.autograd.Function):

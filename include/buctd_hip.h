@@ -368,6 +368,10 @@ int buctd_copy_channels(const float* src, long rows, int Cs, int cs0, float* dst
                         void* stream);
 /* out[b][i] = a[b][i] + v[i]: position embedding added to each image's tokens (transpose_h.py:189-192) */
 int buctd_add_bcast(const float* a, const float* v, float* out, long batch, long n, void* stream);
+/* out[i] (+)= sum over b of x[b*n + i], b ascending; accumulate != 0 adds to what out holds (out first, then
+ * b = 0..batch-1): gradient of a learnable position embedding.  One thread per output, no atomics: bit-reproducible,
+ * and the 16-byte path (n % 4 == 0, aligned pointers) returns the bits of the scalar one.  x and out must not overlap. */
+int buctd_batch_sum(const float* x, long batch, long n, float* out, int accumulate, void* stream);
 /* dx = dy * (y > 0) */
 int buctd_relu_bwd(const float* dy, const float* y, float* dx, long n, void* stream);
 /* column sums of [rows][C] (bias gradients); db overwritten or accumulated */

@@ -131,6 +131,10 @@ VIS_POSE_PLAIN, VIS_POSE_PRETTY = 0, 1
 VIS_POSE_TILE_W, VIS_POSE_TILE_H, VIS_POSE_CHUNK = 64, 16, 256
 
 
+# BUCTD_GRAD_SUMSQ_CHUNK of the header: elements per partial sum of buctd_grad_sumsq
+GRAD_SUMSQ_CHUNK = 8192
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -153,6 +157,7 @@ _SZ = C.c_size_t
 _PD = C.POINTER(ConvDesc)
 _PM = C.POINTER(MatmulDesc)
 _PI = C.POINTER(C.c_int)
+_PL = C.POINTER(C.c_long)
 
 # name -> (restype, argtypes); mirrors include/buctd_hip.h one to one
 SIGNATURES = {
@@ -320,6 +325,13 @@ SIGNATURES = {
     "buctd_flipback_avg": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "buctd_sgd_step": (_I, [_P, _P, _P, _L, _F, _F, _F, _I, _I, _F, _P]),
     "buctd_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
+    "buctd_sgd_step_dscale": (_I, [_P, _P, _P, _L, _F, _F, _F, _I, _I, _F, _P, _P]),
+    "buctd_adam_step_dscale": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P]),
+    # gradient-norm clipping (csrc/grad_norm.hip); runs: a host array of longs, spans: a device one
+    "buctd_grad_sumsq_workspace": (_SZ, [_PL, _I]),
+    "buctd_grad_sumsq": (_I, [_P, _PL, _I, _P, _P, _SZ, _P]),
+    "buctd_grad_clip_coef": (_I, [_P, _D, _D, _P, _P, _P]),
+    "buctd_grad_segment_stats": (_I, [_P, _P, _I, _P, _P, _P]),
     # bf16 inference mode (csrc/conv_bf16.hip)
     "buctd_bf16_pack_conv": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     "buctd_bf16_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _SZ, _P]),

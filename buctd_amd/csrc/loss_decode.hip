@@ -618,10 +618,14 @@ extern "C" int buctd_flipback_avg(const float* a, const float* b, const int32_t*
 }
 
 // --------------------------------------------------------------------- adam ----
+// DSCALE: the _dscale entry - gscale is multiplied by the clip coefficient read from device memory (one wave-uniform load at
+// kernel start); everything behind that line is the plain step's code, so *coef == 1.0f returns its bits.
+template <bool DSCALE>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n, float lr,
                                                    float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                   float gscale) {
+                                                   float gscale, const float* __restrict__ coef) {
+  if (DSCALE) gscale = gscale * coef[0];
   // torch.optim.Adam (no amsgrad, no weight decay):
   //   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
   const float step_size = lr / bc1;
@@ -652,25 +656,38 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[i] -= step_size * (mm / (sqrtf(vv) / bc2_sqrt + eps));
   }
 }
-extern "C" int buctd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
-                               float beta2, float eps, int step, float gscale, void* stream) {
-  BUCTD_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "buctd_adam_step: bad argument");
+template <bool DSCALE>
+static int adam_launch(const char* who, float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
+                       float beta2, float eps, int step, float gscale, const float* coef, void* stream) {
+  BUCTD_CHECK_ARG(p && g && m && v && n > 0 && step >= 1 && (!DSCALE || coef), "%s: bad argument", who);
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   long blocks = ((n + 3) / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, (float)bc1, (float)sqrt(bc2), gscale);
-  BUCTD_CHECK_LAUNCH("buctd_adam_step");
+  hipLaunchKernelGGL(adam_kernel<DSCALE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
+                     beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), gscale, coef);
+  BUCTD_CHECK_LAUNCH(who);
   return BUCTD_OK;
+}
+extern "C" int buctd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
+                               float beta2, float eps, int step, float gscale, void* stream) {
+  return adam_launch<false>("buctd_adam_step", p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, nullptr, stream);
+}
+extern "C" int buctd_adam_step_dscale(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
+                                      float beta2, float eps, int step, float gscale, const float* coef, void* stream) {
+  return adam_launch<true>("buctd_adam_step_dscale", p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, coef, stream);
 }
 
 // ---------------------------------------------------------------------- sgd ----
 // torch.optim.SGD(lr, momentum, dampening = 0, weight_decay, nesterov) on the flat arena - the 'sgd' branch of the
 // reference's get_optimizer (lib/utils/utils.py:260-267):
 //   g += wd p ;  buf = g (first step) | mu buf + g ;  g = nesterov ? g + mu buf : buf ;  p -= lr g        (mu = 0: no buffer)
+// DSCALE: as in adam_kernel - the clipped gradient is g * (gscale * *coef), formed before the weight-decay term
+template <bool DSCALE>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  long n, float lr, float mu, float wd, int nesterov, int first, float gscale) {
+                                                  long n, float lr, float mu, float wd, int nesterov, int first, float gscale,
+                                                  const float* __restrict__ coef) {
+  if (DSCALE) gscale = gscale * coef[0];
   const long step = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
     float pp = p[i];
@@ -683,13 +700,25 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     p[i] = pp - lr * gg;
   }
 }
-extern "C" int buctd_sgd_step(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
-                              float weight_decay, int nesterov, int first_step, float gscale, void* stream) {
-  BUCTD_CHECK_ARG(p && g && n > 0 && (momentum == 0.f || momentum_buf), "buctd_sgd_step: bad argument");
+template <bool DSCALE>
+static int sgd_launch(const char* who, float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
+                      float weight_decay, int nesterov, int first_step, float gscale, const float* coef, void* stream) {
+  BUCTD_CHECK_ARG(p && g && n > 0 && (momentum == 0.f || momentum_buf) && (!DSCALE || coef), "%s: bad argument", who);
   long blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, n, lr,
-                     momentum, weight_decay, nesterov, first_step, gscale);
-  BUCTD_CHECK_LAUNCH("buctd_sgd_step");
+  hipLaunchKernelGGL(sgd_kernel<DSCALE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, n,
+                     lr, momentum, weight_decay, nesterov, first_step, gscale, coef);
+  BUCTD_CHECK_LAUNCH(who);
   return BUCTD_OK;
+}
+extern "C" int buctd_sgd_step(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
+                              float weight_decay, int nesterov, int first_step, float gscale, void* stream) {
+  return sgd_launch<false>("buctd_sgd_step", p, g, momentum_buf, n, lr, momentum, weight_decay, nesterov, first_step, gscale,
+                           nullptr, stream);
+}
+extern "C" int buctd_sgd_step_dscale(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
+                                     float weight_decay, int nesterov, int first_step, float gscale, const float* coef,
+                                     void* stream) {
+  return sgd_launch<true>("buctd_sgd_step_dscale", p, g, momentum_buf, n, lr, momentum, weight_decay, nesterov, first_step,
+                          gscale, coef, stream);
 }

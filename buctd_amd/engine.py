@@ -13,6 +13,7 @@ checkpoint sees (broadcast_buffers()).
 """
 import os
 import time
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -55,6 +56,9 @@ class FlatParams:
             p.data = v
             self._gviews[id(p)] = self._view(self.grad, p)
         self.ready_cb = None
+        self.optimizer = None      # weak reference to the FusedAdam / FusedSGD that steps this arena (clip_grad_norm_ asks it)
+        self._clip = None          # device state of the norm clip (_GradClip), made on first use
+        self._span_table = None    # int64 [P, 2] device table of the parameters' spans (grad_stats)
         ops.set_grad_arena(self)
 
     def _view(self, buf, p):
@@ -104,7 +108,76 @@ class FlatParams:
         return [(s, e) for s, e in runs]
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _GradClip:
+    """Device state of the gradient-norm clip of one arena: the fp64 sum of squares, the fp32 coefficient and norm, and the
+    reduction's workspace.  measure() enqueues the reduction (buctd_grad_sumsq over the arena's gradient runs) and the
+    finalize step (buctd_grad_clip_coef); nothing comes back to the host."""
+
+    def __init__(self, flat):
+        dev = flat.flat.device
+        self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.coef = torch.ones(1, dtype=torch.float32, device=dev)
+        self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.workspace = None
+
+    def measure(self, flat, gscale, max_norm):
+        runs = flat.grad_runs()
+        if runs:
+            need = ops.grad_sumsq_workspace(runs) // 8
+            if self.workspace is None or self.workspace.numel() < need:
+                self.workspace = torch.empty(need, dtype=torch.float64, device=self.sumsq.device)
+            ops.grad_sumsq(flat.grad, runs, self.sumsq, self.workspace)
+        else:
+            self.sumsq.zero_()         # no parameter holds a gradient: torch's norm of nothing is 0
+        ops.grad_clip_coef(self.sumsq, gscale, max_norm, self.coef, self.norm)
+        return runs
+
+
+def _arena_clip(flat):
+    if flat._clip is None:
+        flat._clip = _GradClip(flat)
+    return flat._clip
+
+
+class _NormClipOption:
+    """max_grad_norm of FusedAdam / FusedSGD: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) folded into step().
+    None / 0 is off (the plain step kernels, nothing else runs).  With a value, step() reduces the squared gradient of the
+    arena's gradient runs after collect() and grad_sync() - so under engine.DataParallel the norm is that of the averaged
+    gradient, what one process over the whole batch would clip - keeps norm and coefficient on the device, and the step
+    kernel multiplies the gradient by gscale * coef as it reads it.  An attribute, not optimizer state: state_dict() does
+    not carry it."""
+
+    def _init_clip(self, flat, max_grad_norm):
+        self.max_grad_norm = max_grad_norm
+        self._last_clip = False
+        flat.optimizer = weakref.ref(self)
+
+    def _clip_coef(self, gscale):
+        """-> the device coefficient for this step's kernels, or None when the option is off"""
+        m = self.max_grad_norm
+        if m is None or m == 0:
+            self._last_clip = False
+            return None
+        if not m > 0:
+            raise ValueError(f"max_grad_norm must be positive (or None / 0 for no clipping), got {m!r}")
+        clip = _arena_clip(self.flat)
+        clip.measure(self.flat, gscale, float(m))
+        self._last_clip = True
+        return clip.coef
+
+    @property
+    def last_grad_norm(self):
+        """norm of the (averaged) gradient before the clip, as the last clipped step() measured it: a 0-d fp32 device tensor,
+        overwritten by the next clipped step (clone it to keep it); None when the last step did not clip"""
+        return self.flat._clip.norm.view(()) if self._last_clip else None
+
+    @property
+    def last_clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)) of the last clipped step(): 0-d fp32 device tensor, or None"""
+        return self.flat._clip.coef.view(()) if self._last_clip else None
+
+
+class FusedAdam(_NormClipOption, torch.optim.Optimizer):
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) semantics on the flat arena.
 
     One step counter for the whole arena, and every step updates the whole arena: a parameter without a gradient is stepped
@@ -115,11 +188,12 @@ class FusedAdam(torch.optim.Optimizer):
     is None, while here the bias corrections follow the arena's counter and the moments of a parameter that lost its
     gradient keep decaying into it."""
 
-    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None):
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None, max_grad_norm=None):
         if not isinstance(flat, FlatParams):
             raise TypeError("FusedAdam works on an engine.FlatParams arena")
         super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps))
         self.flat = flat
+        self._init_clip(flat, max_grad_norm)       # the gradient-norm clip folded into step(): _NormClipOption
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self.step_count = 0
@@ -131,10 +205,11 @@ class FusedAdam(torch.optim.Optimizer):
             raise NotImplementedError("closures are not used on the BUCTD path")
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
+        coef = self._clip_coef(gscale)
         self.step_count += 1
         g = self.param_groups[0]
         ops.adam_step(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
-                      g["betas"][1], g["eps"], self.step_count, gscale)
+                      g["betas"][1], g["eps"], self.step_count, gscale, coef)
         ops.weights_updated()  # the kernel wrote the parameters through raw pointers: prepared filter images are stale
         ops.refresh_prepared(self.flat.flat.device)   # ... and are rebuilt here, by one launch behind the Adam kernel
         if self.flat.flat.is_cuda:
@@ -200,11 +275,11 @@ class FusedAdam(torch.optim.Optimizer):
                 g[k] = v
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_NormClipOption, torch.optim.Optimizer):
     """torch.optim.SGD(lr, momentum, weight_decay, nesterov) semantics on the flat arena (one kernel per step) - the 'sgd'
     branch of the reference's get_optimizer (lib/utils/utils.py:260-267).  Reads and writes torch.optim.SGD state_dicts."""
 
-    def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None):
+    def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None, max_grad_norm=None):
         if not isinstance(flat, FlatParams):
             raise TypeError("FusedSGD works on an engine.FlatParams arena")
         if nesterov and momentum <= 0:
@@ -215,6 +290,7 @@ class FusedSGD(torch.optim.Optimizer):
         self.buf = torch.zeros_like(flat.flat) if momentum else None
         self.step_count = 0
         self.grad_sync = grad_sync
+        self._init_clip(flat, max_grad_norm)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -222,13 +298,14 @@ class FusedSGD(torch.optim.Optimizer):
             raise NotImplementedError("closures are not used on the BUCTD path")
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
+        coef = self._clip_coef(gscale)
         g = self.param_groups[0]
         # torch.optim.SGD touches only parameters that hold a gradient: a parameter with p.grad None keeps its value (no
         # weight decay) and its momentum buffer.  A zero momentum buffer makes "buf = momentum * buf + g" the first-step
         # initialisation "buf = g" (dampening 0), so parameters that join later need no flag of their own.
         for s, e in self.flat.grad_runs():
             ops.sgd_step(self.flat.flat[s:e], self.flat.grad[s:e], None if self.buf is None else self.buf[s:e], g["lr"],
-                         g["momentum"], g["weight_decay"], g["nesterov"], False, gscale)
+                         g["momentum"], g["weight_decay"], g["nesterov"], False, gscale, coef)
         self.step_count += 1
         ops.weights_updated()
         ops.refresh_prepared(self.flat.flat.device)
@@ -502,19 +579,72 @@ class DataParallel(torch.nn.Module):
     # (checkpoints carry the reference's 'module.' prefix through nn.Module's own state_dict: the wrapped net is `self.module`)
 
 
-def get_optimizer(cfg, model):
+def get_optimizer(cfg, model, max_grad_norm=None):
     """reference lib/utils/utils.py:258-274: SGD(lr, MOMENTUM, WD, NESTEROV) for 'sgd', Adam(lr) for 'adam' - here the fused
-    flat-arena optimizers, wired to the data-parallel gradient exchange when `model` is an engine.DataParallel."""
+    flat-arena optimizers, wired to the data-parallel gradient exchange when `model` is an engine.DataParallel.
+    max_grad_norm (or, when it is None, cfg.TRAIN.CLIP_GRAD_NORM where a configuration carries that key; 0 = off) switches
+    on the gradient-norm clip inside step() - the reference's loop calls clip_grad_norm(model.parameters(), args.clip)
+    between backward() and step() (lib/core/train.py:138-141)."""
+    if max_grad_norm is None:
+        max_grad_norm = getattr(cfg.TRAIN, "CLIP_GRAD_NORM", 0.0)
     if isinstance(model, DataParallel):
         flat, sync = model.flatten(), model.sync_gradients
     else:
         flat, sync = FlatParams(model), None
     if cfg.TRAIN.OPTIMIZER == "sgd":
         return FusedSGD(flat, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM, weight_decay=cfg.TRAIN.WD,
-                        nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync)
+                        nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync, max_grad_norm=max_grad_norm)
     if cfg.TRAIN.OPTIMIZER == "adam":
-        return FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync)
+        return FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, max_grad_norm=max_grad_norm)
     return None       # the reference returns None for any other name (utils.py:259, 274)
+
+
+def _arena_of(target):
+    if isinstance(target, FlatParams):
+        return target
+    flat = getattr(target, "flat", None)           # FusedAdam / FusedSGD, a flattened engine.DataParallel
+    if isinstance(flat, FlatParams):
+        return flat
+    raise TypeError("expected an engine.FlatParams arena (or the optimizer / DataParallel that owns one)")
+
+
+@torch.no_grad()
+def clip_grad_norm_(flat, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite False) on the arena, for loops
+    that clip between backward() and step() like the reference's (lib/core/train.py:138-141), on one device: one reduction
+    over the gradient runs, the coefficient formed on the device, the runs scaled in place by it.  Returns the norm before
+    the clip as a 0-d fp32 device tensor; nothing is read back.  Under a gradient exchange (an optimizer with a grad_sync)
+    this point of the loop is BEFORE the exchange - the local gradient, not the averaged one, would be clipped - so it
+    refuses: use the optimizer's max_grad_norm, which clips behind the exchange."""
+    flat = _arena_of(flat)
+    opt = flat.optimizer() if flat.optimizer is not None else None
+    if opt is not None and opt.grad_sync is not None:
+        raise RuntimeError("engine.clip_grad_norm_: this arena's optimizer exchanges gradients in step() (grad_sync); "
+                           "clipping here would act on the gradient before the exchange - set max_grad_norm on the "
+                           "optimizer (FusedAdam / FusedSGD / get_optimizer(..., max_grad_norm=...)) instead")
+    if not float(max_norm) > 0:
+        raise ValueError(f"max_norm must be positive, got {max_norm!r}")
+    flat.collect()
+    clip = _arena_clip(flat)
+    for s, e in clip.measure(flat, 1.0, float(max_norm)):
+        ops.scale(flat.grad[s:e], clip.coef, 1.0, out=flat.grad[s:e])
+    return clip.norm.view(()).clone()
+
+
+@torch.no_grad()
+def grad_stats(flat):
+    """{'abs_mean': [P], 'norm': [P]}: mean |grad| and ||grad||_2 of every parameter of the arena, float64 device tensors in
+    flat.params order, from one launch (buctd_grad_segment_stats) - what the reference's get_network_grad_flow
+    (lib/utils/utils.py:293-300) reads parameter by parameter.  The arena is collect()ed first, so a trainable parameter
+    without a gradient reports zeros; a frozen one reports whatever its slot holds."""
+    flat = _arena_of(flat)
+    flat.collect()
+    if flat._span_table is None:
+        flat._span_table = torch.tensor([flat.span(p) for p in flat.params], dtype=torch.int64).to(flat.grad.device)
+    P = len(flat.params)
+    out = torch.empty(2, P, dtype=torch.float64, device=flat.grad.device)
+    ops.grad_segment_stats(flat.grad, flat._span_table, out[0], out[1])
+    return {"abs_mean": out[0], "norm": out[1]}
 
 
 # Stream-capture error mode of the two graph classes: "thread_local" - a DataLoader's pin-memory thread (hipHostMalloc) or any

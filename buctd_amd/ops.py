@@ -1495,14 +1495,64 @@ def flipback_avg(a, b, perm, shift):
     return out
 
 
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale=1.0):
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale=1.0, coef=None):
+    """coef: a one-element fp32 device tensor (grad_clip_coef) that multiplies the gradient with gscale, read by the kernel"""
+    if coef is not None:
+        check(lib().buctd_adam_step_dscale(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, gscale,
+                                           ptr(coef), stream_ptr()), "adam_step_dscale")
+        return
     check(lib().buctd_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, gscale,
                                 stream_ptr()), "adam_step")
 
 
-def sgd_step(p, g, buf, lr, momentum, weight_decay, nesterov, first, gscale=1.0):
+def sgd_step(p, g, buf, lr, momentum, weight_decay, nesterov, first, gscale=1.0, coef=None):
+    if coef is not None:
+        check(lib().buctd_sgd_step_dscale(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay,
+                                          int(bool(nesterov)), int(bool(first)), gscale, ptr(coef), stream_ptr()),
+              "sgd_step_dscale")
+        return
     check(lib().buctd_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay, int(bool(nesterov)),
                                int(bool(first)), gscale, stream_ptr()), "sgd_step")
+
+
+# ---- gradient-norm clipping (csrc/grad_norm.hip) ---------------------------------------------------------------------------
+def _runs_array(runs):
+    flat = [int(v) for r in runs for v in r]
+    return (C.c_long * len(flat))(*flat), len(flat) // 2
+
+
+def grad_sumsq_workspace(runs):
+    """bytes of workspace buctd_grad_sumsq needs for these [start, end) runs (8 per chunk of _C.GRAD_SUMSQ_CHUNK elements)"""
+    arr, n = _runs_array(runs)
+    return int(lib().buctd_grad_sumsq_workspace(arr, n)) if n else 0
+
+
+def grad_sumsq(g, runs, out, workspace):
+    """out[0] (float64, device) = sum of g[i]^2 over the runs of the fp32 buffer g; workspace: a float64 device tensor"""
+    arr, n = _runs_array(runs)
+    if g.dtype != torch.float32 or out.dtype != torch.float64 or workspace.dtype != torch.float64:
+        raise _C.BuctdHipError("grad_sumsq: g is fp32, out and workspace are float64")
+    if n == 0 or any(s < 0 or e <= s or e > g.numel() for s, e in runs):
+        raise _C.BuctdHipError("grad_sumsq: runs must be non-empty [start, end) ranges inside g")
+    check(lib().buctd_grad_sumsq(ptr(g), arr, n, ptr(out), ptr(workspace), workspace.numel() * 8, stream_ptr()), "grad_sumsq")
+    return out
+
+
+def grad_clip_coef(sumsq, gscale, max_norm, coef, total_norm):
+    """coef[0], total_norm[0] (fp32, device) from sumsq[0] (float64, device): torch's clip_grad_norm_ expressions in fp64"""
+    if sumsq.dtype != torch.float64 or coef.dtype != torch.float32 or total_norm.dtype != torch.float32:
+        raise _C.BuctdHipError("grad_clip_coef: sumsq is float64, coef and total_norm are fp32")
+    check(lib().buctd_grad_clip_coef(ptr(sumsq), float(gscale), float(max_norm), ptr(coef), ptr(total_norm), stream_ptr()),
+          "grad_clip_coef")
+
+
+def grad_segment_stats(g, spans, abs_mean, norm):
+    """abs_mean[s], norm[s] (float64 [P], device) of the segments spans[s] = (start, end) (int64 [P, 2], device) of g"""
+    P = spans.shape[0]
+    if (g.dtype != torch.float32 or spans.dtype != torch.int64 or not spans.is_contiguous() or spans.shape != (P, 2)
+            or abs_mean.dtype != torch.float64 or norm.dtype != torch.float64 or abs_mean.numel() != P or norm.numel() != P):
+        raise _C.BuctdHipError("grad_segment_stats: g fp32, spans int64 [P, 2], abs_mean and norm float64 [P]")
+    check(lib().buctd_grad_segment_stats(ptr(g), ptr(spans), P, ptr(abs_mean), ptr(norm), stream_ptr()), "grad_segment_stats")
 
 
 def layernorm_fwd(x, gamma, beta, eps):

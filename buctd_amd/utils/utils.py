@@ -1,6 +1,6 @@
 """Boundary helpers of the training driver - drop-in for the pieces of reference lib/utils/utils.py the path
-uses: get_optimizer (258-274), save_checkpoint (303-308), create_logger (220-255, without the dataset-specific
-directory logic that needs the external data tree)."""
+uses: get_optimizer (258-274), get_network_grad_flow (293-300), save_checkpoint (303-308), create_logger (220-255, without
+the dataset-specific directory logic that needs the external data tree)."""
 import logging
 import os
 import time
@@ -8,6 +8,25 @@ import time
 import torch
 
 from ..engine import get_optimizer  # noqa: F401  (same name / signature as the reference helper)
+
+
+def get_network_grad_flow(model):
+    """Sum over the trainable parameters of mean |grad|, a Python float (reference lib/utils/utils.py:293-300).  When the
+    model's parameters live in an engine.FlatParams arena the per-parameter means come from one launch over the gradient
+    arena (engine.grad_stats) and one read-back; otherwise the reference's loop runs as it stands."""
+    from .. import engine, ops
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    flat = getattr(model, "flat", None)
+    if not isinstance(flat, engine.FlatParams):
+        flat = ops._grad_arena if isinstance(ops._grad_arena, engine.FlatParams) else None
+    if flat is not None and flat.grad.is_cuda and params and all(flat.owns(p) for p in params):
+        index = {id(p): i for i, p in enumerate(flat.params)}
+        rows = torch.tensor([index[id(p)] for p in params], device=flat.grad.device)
+        return float(engine.grad_stats(flat)["abs_mean"][rows].sum().item())
+    total_avg_gradient = 0.0
+    for p in params:
+        total_avg_gradient += p.grad.abs().mean().item()
+    return total_avg_gradient
 
 
 def save_checkpoint(states, is_best, output_dir, filename='checkpoint.pth'):

@@ -643,6 +643,39 @@ int buctd_adam_step(float* p, const float* g, float* m, float* v, long n, float 
  * (lib/utils/utils.py:260-267).  first_step != 0: the momentum buffer is initialised with the gradient. */
 int buctd_sgd_step(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum, float weight_decay,
                    int nesterov, int first_step, float gscale, void* stream);
+/* The same steps with a clip coefficient that lives on the device: the gradient is multiplied by gscale * (*coef) before
+ * anything else (SGD: before the weight-decay term, as torch clips p.grad before step() adds the decay).  coef is what
+ * buctd_grad_clip_coef wrote; nothing is read back by the host.  *coef == 1.0f returns the bits of the plain steps (one
+ * kernel body serves both forms). */
+int buctd_adam_step_dscale(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                           float eps, int step, float gscale, const float* coef, void* stream);
+int buctd_sgd_step_dscale(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
+                          float weight_decay, int nesterov, int first_step, float gscale, const float* coef, void* stream);
+
+/* ------------------------------------------------- gradient-norm clipping --- */
+/* torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite False) on the flat gradient arena -
+ * the reference clips between backward() and step() (lib/core/train.py:138-141).
+ * buctd_grad_sumsq: *sumsq = sum of g[i]^2 over the nruns element runs [runs[2 r], runs[2 r + 1]) of g (runs: HOST array of
+ * 2 nruns longs, 0 <= start < end; what FlatParams.grad_runs() returns).  Elements outside the runs are never read.  fp64
+ * throughout (a float's square is exact there).  Order: every run is cut into chunks of BUCTD_GRAD_SUMSQ_CHUNK elements
+ * counted from its first element, one partial sum per chunk in the workspace, added by one workgroup in a fixed order: the
+ * result depends on the runs and the values alone, not on the grid or the number of CUs, and is bit-identical from launch to
+ * launch (no floating-point atomics).  A run that starts on a 16-byte boundary is read with 16-byte loads and returns the
+ * bits of the scalar path.  Workspace: 8 bytes per chunk, 8-byte aligned; buctd_grad_sumsq_workspace gives the size (0 for
+ * a bad run list). */
+#define BUCTD_GRAD_SUMSQ_CHUNK 8192
+size_t buctd_grad_sumsq_workspace(const long* runs, int nruns);
+int buctd_grad_sumsq(const float* g, const long* runs, int nruns, double* sumsq, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* total_norm = gscale * sqrt(*sumsq) ; coef = min(1, max_norm / (total_norm + 1e-6)) - torch's expressions, in fp64; both
+ * are stored as one float each, on the device.  gscale: the scale the optimizer step applies to the gradient (1 / world),
+ * so that the norm is the averaged gradient's.  A non-finite norm goes through the same expressions (inf -> coef 0,
+ * NaN -> coef NaN): no special case. */
+int buctd_grad_clip_coef(const double* sumsq, double gscale, double max_norm, float* coef, float* total_norm, void* stream);
+/* abs_mean[s] = mean |g[i]|, norm[s] = sqrt(sum g[i]^2) over i in [spans[2 s], spans[2 s + 1]) for P segments (spans: DEVICE
+ * array of 2 P longs - the parameters' spans in the arena): get_network_grad_flow (lib/utils/utils.py:293-300) without a
+ * host trip per parameter.  fp64, one workgroup per segment, fixed order.  A monitor, not part of the step. */
+int buctd_grad_segment_stats(const float* g, const long* spans, int P, double* abs_mean, double* norm, void* stream);
 
 /* Fused self-attention (flash style, nothing T x T in memory) - nn.MultiheadAttention of the TransPose encoder layer
  * (transpose_h.py:168-213) and the CoAM attention cores (self_attention.py:74-86):

@@ -134,6 +134,22 @@ VIS_POSE_TILE_W, VIS_POSE_TILE_H, VIS_POSE_CHUNK = 64, 16, 256
 # BUCTD_GRAD_SUMSQ_CHUNK of the header: elements per partial sum of buctd_grad_sumsq
 GRAD_SUMSQ_CHUNK = 8192
 
+# BUCTD_STEP_MAX_GROUPS / BUCTD_STEP_CHUNK of the header: the grouped optimizer steps (csrc/optim_groups.hip)
+STEP_MAX_GROUPS, STEP_CHUNK = 16, 16384
+
+
+class StepChunk(C.Structure):           # mirrors buctd_step_chunk (16 bytes: one row of the chunk table in device memory)
+    _fields_ = [("start", C.c_long), ("len", C.c_int), ("group", C.c_int)]
+
+
+class AdamGroup(C.Structure):           # mirrors buctd_adam_group
+    _fields_ = ([(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] +
+                [("decoupled", C.c_int), ("step", C.c_int)])
+
+
+class SgdGroup(C.Structure):            # mirrors buctd_sgd_group
+    _fields_ = [(n, C.c_float) for n in ("lr", "momentum", "weight_decay")] + [("nesterov", C.c_int)]
+
 
 class MatmulDesc(C.Structure):
     _fields_ = [
@@ -327,6 +343,11 @@ SIGNATURES = {
     "buctd_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
     "buctd_sgd_step_dscale": (_I, [_P, _P, _P, _L, _F, _F, _F, _I, _I, _F, _P, _P]),
     "buctd_adam_step_dscale": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P]),
+    # parameter groups (csrc/optim_groups.hip); runs, run groups and the group table are host arrays, the chunk table is
+    # a host array for buctd_step_chunks and device memory for the two steps
+    "buctd_step_chunks": (_L, [_PL, _PI, _I, C.POINTER(StepChunk)]),
+    "buctd_adam_step_groups": (_I, [_P, _P, _P, _P, _P, _L, C.POINTER(AdamGroup), _I, _F, _P, _P]),
+    "buctd_sgd_step_groups": (_I, [_P, _P, _P, _P, _L, C.POINTER(SgdGroup), _I, _F, _P, _P]),
     # gradient-norm clipping (csrc/grad_norm.hip); runs: a host array of longs, spans: a device one
     "buctd_grad_sumsq_workspace": (_SZ, [_PL, _I]),
     "buctd_grad_sumsq": (_I, [_P, _PL, _I, _P, _P, _SZ, _P]),

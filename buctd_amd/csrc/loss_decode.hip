@@ -3,6 +3,7 @@
 // condition heat-map rendering (JointsDataset.py:457-543), flip-test merge (lib/core/function.py:226-236),
 // and the fused Adam update (lib/utils/utils.py:268-272).  All HBM-bound; one pass per tensor.
 #include "common.h"
+#include "step_math.h"
 #include "../../include/buctd_hip.h"
 
 // --------------------------------------------------------------- joints MSE ----
@@ -626,8 +627,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float b1, float b2, float eps, float bc1, float bc2_sqrt,
                                                    float gscale, const float* __restrict__ coef) {
   if (DSCALE) gscale = gscale * coef[0];
-  // torch.optim.Adam (no amsgrad, no weight decay):
-  //   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+  // torch.optim.Adam (no amsgrad, no weight decay): adam_update of step_math.h on every element
   const float step_size = lr / bc1;
   const long n4 = n >> 2;
   const long step = (long)gridDim.x * 256;
@@ -638,22 +638,20 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      mm[j] = b1 * mm[j] + (1.f - b1) * gg[j];
-      vv[j] = b2 * vv[j] + (1.f - b2) * gg[j] * gg[j];
-      const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-      pp[j] -= step_size * (mm[j] / denom);
+      float pj = pp[j], mj = mm[j], vj = vv[j];
+      adam_update(pj, gg[j], mj, vj, b1, b2, eps, step_size, bc2_sqrt);
+      pp[j] = pj, mm[j] = mj, vv[j] = vj;
     }
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
     reinterpret_cast<f32x4*>(v)[i] = vv;
   }
   for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
-    const float gg = g[i] * gscale;
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
+    float pp = p[i], mm = m[i], vv = v[i];
+    adam_update(pp, g[i] * gscale, mm, vv, b1, b2, eps, step_size, bc2_sqrt);
     m[i] = mm;
     v[i] = vv;
-    p[i] -= step_size * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+    p[i] = pp;
   }
 }
 template <bool DSCALE>
@@ -691,13 +689,10 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   const long step = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
     float pp = p[i];
-    float gg = g[i] * gscale + wd * pp;
-    if (mu != 0.f) {
-      const float b = first ? gg : mu * buf[i] + gg;
-      buf[i] = b;
-      gg = nesterov ? gg + mu * b : b;
-    }
-    p[i] = pp - lr * gg;
+    float b = (mu != 0.f && !first) ? buf[i] : 0.f;
+    sgd_update(pp, g[i] * gscale, b, lr, mu, wd, nesterov, first);
+    if (mu != 0.f) buf[i] = b;
+    p[i] = pp;
   }
 }
 template <bool DSCALE>

@@ -18,6 +18,7 @@ import weakref
 import torch
 import torch.distributed as dist
 
+from . import _C
 from . import nn as bnn
 from . import ops
 
@@ -31,6 +32,7 @@ class FlatParams:
     def __init__(self, module):
         bnn.prepare_module(module)
         self.params = []
+        self.names = {id(p): n for n, p in module.named_parameters()}     # for messages (parameter groups)
         seen = set()
         for p in module.parameters():
             if id(p) not in seen:
@@ -120,8 +122,10 @@ class _GradClip:
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.workspace = None
 
-    def measure(self, flat, gscale, max_norm):
-        runs = flat.grad_runs()
+    def measure(self, flat, gscale, max_norm, runs=None):
+        """runs: the spans to measure (the grouped optimizers: what this step updates); None = the arena's gradient runs"""
+        if runs is None:
+            runs = flat.grad_runs()
         if runs:
             need = ops.grad_sumsq_workspace(runs) // 8
             if self.workspace is None or self.workspace.numel() < need:
@@ -152,7 +156,7 @@ class _NormClipOption:
         self._last_clip = False
         flat.optimizer = weakref.ref(self)
 
-    def _clip_coef(self, gscale):
+    def _clip_coef(self, gscale, runs=None):
         """-> the device coefficient for this step's kernels, or None when the option is off"""
         m = self.max_grad_norm
         if m is None or m == 0:
@@ -161,7 +165,7 @@ class _NormClipOption:
         if not m > 0:
             raise ValueError(f"max_grad_norm must be positive (or None / 0 for no clipping), got {m!r}")
         clip = _arena_clip(self.flat)
-        clip.measure(self.flat, gscale, float(m))
+        clip.measure(self.flat, gscale, float(m), runs)
         self._last_clip = True
         return clip.coef
 
@@ -177,7 +181,132 @@ class _NormClipOption:
         return self.flat._clip.coef.view(()) if self._last_clip else None
 
 
-class FusedAdam(_NormClipOption, torch.optim.Optimizer):
+class _Live:
+    """What a grouped step works on while the set of parameters holding a gradient stays the same: the chunk table in device
+    memory, the merged spans the norm clip measures, the groups that step and the parameters that are stepped."""
+
+    def __init__(self, table, runs, groups, ids):
+        self.table, self.runs, self.groups, self.ids = table, runs, groups, ids
+
+
+class _ParamGroups:
+    """The grouped form of FusedAdam / FusedSGD (groups=[...], torch's param_groups on the flat arena).
+
+    A step updates exactly the parameters that belong to a group and hold a gradient right now - FlatParams.grad_runs()
+    restricted to the group members - as ONE launch of buctd_adam_step_groups / buctd_sgd_step_groups over a chunk table
+    (buctd_step_chunks) that lives in device memory.  The table is built and uploaded when the set of live parameters
+    changes and cached on that set, so a steady-state step is one launch and no copy; the hyper-parameters travel in the
+    kernel arguments, so a scheduler that edits param_groups[i]['lr'] needs nothing else.  Arena parameters in no group and
+    the slots of parameters without a gradient in the parameter / moment / momentum arenas are never read or written; the
+    padding that fills a stepped parameter's last 16 bytes is part of its span and keeps its zeros (zero gradient, zero
+    moments)."""
+
+    def _check_groups(self, flat, groups, grad_sync):
+        who = type(self).__name__
+        groups = [dict(g) for g in groups]
+        if not groups:
+            raise ValueError(f"{who}: groups is empty")
+        if len(groups) > _C.STEP_MAX_GROUPS:
+            raise ValueError(f"{who}: {len(groups)} parameter groups, at most {_C.STEP_MAX_GROUPS} fit one launch")
+        owner = {}
+        for gi, g in enumerate(groups):
+            ps = g.get("params", [])
+            g["params"] = ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            for p in ps:
+                if not isinstance(p, torch.Tensor) or not flat.owns(p):
+                    shape = tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__
+                    raise ValueError(f"{who}: group {gi} holds a parameter of shape {shape} that is not in the arena")
+                if id(p) in owner:
+                    raise ValueError(f"{who}: parameter {flat.names.get(id(p), '?')!r} is in group {owner[id(p)]} and in "
+                                     f"group {gi}")
+                owner[id(p)] = gi
+        if grad_sync is not None:
+            for p in flat.params:
+                if id(p) not in owner or not p.requires_grad:
+                    what = "is in no group" if id(p) not in owner else "is frozen"
+                    raise ValueError(f"{who}: parameter {flat.names.get(id(p), '?')!r} {what}; with a gradient exchange "
+                                     "(grad_sync) the grouped form needs every arena parameter in a group and trainable")
+        return groups, owner
+
+    def _init_groups(self, owner):
+        flat = self.flat
+        self._members = [(p, owner[id(p)]) for p in flat.params if id(p) in owner]     # in arena order
+        self._live = None
+        self._live_key = None
+        self._stepped = set()          # ids of the parameters that carry optimizer state (torch: those stepped at least once)
+        self.table_builds = 0          # chunk tables built and uploaded so far: one per change of the live set
+
+    def _live_set(self):
+        key = bytes(p.grad is not None for p, _ in self._members)
+        if key == self._live_key:
+            return self._live
+        flat = self.flat
+        runs, owners, merged, ids = [], [], [], set()
+        for p, gi in self._members:
+            if p.grad is None:
+                continue
+            s = flat.offsets[id(p)]
+            e = s + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            if runs and runs[-1][1] == s and owners[-1] == gi:
+                runs[-1][1] = e
+            else:
+                runs.append([s, e])
+                owners.append(gi)
+            if merged and merged[-1][1] == s:
+                merged[-1][1] = e
+            else:
+                merged.append([s, e])
+            ids.add(id(p))
+        table = None
+        if runs:
+            table = ops.step_chunk_table(ops.step_chunks(runs, owners, flat.numel), flat.flat.device)
+            self.table_builds += 1
+        self._live = _Live(table, [(s, e) for s, e in merged], sorted(set(owners)), ids)
+        self._live_key = key
+        return self._live
+
+    def _after_step(self):
+        ops.weights_updated()
+        ops.refresh_prepared(self.flat.flat.device)
+        if self.flat.flat.is_cuda:
+            ops.acc_pool.reset(self.flat.flat.device)
+
+    def _grouped_state_dict(self, per_param, torch_class):
+        fill = torch_class([torch.zeros(1)], lr=1e-3).defaults      # the keys this torch's optimizer reads from a group
+        state, groups, idx = {}, [], 0
+        for gi, g in enumerate(self.param_groups):
+            ids = []
+            for p in g["params"]:
+                if id(p) in self._stepped:
+                    state[idx] = per_param(p, gi)
+                ids.append(idx)
+                idx += 1
+            d = {k: v for k, v in g.items() if k != "params"}
+            for k, v in fill.items():
+                d.setdefault(k, v)
+            d["params"] = ids
+            groups.append(d)
+        return {"state": state, "param_groups": groups}
+
+    def _grouped_entries(self, sd):
+        """[(group index, parameter, its state or None)] of a torch-format state_dict with this optimizer's group layout"""
+        if "state" not in sd or len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError(f"{type(self).__name__}: the state_dict has {len(sd.get('param_groups', []))} parameter groups, "
+                             f"this optimizer {len(self.param_groups)}")
+        out = []
+        for gi, (g, src) in enumerate(zip(self.param_groups, sd["param_groups"])):
+            if len(src["params"]) != len(g["params"]):
+                raise ValueError(f"{type(self).__name__}: group {gi} of the state_dict has {len(src['params'])} parameters, "
+                                 f"this optimizer's {len(g['params'])}")
+            for p, i in zip(g["params"], src["params"]):
+                out.append((gi, p, sd["state"].get(i, sd["state"].get(str(i)))))
+        return out
+
+    def _arena_view(self, arena, p):
+        return torch.as_strided(arena, p.shape, p.stride(), self.flat.offsets[id(p)])
+
+
+class FusedAdam(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) semantics on the flat arena.
 
     One step counter for the whole arena, and every step updates the whole arena: a parameter without a gradient is stepped
@@ -186,12 +315,31 @@ class FusedAdam(_NormClipOption, torch.optim.Optimizer):
     gains or loses its gradient in the middle of a run differs from torch: torch counts the steps of each parameter on its
     own (its bias corrections start at that parameter's first gradient) and leaves a parameter alone whenever its gradient
     is None, while here the bias corrections follow the arena's counter and the moments of a parameter that lost its
-    gradient keep decaying into it."""
+    gradient keep decaying into it.
 
-    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None, max_grad_norm=None):
+    The grouped form (groups=[{"params": [...], "lr": ..., "weight_decay": ..., "betas": ..., "eps": ...}, ...] as torch
+    takes them, or a non-zero weight_decay, which makes one group of every parameter) lifts these deviations: see
+    _ParamGroups.  weight_decay is torch.optim.Adam's coupled decay, with decoupled_weight_decay torch.optim.AdamW's.  Every
+    group keeps its own step counter, which advances on the steps in which at least one of its parameters holds a gradient;
+    a parameter without a gradient is left alone, moments included.  What remains of the deviation is inside a group:
+    parameters of one group that gain or lose their gradients at different times share that group's counter (torch counts
+    per parameter) - put parameters that are unfrozen at different times into different groups.  Without groups and with
+    weight_decay 0 nothing of this applies: the class is the plain one above."""
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None, max_grad_norm=None, *, groups=None,
+                 weight_decay=0.0, decoupled_weight_decay=False):
         if not isinstance(flat, FlatParams):
             raise TypeError("FusedAdam works on an engine.FlatParams arena")
-        super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps))
+        self.grouped = groups is not None or weight_decay != 0
+        if self.grouped:
+            groups, owner = self._check_groups(flat, [{"params": flat.params}] if groups is None else groups, grad_sync)
+            super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                          decoupled_weight_decay=bool(decoupled_weight_decay)))
+            self.flat = flat
+            self._init_groups(owner)
+            self.group_steps = [0] * len(self.param_groups)
+        else:
+            super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps))
         self.flat = flat
         self._init_clip(flat, max_grad_norm)       # the gradient-norm clip folded into step(): _NormClipOption
         self.exp_avg = torch.zeros_like(flat.flat)
@@ -205,6 +353,8 @@ class FusedAdam(_NormClipOption, torch.optim.Optimizer):
             raise NotImplementedError("closures are not used on the BUCTD path")
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
+        if self.grouped:
+            return self._step_groups(gscale)
         coef = self._clip_coef(gscale)
         self.step_count += 1
         g = self.param_groups[0]
@@ -215,14 +365,73 @@ class FusedAdam(_NormClipOption, torch.optim.Optimizer):
         if self.flat.flat.is_cuda:
             ops.acc_pool.reset(self.flat.flat.device)  # BatchNorm accumulators of the step: one fill, every stream is joined here
 
+    def _step_groups(self, gscale):
+        live = self._live_set()
+        coef = self._clip_coef(gscale, live.runs)
+        self.step_count += 1
+        if live.table is None:         # no group member holds a gradient: torch.optim.Adam does nothing either
+            return
+        for gi in live.groups:
+            self.group_steps[gi] += 1
+        self._stepped |= live.ids
+        table = (_C.AdamGroup * len(self.param_groups))()
+        for t, g, n in zip(table, self.param_groups, self.group_steps):
+            t.lr, t.beta1, t.beta2, t.eps, t.weight_decay = g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]
+            t.decoupled, t.step = int(bool(g["decoupled_weight_decay"])), n
+        ops.adam_step_groups(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, live.table, table, gscale, coef)
+        self._after_step()
+
     def zero_grad(self, set_to_none=True):
         self.zeroed = getattr(self, "zeroed", 0) + 1      # (StepGraph: the gradient views a capture installed are gone)
         for p in self.flat.params:
             p.grad = None
 
+    def _state_dict_groups(self):
+        def per_param(p, gi):
+            return {"step": torch.tensor(float(self.group_steps[gi])), "exp_avg": self._arena_view(self.exp_avg, p).clone(),
+                    "exp_avg_sq": self._arena_view(self.exp_avg_sq, p).clone()}
+        decoupled = any(g["decoupled_weight_decay"] for g in self.param_groups)
+        return self._grouped_state_dict(per_param, torch.optim.AdamW if decoupled else torch.optim.Adam)
+
+    def _load_state_dict_groups(self, sd):
+        entries = self._grouped_entries(sd)
+        for src in sd["param_groups"]:
+            for k in ("amsgrad", "maximize"):
+                if src.get(k):
+                    raise ValueError(f"FusedAdam does not implement {k}")
+        steps = [set() for _ in self.param_groups]
+        for gi, p, st in entries:
+            if st is not None:
+                for name in ("exp_avg", "exp_avg_sq"):
+                    if tuple(st[name].shape) != tuple(p.shape):
+                        raise ValueError(f"optimizer state of parameter {self.flat.names.get(id(p), '?')!r}: shape "
+                                         f"{tuple(st[name].shape)} != {tuple(p.shape)}")
+                steps[gi].add(int(float(st["step"])))
+        for gi, ss in enumerate(steps):
+            if len(ss) > 1:
+                raise ValueError(f"FusedAdam keeps one step counter per group: the steps of group {gi} differ in this "
+                                 f"state_dict ({sorted(ss)})")
+        self._stepped = set()
+        for gi, p, st in entries:
+            for name, arena in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+                view = self._arena_view(arena, p)
+                if st is None:
+                    view.zero_()
+                else:
+                    view.copy_(st[name])
+            if st is not None:
+                self._stepped.add(id(p))
+        self.group_steps = [ss.pop() if ss else 0 for ss in steps]
+        self.step_count = max(self.group_steps)
+        for g, src in zip(self.param_groups, sd["param_groups"]):
+            g.update({k: v for k, v in src.items() if k != "params"})
+
     def state_dict(self):
         """torch.optim.Adam's checkpoint format (what the reference stores under checkpoint['optimizer'],
-        tools/train.py:243-266): per-parameter 'step' / 'exp_avg' / 'exp_avg_sq' keyed by parameter index."""
+        tools/train.py:243-266): per-parameter 'step' / 'exp_avg' / 'exp_avg_sq' keyed by parameter index.  The grouped form
+        writes several param_groups, indices running over their concatenation, each parameter's step its group's counter."""
+        if self.grouped:
+            return self._state_dict_groups()
         state = {}
         if self.step_count > 0:
             for i, p in enumerate(self.flat.params):
@@ -240,7 +449,10 @@ class FusedAdam(_NormClipOption, torch.optim.Optimizer):
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
-        """Accepts a torch.optim.Adam state_dict (reference checkpoints) or this class's round-1 flat format."""
+        """Accepts a torch.optim.Adam state_dict (reference checkpoints) or this class's round-1 flat format; the grouped form
+        a torch.optim.Adam / AdamW state_dict with the same groups."""
+        if self.grouped:
+            return self._load_state_dict_groups(sd)
         if "state" not in sd:                      # round-1 private format: flat arenas
             self.step_count = int(sd["step"])
             self.exp_avg.copy_(sd["exp_avg"])
@@ -275,17 +487,35 @@ class FusedAdam(_NormClipOption, torch.optim.Optimizer):
                 g[k] = v
 
 
-class FusedSGD(_NormClipOption, torch.optim.Optimizer):
+class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     """torch.optim.SGD(lr, momentum, weight_decay, nesterov) semantics on the flat arena (one kernel per step) - the 'sgd'
-    branch of the reference's get_optimizer (lib/utils/utils.py:260-267).  Reads and writes torch.optim.SGD state_dicts."""
+    branch of the reference's get_optimizer (lib/utils/utils.py:260-267).  Reads and writes torch.optim.SGD state_dicts.
 
-    def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None, max_grad_norm=None):
+    With groups=[{"params": [...], "lr": ..., "momentum": ..., "weight_decay": ..., "nesterov": ...}, ...] the grouped form
+    (_ParamGroups): every group steps with its own values and a step is one launch however many gradient runs there are
+    (the plain form launches once per run)."""
+
+    def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None, max_grad_norm=None, *,
+                 groups=None):
         if not isinstance(flat, FlatParams):
             raise TypeError("FusedSGD works on an engine.FlatParams arena")
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(flat.params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
-                                           nesterov=nesterov))
+        defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=nesterov)
+        self.grouped = groups is not None
+        if self.grouped:
+            groups, owner = self._check_groups(flat, groups, grad_sync)
+            super().__init__(groups, defaults)
+            self.flat = flat
+            self._init_groups(owner)
+            for gi, g in enumerate(self.param_groups):
+                if g["nesterov"] and g["momentum"] <= 0:
+                    raise ValueError(f"FusedSGD: group {gi}: Nesterov momentum requires a momentum and zero dampening")
+                if g["dampening"] not in (0, 0.0):
+                    raise ValueError(f"FusedSGD: group {gi}: dampening = 0 is what FusedSGD implements")
+            momentum = any(g["momentum"] for g in self.param_groups)
+        else:
+            super().__init__(flat.params, defaults)
         self.flat = flat
         self.buf = torch.zeros_like(flat.flat) if momentum else None
         self.step_count = 0
@@ -298,6 +528,8 @@ class FusedSGD(_NormClipOption, torch.optim.Optimizer):
             raise NotImplementedError("closures are not used on the BUCTD path")
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
+        if self.grouped:
+            return self._step_groups(gscale)
         coef = self._clip_coef(gscale)
         g = self.param_groups[0]
         # torch.optim.SGD touches only parameters that hold a gradient: a parameter with p.grad None keeps its value (no
@@ -312,12 +544,60 @@ class FusedSGD(_NormClipOption, torch.optim.Optimizer):
         if self.flat.flat.is_cuda:
             ops.acc_pool.reset(self.flat.flat.device)
 
+    def _step_groups(self, gscale):
+        live = self._live_set()
+        coef = self._clip_coef(gscale, live.runs)
+        self.step_count += 1
+        if live.table is None:
+            return
+        self._stepped |= live.ids
+        table = (_C.SgdGroup * len(self.param_groups))()
+        for t, g in zip(table, self.param_groups):
+            t.lr, t.momentum, t.weight_decay, t.nesterov = g["lr"], g["momentum"], g["weight_decay"], int(bool(g["nesterov"]))
+        # a zero momentum buffer makes "buf = momentum * buf + g" the first-step "buf = g", as in the plain form
+        ops.sgd_step_groups(self.flat.flat, self.flat.grad, self.buf, live.table, table, gscale, coef)
+        self._after_step()
+
     def zero_grad(self, set_to_none=True):
         self.zeroed = getattr(self, "zeroed", 0) + 1
         for p in self.flat.params:
             p.grad = None
 
+    def _state_dict_groups(self):
+        sd = self._grouped_state_dict(lambda p, gi: {"momentum_buffer": self._arena_view(self.buf, p).clone()}
+                                      if self.param_groups[gi]["momentum"] else None, torch.optim.SGD)
+        sd["state"] = {i: st for i, st in sd["state"].items() if st is not None}     # torch: no state without momentum
+        return sd
+
+    def _load_state_dict_groups(self, sd):
+        entries = self._grouped_entries(sd)
+        for gi, src in enumerate(sd["param_groups"]):
+            if src.get("dampening", 0) not in (0, 0.0):
+                raise ValueError("FusedSGD implements dampening = 0 (the reference's recipe)")
+            if src.get("maximize"):
+                raise ValueError("FusedSGD does not implement maximize")
+        if self.buf is None and any(st is not None and st.get("momentum_buffer") is not None for _, _, st in entries):
+            raise ValueError("FusedSGD was built without momentum but the state_dict carries momentum buffers")
+        self._stepped = set()
+        for gi, p, st in entries:
+            has = st is not None and st.get("momentum_buffer") is not None
+            if self.buf is not None:
+                view = self._arena_view(self.buf, p)
+                if has:
+                    view.copy_(st["momentum_buffer"])
+                else:
+                    view.zero_()
+            if has:
+                self._stepped.add(id(p))
+        self.step_count = 1 if self._stepped else 0
+        for g, src in zip(self.param_groups, sd["param_groups"]):
+            g.update({k: v for k, v in src.items() if k != "params"})
+        if self.buf is None and any(g["momentum"] for g in self.param_groups):
+            self.buf = torch.zeros_like(self.flat.flat)
+
     def state_dict(self):
+        if self.grouped:
+            return self._state_dict_groups()
         state = {}
         if self.buf is not None and self.step_count > 0:
             for i, p in enumerate(self.flat.params):
@@ -333,6 +613,8 @@ class FusedSGD(_NormClipOption, torch.optim.Optimizer):
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        if self.grouped:
+            return self._load_state_dict_groups(sd)
         state = sd.get("state", {})
         loaded = 0
         for i, p in enumerate(self.flat.params):
@@ -579,12 +861,14 @@ class DataParallel(torch.nn.Module):
     # (checkpoints carry the reference's 'module.' prefix through nn.Module's own state_dict: the wrapped net is `self.module`)
 
 
-def get_optimizer(cfg, model, max_grad_norm=None):
+def get_optimizer(cfg, model, max_grad_norm=None, *, groups=None, weight_decay=None, decoupled_weight_decay=False):
     """reference lib/utils/utils.py:258-274: SGD(lr, MOMENTUM, WD, NESTEROV) for 'sgd', Adam(lr) for 'adam' - here the fused
     flat-arena optimizers, wired to the data-parallel gradient exchange when `model` is an engine.DataParallel.
     max_grad_norm (or, when it is None, cfg.TRAIN.CLIP_GRAD_NORM where a configuration carries that key; 0 = off) switches
     on the gradient-norm clip inside step() - the reference's loop calls clip_grad_norm(model.parameters(), args.clip)
-    between backward() and step() (lib/core/train.py:138-141)."""
+    between backward() and step() (lib/core/train.py:138-141).
+    groups (torch's param_groups, e.g. from groups_by_name), weight_decay and decoupled_weight_decay go to the optimizers'
+    grouped form; without them the two branches are the reference's: SGD decays with cfg.TRAIN.WD, Adam does not decay."""
     if max_grad_norm is None:
         max_grad_norm = getattr(cfg.TRAIN, "CLIP_GRAD_NORM", 0.0)
     if isinstance(model, DataParallel):
@@ -592,11 +876,49 @@ def get_optimizer(cfg, model, max_grad_norm=None):
     else:
         flat, sync = FlatParams(model), None
     if cfg.TRAIN.OPTIMIZER == "sgd":
-        return FusedSGD(flat, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM, weight_decay=cfg.TRAIN.WD,
-                        nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync, max_grad_norm=max_grad_norm)
+        if decoupled_weight_decay:
+            raise ValueError("get_optimizer: decoupled_weight_decay belongs to Adam (torch.optim.AdamW)")
+        return FusedSGD(flat, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM,
+                        weight_decay=cfg.TRAIN.WD if weight_decay is None else weight_decay,
+                        nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups)
     if cfg.TRAIN.OPTIMIZER == "adam":
-        return FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, max_grad_norm=max_grad_norm)
+        return FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups,
+                         weight_decay=0.0 if weight_decay is None else weight_decay,
+                         decoupled_weight_decay=decoupled_weight_decay)
     return None       # the reference returns None for any other name (utils.py:259, 274)
+
+
+_NORM_TYPES = (torch.nn.modules.batchnorm._BatchNorm, torch.nn.LayerNorm, torch.nn.GroupNorm)
+
+
+def groups_by_name(model, rules, no_decay_for_norm_and_bias=False):
+    """torch-style param_groups of `model` from an ordered list of (substring, options) rules: a parameter goes to the first
+    rule whose substring occurs in its name ("" matches every name), a parameter that matches none is left out - the
+    grouped optimizers never touch it.  options are a group's keys (lr, weight_decay, betas, ...).  With
+    no_decay_for_norm_and_bias, the weights of BatchNorm / LayerNorm / GroupNorm modules and every bias move into a twin group
+    behind their rule's group, with the same options but weight_decay = 0 (the usual fine-tuning recipe).  Rules that match
+    nothing give no group.  Returns the list for FusedAdam / FusedSGD / get_optimizer(groups=...)."""
+    model = model.module if isinstance(model, DataParallel) else model
+    norm_ids = set()
+    if no_decay_for_norm_and_bias:
+        for mod in model.modules():
+            if isinstance(mod, _NORM_TYPES):
+                norm_ids.update(id(p) for p in mod.parameters(recurse=False))
+    main = [[] for _ in rules]
+    twin = [[] for _ in rules]
+    for name, p in model.named_parameters():
+        for k, (sub, _) in enumerate(rules):
+            if sub in name:
+                plain = no_decay_for_norm_and_bias and (id(p) in norm_ids or name.rsplit(".", 1)[-1] == "bias")
+                (twin if plain else main)[k].append(p)
+                break
+    groups = []
+    for k, (_, options) in enumerate(rules):
+        if main[k]:
+            groups.append(dict(options, params=main[k]))
+        if twin[k]:
+            groups.append(dict(options, params=twin[k], weight_decay=0.0))
+    return groups
 
 
 def _arena_of(target):

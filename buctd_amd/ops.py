@@ -1521,6 +1521,53 @@ def _runs_array(runs):
     return (C.c_long * len(flat))(*flat), len(flat) // 2
 
 
+# ---- optimizer steps over parameter groups (csrc/optim_groups.hip) ---------------------------------------------------------
+def step_chunks(runs, run_group, numel):
+    """The chunk table (a host ctypes array of _C.StepChunk) of these ascending [start, end) runs of an arena of `numel`
+    elements, run r owned by group run_group[r]: buctd_step_chunks, count first, then fill.  No device call."""
+    arr, n = _runs_array(runs)
+    if n == 0 or n != len(run_group):
+        raise _C.BuctdHipError("step_chunks: one group id per run, at least one run")
+    if any(e > numel for _, e in runs):
+        raise _C.BuctdHipError(f"step_chunks: a run ends behind the arena's {numel} elements")
+    grp = (C.c_int * n)(*[int(v) for v in run_group])
+    count = lib().buctd_step_chunks(arr, grp, n, None)
+    if count < 0:
+        check(-1, "step_chunks")
+    out = (_C.StepChunk * count)()
+    if lib().buctd_step_chunks(arr, grp, n, out) != count:
+        check(-1, "step_chunks")
+    return out
+
+
+def step_chunk_table(chunks, device):
+    """the device copy of a step_chunks() result: a uint8 tensor of 16 bytes per chunk (the one upload of a live set)"""
+    return torch.frombuffer(bytearray(bytes(chunks)), dtype=torch.uint8).to(device)
+
+
+def _step_groups_args(table, coef):
+    if table.dtype != torch.uint8 or table.numel() == 0 or table.numel() % 16 != 0 or not table.is_contiguous():
+        raise _C.BuctdHipError("step_groups: the chunk table is a contiguous uint8 device tensor of 16 bytes per chunk")
+    if coef is not None and coef.dtype != torch.float32:
+        raise _C.BuctdHipError("step_groups: coef is a one-element fp32 device tensor")
+    return table.numel() // 16
+
+
+def adam_step_groups(p, g, m, v, table, groups, gscale=1.0, coef=None):
+    """One launch over the chunk table.  groups: a host array of _C.AdamGroup (lr, betas, eps, weight_decay, decoupled and
+    the group's own step), read during the call - nothing is copied to the device.  coef as in adam_step."""
+    n = _step_groups_args(table, coef)
+    check(lib().buctd_adam_step_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(table), n, groups, len(groups), gscale, ptr(coef),
+                                       stream_ptr()), "adam_step_groups")
+
+
+def sgd_step_groups(p, g, buf, table, groups, gscale=1.0, coef=None):
+    """groups: a host array of _C.SgdGroup; buf may be None only where every momentum is 0"""
+    n = _step_groups_args(table, coef)
+    check(lib().buctd_sgd_step_groups(ptr(p), ptr(g), ptr(buf), ptr(table), n, groups, len(groups), gscale, ptr(coef),
+                                      stream_ptr()), "sgd_step_groups")
+
+
 def grad_sumsq_workspace(runs):
     """bytes of workspace buctd_grad_sumsq needs for these [start, end) runs (8 per chunk of _C.GRAD_SUMSQ_CHUNK elements)"""
     arr, n = _runs_array(runs)

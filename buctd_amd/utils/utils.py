@@ -10,6 +10,25 @@ import torch
 from ..engine import get_optimizer  # noqa: F401  (same name / signature as the reference helper)
 
 
+def get_last_layer_optimizer(cfg, model):
+    """reference lib/utils/utils.py:277-290, its fine-tuning entry: freeze every parameter whose name lacks 'final_layer'
+    and run Adam(cfg.TRAIN.LR) over what is left - here a grouped engine.FusedAdam with that one group, so the frozen trunk
+    is never read or written by a step (and its backward kernels are not launched).  The model stays as it is otherwise:
+    in train mode BatchNorm running statistics keep moving, as in the reference.  `model` may be an engine.DataParallel in
+    a world of one; under a gradient exchange the grouped form refuses a partly frozen arena."""
+    from .. import engine
+    for name, param in model.named_parameters():
+        if 'final_layer' not in name:
+            param.requires_grad = False
+    if isinstance(model, engine.DataParallel):
+        flat = model.flatten()
+        sync = model.sync_gradients if model._exchange else None      # a world of one exchanges nothing
+    else:
+        flat, sync = engine.FlatParams(model), None
+    head = [p for p in flat.params if p.requires_grad]
+    return engine.FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, groups=[{"params": head}])
+
+
 def get_network_grad_flow(model):
     """Sum over the trainable parameters of mean |grad|, a Python float (reference lib/utils/utils.py:293-300).  When the
     model's parameters live in an engine.FlatParams arena the per-parameter means come from one launch over the gradient

@@ -652,6 +652,51 @@ int buctd_adam_step_dscale(float* p, const float* g, float* m, float* v, long n,
 int buctd_sgd_step_dscale(float* p, const float* g, float* momentum_buf, long n, float lr, float momentum,
                           float weight_decay, int nesterov, int first_step, float gscale, const float* coef, void* stream);
 
+/* ------------------------------------------------------ parameter groups --- */
+/* The same two steps over PARTS of the arena, each part with the hyper-parameters of its parameter group, as one launch
+ * (engine.FusedAdam / FusedSGD with groups=: fine-tuning with a frozen trunk, a head at another learning rate, weight decay
+ * on some tensors only).  The parts are given as a chunk table in device memory: chunk c is the len elements from element
+ * start of p / g / m / v / buf and belongs to group `group` of the table passed by value.  Elements outside the chunks are
+ * neither read nor written.  Workgroups walk the table with a grid stride; every access is 16 bytes wide, so start and len
+ * are multiples of 4 (the arena pads every parameter to 16 bytes) and the buffers are 16-byte aligned.
+ * Adam per element: coupled decay (decoupled == 0, torch.optim.Adam(weight_decay)) g = g * scale + weight_decay * p, then
+ * the update of buctd_adam_step; decoupled (torch.optim.AdamW) p *= 1 - lr * weight_decay (formed in double by the host,
+ * as torch forms it), then that update on the undecayed gradient.  With weight_decay == 0 both give the bits of
+ * buctd_adam_step / _dscale on the same elements with the same hyper-parameters and step; the SGD form gives the bits of
+ * buctd_sgd_step / _dscale with first_step = 0 (one set of per-element functions, csrc/step_math.h, serves all of them).
+ * scale = gscale, times *coef where coef (device, what buctd_grad_clip_coef wrote) is not NULL. */
+#define BUCTD_STEP_MAX_GROUPS 16
+#define BUCTD_STEP_CHUNK 16384 /* elements, a multiple of 4 */
+typedef struct {
+  long start; /* first element; start % 4 == 0 */
+  int len;    /* 0 < len <= BUCTD_STEP_CHUNK, len % 4 == 0 */
+  int group;  /* 0 <= group < ngroups */
+} buctd_step_chunk;
+typedef struct {
+  float lr, beta1, beta2, eps, weight_decay;
+  int decoupled;
+  int step; /* this group's own step count, >= 1 in every group a chunk names (0: a group that has never stepped and is not
+               named); the bias corrections are formed from it in double */
+} buctd_adam_group;
+typedef struct {
+  float lr, momentum, weight_decay;
+  int nesterov;
+} buctd_sgd_group;
+/* HOST only, no device call: cuts the nruns element runs [runs[2 r], runs[2 r + 1]) - run r owned by group run_group[r] -
+ * into chunks of BUCTD_STEP_CHUNK elements counted from the run's first element (the last chunk of a run holds the rest)
+ * and returns their number; out == NULL only counts.  Runs are given in ascending order.  Returns -1 (message in
+ * buctd_last_error) for an empty, unaligned (start or end not a multiple of 4), descending or overlapping run and for a
+ * group id outside [0, BUCTD_STEP_MAX_GROUPS). */
+long buctd_step_chunks(const long* runs, const int* run_group, int nruns, buctd_step_chunk* out);
+/* groups: HOST array of ngroups (1 .. BUCTD_STEP_MAX_GROUPS) entries, read during the call and handed to the kernel in its
+ * arguments: nothing is copied to the device.  chunks_device: nchunks (> 0) entries as buctd_step_chunks wrote them; the
+ * caller keeps every chunk inside the buffers and every group id below ngroups.  A group no chunk names costs nothing. */
+int buctd_adam_step_groups(float* p, const float* g, float* m, float* v, const buctd_step_chunk* chunks_device, long nchunks,
+                           const buctd_adam_group* groups, int ngroups, float gscale, const float* coef, void* stream);
+/* buf: the momentum arena; may be NULL only where every group's momentum is 0 (it is not touched then) */
+int buctd_sgd_step_groups(float* p, const float* g, float* buf, const buctd_step_chunk* chunks_device, long nchunks,
+                          const buctd_sgd_group* groups, int ngroups, float gscale, const float* coef, void* stream);
+
 /* ------------------------------------------------- gradient-norm clipping --- */
 /* torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite False) on the flat gradient arena -
  * the reference clips between backward() and step() (lib/core/train.py:138-141).

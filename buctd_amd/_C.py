@@ -151,6 +151,10 @@ class SgdGroup(C.Structure):            # mirrors buctd_sgd_group
     _fields_ = [(n, C.c_float) for n in ("lr", "momentum", "weight_decay")] + [("nesterov", C.c_int)]
 
 
+class AvgItem(C.Structure):             # mirrors buctd_avg_item (24 bytes: one row of the item table in device memory)
+    _fields_ = [("src", C.c_void_p), ("avg", C.c_void_p), ("n", C.c_long)]
+
+
 class MatmulDesc(C.Structure):
     _fields_ = [
         ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -353,6 +357,10 @@ SIGNATURES = {
     "buctd_grad_sumsq": (_I, [_P, _PL, _I, _P, _P, _SZ, _P]),
     "buctd_grad_clip_coef": (_I, [_P, _D, _D, _P, _P, _P]),
     "buctd_grad_segment_stats": (_I, [_P, _P, _I, _P, _P, _P]),
+    # weight averaging (csrc/weight_avg.hip); the item table of buctd_ema_update_tensors is device memory
+    "buctd_ema_update": (_I, [_P, _P, _L, _F, _P]),
+    "buctd_ema_update_tensors": (_I, [_P, _I, _F, _P]),
+    "buctd_swap": (_I, [_P, _P, _L, _P]),
     # bf16 inference mode (csrc/conv_bf16.hip)
     "buctd_bf16_pack_conv": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P]),
     "buctd_bf16_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _SZ, _P]),

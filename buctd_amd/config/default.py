@@ -49,6 +49,7 @@ _C.TRAIN = CN({
     'LR_FACTOR': 0.1, 'LR_STEP': [90, 110], 'LR': 0.001, 'OPTIMIZER': 'adam', 'MOMENTUM': 0.9, 'WD': 0.0001,
     'NESTEROV': False, 'GAMMA1': 0.99, 'GAMMA2': 0.0, 'BEGIN_EPOCH': 0, 'END_EPOCH': 140, 'RESUME': False,
     'CHECKPOINT': '', 'BATCH_SIZE_PER_GPU': 32, 'SHUFFLE': True, 'USE_BU_BBOX': True,
+    'EMA_DECAY': 0.0,      # > 0: get_optimizer attaches an engine.WeightAverage with this decay (not in the reference)
 })
 
 _C.TEST = CN({

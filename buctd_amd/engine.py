@@ -11,6 +11,7 @@ What it replaces in the reference:
 BatchNorm statistics stay per replica, like under nn.DataParallel (no SyncBN); buffers of rank 0 are the ones a
 checkpoint sees (broadcast_buffers()).
 """
+import contextlib
 import os
 import time
 import weakref
@@ -31,6 +32,7 @@ class FlatParams:
 
     def __init__(self, module):
         bnn.prepare_module(module)
+        self.module = module       # WeightAverage: buffers and state_dict keys of the network the arena belongs to
         self.params = []
         self.names = {id(p): n for n, p in module.named_parameters()}     # for messages (parameter groups)
         seen = set()
@@ -326,6 +328,8 @@ class FusedAdam(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     per parameter) - put parameters that are unfrozen at different times into different groups.  Without groups and with
     weight_decay 0 nothing of this applies: the class is the plain one above."""
 
+    avg = None      # the engine.WeightAverage attached to this optimizer: step() ends with avg.update()
+
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None, max_grad_norm=None, *, groups=None,
                  weight_decay=0.0, decoupled_weight_decay=False):
         if not isinstance(flat, FlatParams):
@@ -354,7 +358,13 @@ class FusedAdam(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
         if self.grouped:
-            return self._step_groups(gscale)
+            self._step_groups(gscale)
+        else:
+            self._step_plain(gscale)
+        if self.avg is not None:
+            self.avg.update()      # the averaged weights follow the step: one launch behind it (WeightAverage)
+
+    def _step_plain(self, gscale):
         coef = self._clip_coef(gscale)
         self.step_count += 1
         g = self.param_groups[0]
@@ -495,6 +505,8 @@ class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     (_ParamGroups): every group steps with its own values and a step is one launch however many gradient runs there are
     (the plain form launches once per run)."""
 
+    avg = None      # as in FusedAdam
+
     def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None, max_grad_norm=None, *,
                  groups=None):
         if not isinstance(flat, FlatParams):
@@ -529,7 +541,13 @@ class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
         self.flat.collect()
         gscale = self.grad_sync() if self.grad_sync is not None else 1.0
         if self.grouped:
-            return self._step_groups(gscale)
+            self._step_groups(gscale)
+        else:
+            self._step_plain(gscale)
+        if self.avg is not None:
+            self.avg.update()
+
+    def _step_plain(self, gscale):
         coef = self._clip_coef(gscale)
         g = self.param_groups[0]
         # torch.optim.SGD touches only parameters that hold a gradient: a parameter with p.grad None keeps its value (no
@@ -861,16 +879,21 @@ class DataParallel(torch.nn.Module):
     # (checkpoints carry the reference's 'module.' prefix through nn.Module's own state_dict: the wrapped net is `self.module`)
 
 
-def get_optimizer(cfg, model, max_grad_norm=None, *, groups=None, weight_decay=None, decoupled_weight_decay=False):
+def get_optimizer(cfg, model, max_grad_norm=None, *, groups=None, weight_decay=None, decoupled_weight_decay=False,
+                  ema_decay=None):
     """reference lib/utils/utils.py:258-274: SGD(lr, MOMENTUM, WD, NESTEROV) for 'sgd', Adam(lr) for 'adam' - here the fused
     flat-arena optimizers, wired to the data-parallel gradient exchange when `model` is an engine.DataParallel.
     max_grad_norm (or, when it is None, cfg.TRAIN.CLIP_GRAD_NORM where a configuration carries that key; 0 = off) switches
     on the gradient-norm clip inside step() - the reference's loop calls clip_grad_norm(model.parameters(), args.clip)
     between backward() and step() (lib/core/train.py:138-141).
     groups (torch's param_groups, e.g. from groups_by_name), weight_decay and decoupled_weight_decay go to the optimizers'
-    grouped form; without them the two branches are the reference's: SGD decays with cfg.TRAIN.WD, Adam does not decay."""
+    grouped form; without them the two branches are the reference's: SGD decays with cfg.TRAIN.WD, Adam does not decay.
+    ema_decay (or, when it is None, cfg.TRAIN.EMA_DECAY; 0 = off) attaches a WeightAverage(optimizer, decay=ema_decay) - an
+    exponential moving average of the weights with warm-up, updated by every step(): `optimizer.avg`."""
     if max_grad_norm is None:
         max_grad_norm = getattr(cfg.TRAIN, "CLIP_GRAD_NORM", 0.0)
+    if ema_decay is None:
+        ema_decay = getattr(cfg.TRAIN, "EMA_DECAY", 0.0)
     if isinstance(model, DataParallel):
         flat, sync = model.flatten(), model.sync_gradients
     else:
@@ -878,14 +901,18 @@ def get_optimizer(cfg, model, max_grad_norm=None, *, groups=None, weight_decay=N
     if cfg.TRAIN.OPTIMIZER == "sgd":
         if decoupled_weight_decay:
             raise ValueError("get_optimizer: decoupled_weight_decay belongs to Adam (torch.optim.AdamW)")
-        return FusedSGD(flat, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM,
-                        weight_decay=cfg.TRAIN.WD if weight_decay is None else weight_decay,
-                        nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups)
-    if cfg.TRAIN.OPTIMIZER == "adam":
-        return FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups,
-                         weight_decay=0.0 if weight_decay is None else weight_decay,
-                         decoupled_weight_decay=decoupled_weight_decay)
-    return None       # the reference returns None for any other name (utils.py:259, 274)
+        opt = FusedSGD(flat, lr=cfg.TRAIN.LR, momentum=cfg.TRAIN.MOMENTUM,
+                       weight_decay=cfg.TRAIN.WD if weight_decay is None else weight_decay,
+                       nesterov=cfg.TRAIN.NESTEROV, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups)
+    elif cfg.TRAIN.OPTIMIZER == "adam":
+        opt = FusedAdam(flat, lr=cfg.TRAIN.LR, grad_sync=sync, max_grad_norm=max_grad_norm, groups=groups,
+                        weight_decay=0.0 if weight_decay is None else weight_decay,
+                        decoupled_weight_decay=decoupled_weight_decay)
+    else:
+        return None   # the reference returns None for any other name (utils.py:259, 274)
+    if ema_decay:
+        WeightAverage(opt, decay=ema_decay)
+    return opt
 
 
 _NORM_TYPES = (torch.nn.modules.batchnorm._BatchNorm, torch.nn.LayerNorm, torch.nn.GroupNorm)
@@ -967,6 +994,227 @@ def grad_stats(flat):
     out = torch.empty(2, P, dtype=torch.float64, device=flat.grad.device)
     ops.grad_segment_stats(flat.grad, flat._span_table, out[0], out[1])
     return {"abs_mean": out[0], "norm": out[1]}
+
+
+# ---- weight averaging on the arena (csrc/weight_avg.hip) -------------------------------------------------------------------
+def avg_decay(decay, t, warmup=True):
+    """effective EMA decay of update t (counting from 0): with warm-up min(decay, (1 + t) / (10 + t)) - 0.1, 2/11, 3/12, ... so
+    that the first updates are not dominated by the initial weights - else decay"""
+    return min(decay, (1 + t) / (10 + t)) if warmup else decay
+
+
+def avg_weight(mode, decay, warmup, t):
+    """w of update t in avg += w * (p - avg), as a Python float (a double; the launch rounds it once to fp32): 1 - the
+    effective decay for "ema", 1 / (t + 1) for "swa" (the equal average of t + 1 samples)"""
+    if mode == "swa":
+        return 1.0 / (t + 1)
+    return 1.0 - avg_decay(decay, t, warmup)
+
+
+def avg_due(step, start_step, update_every):
+    """whether the step-th optimizer step (counting from 1) is averaged"""
+    return step >= start_step and step % update_every == 0
+
+
+class WeightAverage:
+    """An averaged copy of the weights of a flat arena: an exponential moving average (mode "ema") or SWA's equal average of
+    the sampled iterates (mode "swa") - what torch.optim.swa_utils.AveragedModel keeps in a deep copy of the module, here a
+    shadow buffer of the arena's layout and one launch per update (buctd_ema_update: avg += w * (p - avg) over the whole
+    arena; where p == avg - frozen parameters, the sine position embedding, the padding - the bits stay).
+
+    target: a FusedAdam / FusedSGD - the average is attached (`optimizer.avg`) and every step() ends with update(); one
+    average per optimizer - or a FlatParams arena, updated by hand.
+    decay, warmup: "ema" - the effective decay of update t is avg_decay(decay, t, warmup); "swa" ignores them.
+    start_step, update_every: the step-th call of update() (the optimizer's steps, counting from 1) is averaged when
+    step >= start_step and step % update_every == 0; the others do nothing.
+    buffers: "live" - nothing is kept for module buffers, the network inside applied() runs on its current BatchNorm running
+    statistics; "average" - every fp32 buffer gets a shadow, updated by the same rule in one more launch
+    (buctd_ema_update_tensors) and exchanged by applied().  Integer buffers (num_batches_tracked) are left alone.
+
+    applied(): a context that exchanges arena and shadow in place (buctd_swap: no third buffer), so that the network - the
+    same module, ForwardGraph and Bf16Inference wrappers included - evaluates the averaged weights, and exchanges them back on
+    exit, exception or not.  Both exchanges announce themselves like an optimizer step (ops.weights_updated +
+    ops.refresh_prepared): prepared filter images, folded BatchNorms and captured forward graphs follow.
+    Under engine.DataParallel every rank averages the identical weights it holds: there is nothing to exchange."""
+
+    MODES, BUFFERS = ("ema", "swa"), ("live", "average")
+
+    def __init__(self, target, decay=0.9998, *, mode="ema", warmup=True, update_every=1, start_step=0, buffers="live"):
+        if mode not in self.MODES:
+            raise ValueError(f"WeightAverage: mode is one of {self.MODES}, got {mode!r}")
+        if buffers not in self.BUFFERS:
+            raise ValueError(f"WeightAverage: buffers is one of {self.BUFFERS}, got {buffers!r}")
+        if mode == "ema" and not 0.0 <= decay < 1.0:
+            raise ValueError(f"WeightAverage: decay must lie in [0, 1), got {decay!r}")
+        if int(update_every) != update_every or update_every < 1:
+            raise ValueError(f"WeightAverage: update_every is a positive whole number, got {update_every!r}")
+        if int(start_step) != start_step or start_step < 0:
+            raise ValueError(f"WeightAverage: start_step is a whole number >= 0, got {start_step!r}")
+        optimizer = target if isinstance(target, (FusedAdam, FusedSGD)) else None
+        if optimizer is not None and optimizer.avg is not None:
+            raise RuntimeError("WeightAverage: this optimizer already has a weight average attached (optimizer.avg); "
+                               "detach() it first")
+        self.flat = _arena_of(target)
+        self.mode, self.decay, self.warmup = mode, float(decay), bool(warmup)
+        self.update_every, self.start_step, self.buffers = int(update_every), int(start_step), buffers
+        self.steps = 0             # calls of update(): the optimizer's steps
+        self.num_updates = 0       # of which averaged
+        self.shadow = torch.empty_like(self.flat.flat)
+        self.shadow.copy_(self.flat.flat)
+        self._names, self._slots, self._views, self._buffer_shadow, self._table, self._table_key = [], [], [], None, None, None
+        if buffers == "average":
+            self._make_buffer_shadows()
+        self._applied = False
+        self._optimizer = None
+        if optimizer is not None:
+            optimizer.avg = self
+            self._optimizer = weakref.ref(optimizer)
+
+    def detach(self):
+        """take the average off its optimizer: step() no longer updates it"""
+        opt = self._optimizer() if self._optimizer is not None else None
+        if opt is not None and opt.avg is self:
+            opt.avg = None
+        self._optimizer = None
+
+    # -- buffers ---------------------------------------------------------------------------------------------------------
+    def _live_buffers(self):
+        """the averaged buffers as the modules hold them now (a module may have been handed a new tensor since)"""
+        return [held[leaf] for held, leaf in self._slots]
+
+    def _make_buffer_shadows(self):
+        # named_buffers()' names and order, with the dict that holds each buffer: a step looks them up without walking the tree
+        self._slots, views, off, seen = [], [], 0, set()
+        for prefix, mod in self.flat.module.named_modules():
+            for leaf, b in mod._buffers.items():
+                if b is None or id(b) in seen or not b.is_floating_point():
+                    continue
+                seen.add(id(b))
+                name = f"{prefix}.{leaf}" if prefix else leaf
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.device != self.flat.flat.device:
+                    raise ValueError(f"WeightAverage: buffer {name!r} is not a contiguous fp32 tensor on the arena's device")
+                self._names.append(name)
+                self._slots.append((mod._buffers, leaf))
+                views.append((off, b.numel()))
+                off += (b.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+        self._buffer_shadow = torch.zeros(off, dtype=torch.float32, device=self.flat.flat.device)
+        self._views = [self._buffer_shadow[o:o + n] for o, n in views]
+        for b, v in zip(self._live_buffers(), self._views):
+            v.copy_(b.reshape(-1))
+
+    def _buffer_views(self):
+        """the shadows of the averaged buffers, flat views into one allocation, in the order of self._names"""
+        return self._views
+
+    def _buffer_table(self):
+        live = self._live_buffers()
+        key = tuple(b.data_ptr() for b in live)
+        if key != self._table_key:             # a buffer moved (module.to(), a new tensor assigned): the table holds addresses
+            self._table = ops.avg_item_table(list(zip(live, self._buffer_views())), self.flat.flat.device)
+            self._table_key = key
+        return self._table
+
+    # -- the average -----------------------------------------------------------------------------------------------------
+    def weight(self):
+        """w of the next averaged update (a Python float)"""
+        return avg_weight(self.mode, self.decay, self.warmup, self.num_updates)
+
+    @torch.no_grad()
+    def update(self):
+        """Count one optimizer step and, when it is due, fold the arena into the average: one launch, plus one over the
+        buffer table with buffers="average".  Returns whether the step was averaged."""
+        if self._applied:
+            raise RuntimeError("WeightAverage.update() inside applied(): the arena holds the averaged weights")
+        self.steps += 1
+        if not avg_due(self.steps, self.start_step, self.update_every):
+            return False
+        w = self.weight()
+        ops.ema_update(self.flat.flat, self.shadow, w)
+        if self._names:
+            ops.ema_update_tensors(self._buffer_table(), w)
+        self.num_updates += 1
+        return True
+
+    def _exchange(self):
+        ops.swap(self.flat.flat, self.shadow)
+        if self._names:
+            for b, s in zip(self._live_buffers(), self._buffer_views()):
+                ops.swap(b, s)
+        # what an optimizer step does for everything keyed on the weights
+        ops.weights_updated()
+        ops.refresh_prepared(self.flat.flat.device)
+
+    @contextlib.contextmanager
+    def applied(self):
+        if self._applied:
+            raise RuntimeError("WeightAverage.applied() is not re-entrant: the averaged weights are already in the arena")
+        with torch.no_grad():
+            self._exchange()
+        self._applied = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self._exchange()
+            self._applied = False
+
+    def _average(self):
+        """(arena-layout buffer, buffer shadows or live buffers) that hold the average right now"""
+        if self._applied:
+            return self.flat.flat, (self._live_buffers() if self._names else [])
+        return self.shadow, (self._buffer_views() if self._names else [])
+
+    @torch.no_grad()
+    def model_state_dict(self):
+        """The network's state_dict() - its keys, shapes and order - with the averaged weights in place of the parameters (and
+        the averaged buffers with buffers="average"; every other entry is a copy of the live one): load it into a freshly
+        built network, or store it as the checkpoint to evaluate."""
+        arena, bufs = self._average()
+        averaged = dict(zip(self._names, bufs))
+        names = {id(b): n for n, b in self.flat.module.named_buffers()}
+        live = self.flat.module.state_dict(keep_vars=True)
+        out = type(live)()
+        if hasattr(live, "_metadata"):
+            out._metadata = live._metadata         # the modules' versions, which load_state_dict reads
+        for key, v in live.items():
+            if self.flat.owns(v):
+                out[key] = torch.as_strided(arena, v.shape, v.stride(), self.flat.offsets[id(v)]).clone()
+            elif names.get(id(v)) in averaged:
+                out[key] = averaged[names[id(v)]].view(v.shape).clone()
+            else:
+                out[key] = v.detach().clone()
+        return out
+
+    def state_dict(self):
+        arena, bufs = self._average()
+        return {"shadow": arena.detach().clone(), "buffer_names": list(self._names),
+                "buffer_shadows": [b.detach().clone() for b in bufs], "steps": self.steps, "num_updates": self.num_updates,
+                "mode": self.mode, "decay": self.decay, "warmup": self.warmup, "update_every": self.update_every,
+                "start_step": self.start_step, "buffers": self.buffers}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if self._applied:
+            raise RuntimeError("WeightAverage.load_state_dict() inside applied()")
+        if sd["mode"] not in self.MODES:
+            raise ValueError(f"WeightAverage: the state_dict's mode is {sd['mode']!r}")
+        if sd["buffers"] != self.buffers or list(sd["buffer_names"]) != self._names:
+            raise ValueError(f"WeightAverage: the state_dict was taken with buffers={sd['buffers']!r} over "
+                             f"{len(sd['buffer_names'])} buffers, this average has buffers={self.buffers!r} over "
+                             f"{len(self._names)}")
+        if tuple(sd["shadow"].shape) != tuple(self.shadow.shape):
+            raise ValueError(f"WeightAverage: the state_dict's shadow has {sd['shadow'].numel()} elements, the arena "
+                             f"{self.shadow.numel()}")
+        views = self._buffer_views() if self._names else []
+        for name, v, src in zip(self._names, views, sd["buffer_shadows"]):
+            if src.numel() != v.numel():
+                raise ValueError(f"WeightAverage: buffer {name!r} has {v.numel()} elements, the state_dict's {src.numel()}")
+        self.shadow.copy_(sd["shadow"])
+        for v, src in zip(views, sd["buffer_shadows"]):
+            v.copy_(src.reshape(-1))
+        self.steps, self.num_updates = int(sd["steps"]), int(sd["num_updates"])
+        self.mode, self.decay, self.warmup = sd["mode"], float(sd["decay"]), bool(sd["warmup"])
+        self.update_every, self.start_step = int(sd["update_every"]), int(sd["start_step"])
 
 
 # Stream-capture error mode of the two graph classes: "thread_local" - a DataLoader's pin-memory thread (hipHostMalloc) or any

@@ -1602,6 +1602,45 @@ def grad_segment_stats(g, spans, abs_mean, norm):
     check(lib().buctd_grad_segment_stats(ptr(g), ptr(spans), P, ptr(abs_mean), ptr(norm), stream_ptr()), "grad_segment_stats")
 
 
+# ---- weight averaging (csrc/weight_avg.hip) -------------------------------------------------------------------------------
+def _flat_f32(t, who):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise _C.BuctdHipError(f"{who}: contiguous fp32 device tensors")
+    return t
+
+
+def ema_update(p, avg, w):
+    """avg[i] = fmaf(w, p[i] - avg[i], avg[i]) over two fp32 buffers of one length; w: a Python float, rounded once to fp32"""
+    if _flat_f32(p, "ema_update").numel() != _flat_f32(avg, "ema_update").numel():
+        raise _C.BuctdHipError("ema_update: p and avg differ in length")
+    check(lib().buctd_ema_update(ptr(p), ptr(avg), p.numel(), w, stream_ptr()), "ema_update")
+
+
+def avg_item_table(pairs, device):
+    """the device table of buctd_ema_update_tensors for these (src, avg) tensor pairs: int64 [items, 3] = _C.AvgItem rows.
+    The table holds addresses: it lives as long as the tensors stay where they are."""
+    rows = []
+    for src, avg in pairs:
+        if _flat_f32(src, "avg_item_table").numel() != _flat_f32(avg, "avg_item_table").numel():
+            raise _C.BuctdHipError("avg_item_table: a source and its average differ in length")
+        rows.append((ptr(src), ptr(avg), src.numel()))
+    return torch.tensor(rows, dtype=torch.int64).view(-1, 3).to(device)
+
+
+def ema_update_tensors(table, w):
+    """the rule of ema_update over every item of an avg_item_table, one launch"""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise _C.BuctdHipError("ema_update_tensors: the item table is a contiguous int64 [items, 3] device tensor")
+    check(lib().buctd_ema_update_tensors(ptr(table), table.shape[0], w, stream_ptr()), "ema_update_tensors")
+
+
+def swap(a, b):
+    """exchange the contents of two fp32 buffers of one length in place, one launch, no third buffer"""
+    if _flat_f32(a, "swap").numel() != _flat_f32(b, "swap").numel():
+        raise _C.BuctdHipError("swap: the buffers differ in length")
+    check(lib().buctd_swap(ptr(a), ptr(b), a.numel(), stream_ptr()), "swap")
+
+
 def layernorm_fwd(x, gamma, beta, eps):
     Cn = x.shape[-1]
     rows = x.numel() // Cn

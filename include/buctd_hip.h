@@ -722,6 +722,34 @@ int buctd_grad_clip_coef(const double* sumsq, double gscale, double max_norm, fl
  * host trip per parameter.  fp64, one workgroup per segment, fixed order.  A monitor, not part of the step. */
 int buctd_grad_segment_stats(const float* g, const long* spans, int P, double* abs_mean, double* norm, void* stream);
 
+/* ------------------------------------------------------- weight averaging --- */
+/* An averaged copy of the flat parameter arena (engine.WeightAverage: an exponential moving average, or SWA's equal
+ * average), kept in a shadow buffer of the arena's layout (csrc/weight_avg.hip).  Per element
+ *     avg[i] = fmaf(w, p[i] - avg[i], avg[i])
+ * with w = 1 - decay for an EMA and 1 / (k + 1) for the k-th SWA sample, formed in double by the host and rounded once to
+ * float.  The lerp form is the contract: p[i] == avg[i] and w == 0 leave avg[i] bit-unchanged (a zero keeps its sign too),
+ * so frozen spans, constant tensors and the arena's zero padding need no table and one launch over the whole arena is right.
+ * Any n >= 0 (0: no launch) and any alignment: 16-byte accesses when both pointers are 16-byte aligned (with a scalar tail of
+ * n % 4 elements), a scalar kernel otherwise; both return the same bits.  Neither call allocates or synchronises.
+ * BUCTD_EINVAL before any launch: n < 0, a NULL pointer with n > 0, p and avg ranges that overlap without being the same
+ * buffer (p == avg is legal and changes nothing). */
+int buctd_ema_update(const float* p, float* avg, long n, float w, void* stream);
+/* The same rule over nitems separate tensors in ONE launch - the BatchNorm running statistics, which are module buffers
+ * outside the arena.  items_device: a table in DEVICE memory (8-byte aligned), built once; workgroups walk it with a grid
+ * stride.  An item may have any length (0 included: nothing happens) and alignment; the caller keeps every item inside its
+ * buffers and the avg ranges of different items apart.  nitems == 0: no launch.  BUCTD_EINVAL: nitems < 0, a NULL or
+ * misaligned table. */
+typedef struct {
+  const float* src;
+  float* avg;
+  long n;
+} buctd_avg_item;
+int buctd_ema_update_tensors(const buctd_avg_item* items_device, int nitems, float w, void* stream);
+/* a[i] <-> b[i] for i in [0, n), one pass, no third buffer (the arena of the largest network is several hundred MB): puts
+ * the averaged weights in front of the network and takes them out again.  Any n >= 0 and alignment, as above.
+ * BUCTD_EINVAL before any launch: n < 0, a NULL pointer with n > 0, buffers that share a byte. */
+int buctd_swap(float* a, float* b, long n, void* stream);
+
 /* Fused self-attention (flash style, nothing T x T in memory) - nn.MultiheadAttention of the TransPose encoder layer
  * (transpose_h.py:168-213) and the CoAM attention cores (self_attention.py:74-86):
  *     out[b][i] = sum_j dropout(softmax_j(scale * q_i . k_j)) v_j   per head.

@@ -248,6 +248,9 @@ SIGNATURES = {
     "buctd_x6_image_bytes": (C.c_size_t, [_I, _I, _I]),
     "buctd_x6_image": (_I, [_P, _I, _I, _I, _L, _L, _I, _L, _L, _I, _P, _P]),
     "buctd_x6_gemm": (_I, [_I, _I, _I, _P, _P, _P, _I, _F, _P, _L, _I, _L, _P]),
+    "buctd_x6_gemm_plan": (_I, [_I, _I, _I, _PI]),
+    "buctd_x6_gemm_tile": (_I, [_I, _I, _I, _I, _PI, _PI]),
+    "buctd_x6_image_path": (_I, [_P, _I, _I, _I, _L, _L, _I, _L, _L, _I, _I, _I, _PI]),
     "buctd_add": (_I, [_P, _P, _P, _L, _I, _P]),
     "buctd_add_n": (_I, [C.POINTER(_P), _I, _P, _L, _P]),
     "buctd_mul": (_I, [_P, _P, _P, _L, _P]),

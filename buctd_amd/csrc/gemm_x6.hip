@@ -49,6 +49,34 @@ struct GxImg {
   long vgs, vs, kgs, ks; // address(v, k) = (v / vg) * vgs + (v % vg) * vs + (k / kg) * kgs + (k % kg) * ks
 };
 
+// offset of row v of the logical matrix from p.src, in elements
+__host__ __device__ inline long gx_img_vo(const GxImg& p, int v) {
+  return p.vg ? (long)(v / p.vg) * p.vgs + (long)(v % p.vg) * p.vs : (long)v * p.vs;
+}
+
+// the eight slots k0 .. k0 + 7 of the row at vo come from two 16-byte loads: contiguous in k, all inside K, and the
+// ADDRESS of the first one on a 16-byte boundary (p.src itself need not be: a caller may hand in any float pointer);
+// everything else is gathered slot by slot
+__host__ __device__ inline bool gx_img_vector(const GxImg& p, long vo, int k0) {
+  return p.ks == 1 && !p.kg && k0 + 8 <= p.K && (reinterpret_cast<uintptr_t>(p.src + vo + k0) & 15) == 0;
+}
+
+// Tile (bx, by) of the workgroup with linear id lin = blockIdx.y * gx + blockIdx.x on a gx x gy grid.
+// XCD-aware order: the workgroups of one XCD (lin & 7) walk the tiles that share the LARGER operand's blocks back to
+// back, so that operand streams from HBM once and the smaller one is re-read from L2 / the Infinity Cache
+__host__ __device__ inline void gx_tile_of(unsigned lin, unsigned gx, unsigned gy, int row_major, int* bx, int* by) {
+  const unsigned total = gx * gy;
+  const unsigned xcd = lin & 7, idx = lin >> 3, per = total >> 3, rem = total & 7;
+  const unsigned L = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
+  if (row_major) {        // consecutive workgroups share the ROW tile: the larger operand is A (fc_o: 287 MB of weights)
+    *bx = (int)(L / gy);
+    *by = (int)(L - (unsigned)*bx * gy);
+  } else {
+    *by = (int)(L / gx);
+    *bx = (int)(L - (unsigned)*by * gx);
+  }
+}
+
 __global__ __launch_bounds__(256) void x6_image_kernel(GxImg p) {
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const int kbn = p.Kpad / 32;
@@ -62,8 +90,8 @@ __global__ __launch_bounds__(256) void x6_image_kernel(GxImg p) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) x[e] = 0.f;
   if (v < p.V) {
-    const long vo = p.vg ? (long)(v / p.vg) * p.vgs + (long)(v % p.vg) * p.vs : (long)v * p.vs;
-    if (p.ks == 1 && !p.kg && k0 + 8 <= p.K && ((vo + k0) & 3) == 0) {
+    const long vo = gx_img_vo(p, v);
+    if (gx_img_vector(p, vo, k0)) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(p.src + vo + k0);
       const f32x4 b = *reinterpret_cast<const f32x4*>(p.src + vo + k0 + 4);
       x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
@@ -99,22 +127,8 @@ __global__ __launch_bounds__(512, 1) void x6_gemm_kernel(GxArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wave_m = wave % GX_WM, wave_n = wave / GX_WM;
   const int i16 = lane & 15, g = lane >> 4;
-  // XCD-aware order: the workgroups of one XCD walk the tiles that share the LARGER operand's blocks back to back, so
-  // that operand streams from HBM once and the smaller one is re-read from L2 / the Infinity Cache
   int bx, by;
-  {
-    const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy;
-    const unsigned lin = blockIdx.y * gx + blockIdx.x;
-    const unsigned xcd = lin & 7, idx = lin >> 3, per = total >> 3, rem = total & 7;
-    const unsigned L = xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-    if (p.row_major) {        // consecutive workgroups share the ROW tile: the larger operand is A (fc_o: 287 MB of weights)
-      bx = (int)(L / gy);
-      by = (int)(L - (unsigned)bx * gy);
-    } else {
-      by = (int)(L / gx);
-      bx = (int)(L - (unsigned)by * gx);
-    }
-  }
+  gx_tile_of(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, p.row_major, &bx, &by);
   const int mb0 = bx * (GX_BM / 16), nb0 = by * (GX_BN / 16);
   const int nchunks = p.KB / CH;
 
@@ -244,17 +258,67 @@ extern "C" size_t buctd_x6_image_bytes(int V, int K, int role) {
   return (size_t)(pad_to(V, role == 0 ? GX_BM : GX_BN) / 16) * (pad_to(K, GX_KPAD) / 32) * 3072;
 }
 
-extern "C" int buctd_x6_image(const float* src, int V, int K, int vg, long vgs, long vs, int kg, long kgs, long ks, int role,
-                              void* image, void* stream) {
-  BUCTD_CHECK_ARG(src && image && V > 0 && K > 0 && (role == 0 || role == 1) && vg >= 0 && kg >= 0,
-                  "buctd_x6_image: bad argument");
+// the arguments of an image launch; the load-path query fills them the same way
+static GxImg gx_img_of(const float* src, int V, int K, int vg, long vgs, long vs, int kg, long kgs, long ks, int role, void* image) {
   GxImg p;
   p.src = src; p.out = (unsigned char*)image; p.V = V; p.K = K;
   p.Vpad = pad_to(V, role == 0 ? GX_BM : GX_BN); p.Kpad = pad_to(K, GX_KPAD);
   p.vg = vg; p.kg = kg; p.vgs = vgs; p.vs = vs; p.kgs = kgs; p.ks = ks;
+  return p;
+}
+
+// what a product of M x N x K launches: the grid, and the fields of GxArgs that follow from the sizes alone
+struct GxLaunch {
+  unsigned gx, gy;
+  int row_major, KB;
+};
+
+static GxLaunch gx_launch_of(int M, int N, int K) {
+  GxLaunch l;
+  l.KB = pad_to(K, GX_KPAD) / 32;
+  l.row_major = (size_t)pad_to(M, GX_BM) > (size_t)pad_to(N, GX_BN) ? 1 : 0;     // image bytes ~ V x Kpad
+  l.gx = pad_to(M, GX_BM) / GX_BM;
+  l.gy = pad_to(N, GX_BN) / GX_BN;
+  return l;
+}
+
+#define GX_IMAGE_ARGS_OK (V > 0 && K > 0 && (role == 0 || role == 1) && vg >= 0 && kg >= 0)
+
+extern "C" int buctd_x6_image(const float* src, int V, int K, int vg, long vgs, long vs, int kg, long kgs, long ks, int role,
+                              void* image, void* stream) {
+  BUCTD_CHECK_ARG(src && image && GX_IMAGE_ARGS_OK, "buctd_x6_image: bad argument");
+  const GxImg p = gx_img_of(src, V, K, vg, vgs, vs, kg, kgs, ks, role, image);
   const long lanes = (long)(p.Vpad / 16) * (p.Kpad / 32) * 64;
   hipLaunchKernelGGL(x6_image_kernel, dim3((unsigned)ceil_div(lanes, 256)), dim3(256), 0, (hipStream_t)stream, p);
   BUCTD_CHECK_LAUNCH("buctd_x6_image");
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_x6_image_path(const float* src, int V, int K, int vg, long vgs, long vs, int kg, long kgs, long ks, int role,
+                                   int v, int k0, int* vector) {
+  if (vector) *vector = 0;
+  BUCTD_CHECK_ARG(src && vector && GX_IMAGE_ARGS_OK, "buctd_x6_image_path: bad argument");
+  const GxImg p = gx_img_of(src, V, K, vg, vgs, vs, kg, kgs, ks, role, nullptr);
+  BUCTD_CHECK_ARG(v >= 0 && v < V && k0 >= 0 && k0 < p.Kpad && k0 % 8 == 0,
+                  "buctd_x6_image_path: v must be a row of the matrix and k0 the first slot of a lane (a multiple of 8 below Kpad)");
+  *vector = gx_img_vector(p, gx_img_vo(p, v), k0) ? 1 : 0;
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_x6_gemm_plan(int M, int N, int K, int* out) {
+  if (out) for (int i = 0; i < 8; ++i) out[i] = 0;
+  BUCTD_CHECK_ARG(out && M > 0 && N > 0 && K > 0, "buctd_x6_gemm_plan: bad argument");
+  const GxLaunch l = gx_launch_of(M, N, K);
+  const unsigned total = l.gx * l.gy;
+  out[0] = (int)l.gx; out[1] = (int)l.gy; out[2] = l.row_major; out[3] = l.KB; out[4] = l.KB / GX_CH;
+  out[5] = (int)total; out[6] = (int)(total >> 3); out[7] = (int)(total & 7);
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_x6_gemm_tile(int lin, int gx, int gy, int row_major, int* bx, int* by) {
+  BUCTD_CHECK_ARG(bx && by && gx > 0 && gy > 0 && lin >= 0 && (long)lin < (long)gx * gy && (row_major == 0 || row_major == 1),
+                  "buctd_x6_gemm_tile: bad argument");
+  gx_tile_of((unsigned)lin, (unsigned)gx, (unsigned)gy, row_major, bx, by);
   return BUCTD_OK;
 }
 
@@ -265,13 +329,13 @@ extern "C" int buctd_x6_gemm(int M, int N, int K, const void* a_image, const voi
   if (Nc <= 0) Nc = N;
   static unsigned char attr_done[BUCTD_MAX_DEVICES] = {0};
   if (const int rc = buctd_raise_lds_limit(reinterpret_cast<const void*>(x6_gemm_kernel), 2 * GX_ABUF, attr_done, "buctd_x6_gemm")) return rc;
+  const GxLaunch l = gx_launch_of(M, N, K);
   GxArgs p;
   p.a = (const unsigned char*)a_image; p.b = (const unsigned char*)b_image; p.c = C; p.bias = bias;
-  p.M = M; p.N = N; p.KB = pad_to(K, GX_KPAD) / 32; p.ldc = ldc; p.gsc = gsc; p.Nc = Nc; p.alpha = alpha;
+  p.M = M; p.N = N; p.KB = l.KB; p.ldc = ldc; p.gsc = gsc; p.Nc = Nc; p.alpha = alpha;
   p.bias_axis = bias_axis;
-  p.row_major = (size_t)pad_to(M, GX_BM) > (size_t)pad_to(N, GX_BN) ? 1 : 0;     // image bytes ~ V x Kpad
-  dim3 grid(pad_to(M, GX_BM) / GX_BM, pad_to(N, GX_BN) / GX_BN);
-  hipLaunchKernelGGL(x6_gemm_kernel, grid, dim3(512), 2 * GX_ABUF, (hipStream_t)stream, p);
+  p.row_major = l.row_major;
+  hipLaunchKernelGGL(x6_gemm_kernel, dim3(l.gx, l.gy), dim3(512), 2 * GX_ABUF, (hipStream_t)stream, p);
   BUCTD_CHECK_LAUNCH("buctd_x6_gemm");
   return BUCTD_OK;
 }

@@ -633,6 +633,19 @@ int buctd_x6_image(const float* src, int V, int K, int vg, long vgs, long vs, in
                    void* image, void* stream);
 int buctd_x6_gemm(int M, int N, int K, const void* a_image, const void* b_image, const float* bias, int bias_axis,
                   float alpha, float* C, long ldc, int Nc, long gsc, void* stream);
+/* Host-only queries, no launch; each runs the code the launch itself runs.
+ * buctd_x6_gemm_plan: what buctd_x6_gemm launches for M x N x K: out[8] = grid x (row tiles of 128), grid y (column tiles of
+ *   192), row_major (1: consecutive workgroups of an XCD share the row tile), KB (32-slot steps of the padded K), chunks
+ *   (KB / 2), total workgroups, total >> 3, total & 7.
+ * buctd_x6_gemm_tile: the tile (bx, by) that the workgroup with linear id lin = blockIdx.y * gx + blockIdx.x computes on a
+ *   gx x gy grid in the given order - the function the kernel calls.
+ * buctd_x6_image_path: *vector = 1 where the lane of buctd_x6_image that holds row v, slots k0 .. k0 + 7 (k0 a multiple of
+ *   8) reads them with two 16-byte loads, 0 where it gathers them one by one.  src is the pointer of the image call (the
+ *   answer depends on its alignment); it is not dereferenced. */
+int buctd_x6_gemm_plan(int M, int N, int K, int* out);
+int buctd_x6_gemm_tile(int lin, int gx, int gy, int row_major, int* bx, int* by);
+int buctd_x6_image_path(const float* src, int V, int K, int vg, long vgs, long vs, int kg, long kgs, long ks, int role,
+                        int v, int k0, int* vector);
 
 /* -------------------------------------------------------------- optimizer --- */
 /* torch.optim.Adam step (utils/utils.py:268-272: betas .9/.999, eps 1e-8, no weight decay, no amsgrad)

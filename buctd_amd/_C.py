@@ -228,6 +228,7 @@ SIGNATURES = {
     "buctd_conv3x3_bf16x6_group": (_I, [_I, C.POINTER(C3Conv), _P]),
     "buctd_conv3x3_bf16x6_group_eval": (_I, [_I, C.POINTER(C3ConvEval), _P]),
     "buctd_conv3x3_bf16x6_group_workgroups": (_I, [_I, C.POINTER(C3Conv)]),
+    "buctd_conv3x3_bf16x6_group_plan": (_I, [_I, C.POINTER(C3Conv), C.POINTER(C.c_int)]),     # out[30]
     "buctd_conv3x3_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "buctd_conv3x3_wgrad_bf16x6_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "buctd_gconv_wgrad_x6_supported": (_I, [_I] * 6),
@@ -239,6 +240,7 @@ SIGNATURES = {
     "buctd_conv3x3_wgrad_bf16x6_group_workspace": (_SZ, [_I] * 6),
     "buctd_conv3x3_wgrad_bf16x6_group": (_I, [_I, C.POINTER(Wg3Conv), _P]),
     "buctd_conv3x3_wgrad_bf16x6_group_workgroups": (_I, [_I, C.POINTER(Wg3Conv)]),
+    "buctd_conv3x3_wgrad_bf16x6_group_plan": (_I, [_I, C.POINTER(Wg3Conv), C.POINTER(C.c_int)]),  # out[34]
     "buctd_stream_fork": (_I, [_P, _P]),
     "buctd_basic_branches_fwd_train": (_I, [_I, _I, C.POINTER(BasicBlockDesc), _P]),
     "buctd_basic_branches_bwd": (_I, [_I, _I, C.POINTER(BasicBlockDesc), C.POINTER(BasicBlockGrads), _P, _P]),

@@ -864,8 +864,15 @@ static int c3_group_variant(const C3Plan& pl, int* fam, bool general = false) {
 }
 
 // what a launch would run, for the no-launch queries: kernel 0 = conv3x3_x6_kernel (c3_dispatch), 1 = a group / train-mode
-// kernel with its family and the variant of the first member in launch order; wgs = its grid
-struct C3Dry { int kernel, fam, variant, wgs; };
+// kernel with its family and the variant of the first member in launch order; wgs = its grid.  For kernel 1 also the rest of
+// the launch: the train-mode option set (-1: the general group kernel), the dynamic LDS size, and per member in launch order
+// its index in the call and what the kernel's descriptor (C3Group) holds for it
+struct C3Dry {
+  int kernel, fam, variant, wgs;
+  int lean, n;
+  size_t lds;
+  int member[C3G_MAX], var[C3G_MAX], gx[C3G_MAX], gy[C3G_MAX], tiles[C3G_MAX], col_major[C3G_MAX];
+};
 
 // n convolutions (argument blocks a[], tile plans pl[]) as ONE launch: the train-mode kernel of their common option set, else
 // the general group kernel (n > 1 only).  *done = false: the tile shapes have no common kernel family - nothing was launched.
@@ -914,7 +921,14 @@ static int c3_group_launch(int n, const C3Args* a, const C3Plan* pl, hipStream_t
   for (int i = n; i < C3G_MAX; ++i) h.tiles[i] = h.gx[i] = h.gy[i] = h.variant[i] = 0;
   if (lds > 160 * 1024) return BUCTD_OK;
   *done = true;
-  if (dry) { *dry = C3Dry{1, fam, h.variant[0], (int)(per_xcd * 8)}; return BUCTD_OK; }
+  if (dry) {
+    *dry = C3Dry{1, fam, h.variant[0], (int)(per_xcd * 8), lean, n, lds};
+    for (int i = 0; i < n; ++i) {
+      dry->member[i] = order[i]; dry->var[i] = h.variant[i]; dry->gx[i] = h.gx[i]; dry->gy[i] = h.gy[i];
+      dry->tiles[i] = h.tiles[i]; dry->col_major[i] = h.conv[i].col_major;
+    }
+    return BUCTD_OK;
+  }
   if (lean >= 0) return c3_lean_launch(h, fam, lean, per_xcd * 8, lds, stream);
   static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
   void (*fn)(C3Group) = fam ? conv3x3_x6_group_kernel<1> : conv3x3_x6_group_kernel<0>;
@@ -1077,6 +1091,32 @@ extern "C" int buctd_conv3x3_bf16x6_group_workgroups(int n, const buctd_c3_conv*
   const int rc = c3_group_launch(n, a, pl, nullptr, &done, &dry);
   if (rc) return rc;
   return done ? dry.wgs : 0;
+}
+
+/* What buctd_conv3x3_bf16x6_group(n, convs) would launch (no launch, nothing is read through the tensor pointers - they only
+ * have to be set as in the call, since which of them are set decides the option set).  An entry without any train-mode option
+ * (no stats_acc, in_bn, residual, relu, bn_acc) is what buctd_conv3x3_bf16x6_group_eval makes of its entries, whatever their
+ * scale / shift / residual / relu: n > 1 such entries give the plan of that call.  The answer is the descriptor
+ * c3_group_launch hands to the kernel.  out[BUCTD_C3_GROUP_PLAN_INTS]: see include/buctd_hip.h. */
+extern "C" int buctd_conv3x3_bf16x6_group_plan(int n, const buctd_c3_conv* convs, int* out) {
+  BUCTD_CHECK_ARG(n > 0 && n <= C3G_MAX && convs && out, "buctd_conv3x3_bf16x6_group_plan: 1..%d convolutions", C3G_MAX);
+  C3Args a[C3G_MAX];
+  C3Plan pl[C3G_MAX];
+  if (const int rc0 = c3_group_fill(n, convs, a, pl)) return rc0;
+  bool done = false;
+  C3Dry dry{};
+  const int rc = c3_group_launch(n, a, pl, nullptr, &done, &dry);
+  if (rc) return rc;
+  for (int i = 0; i < BUCTD_C3_GROUP_PLAN_INTS; ++i) out[i] = -1;
+  out[0] = done ? 1 : 0;
+  out[5] = n;
+  if (!done) return BUCTD_OK;
+  out[1] = dry.lean; out[2] = dry.fam; out[3] = dry.wgs; out[4] = (int)dry.lds;
+  for (int i = 0; i < n; ++i) {
+    const int v[6] = {dry.member[i], dry.var[i], dry.gx[i], dry.gy[i], dry.tiles[i], dry.col_major[i]};
+    for (int j = 0; j < 6; ++j) out[6 + 6 * i + j] = v[j];
+  }
+  return BUCTD_OK;
 }
 
 /* Which tile plan and which kernel buctd_conv3x3_bf16x6* / _acc / _bnstat_acc would run for this shape with the train-mode

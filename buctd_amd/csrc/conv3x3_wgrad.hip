@@ -508,13 +508,14 @@ static int wg3_launch(const WG3Args& a, const WG3Plan& pl, hipStream_t st) {
 struct WG3InBn { const float* mean; const float* invstd; const float* gamma; const float* beta; int relu; };
 
 // argument block + plan of one weight gradient (no launch); target: see wg3_plan
+// dry: for the no-launch query (buctd_conv3x3_wgrad_bf16x6_group_plan) - tensors and workspace need not be there
 static int wg3_fill(int np, int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw, void* workspace,
-                    size_t workspace_bytes, const WG3InBn* x_bn, int target, WG3Args& a, WG3Plan& pl) {
-  BUCTD_CHECK_ARG(x && dy && dw, "buctd_conv3x3_wgrad (split bf16): null tensor pointer");
+                    size_t workspace_bytes, const WG3InBn* x_bn, int target, WG3Args& a, WG3Plan& pl, bool dry = false) {
+  BUCTD_CHECK_ARG(dry || (x && dy && dw), "buctd_conv3x3_wgrad (split bf16): null tensor pointer");
   BUCTD_CHECK_ARG(wg3_plan(np, N, H, W, Ci, Co, &pl, target),
                   "buctd_conv3x3_wgrad (split bf16): unsupported shape N%d H%d W%d Ci%d Co%d", N, H, W, Ci, Co);
   const size_t need = wg3_ws_bytes(pl, Ci, Co);
-  if (!workspace || workspace_bytes < need) {
+  if (!dry && (!workspace || workspace_bytes < need)) {
     buctd_set_error("buctd_conv3x3_wgrad (split bf16): workspace %zu bytes < required %zu", workspace_bytes, need);
     return BUCTD_EWORKSPACE;
   }
@@ -576,16 +577,9 @@ extern "C" size_t buctd_conv3x3_wgrad_bf16x6_group_workspace(int n, int N, int H
   return wg3_ws_bytes(pl, Ci, Co);
 }
 
-extern "C" int buctd_conv3x3_wgrad_bf16x6_group(int n, const buctd_wg3_conv* convs, void* stream) {
-  BUCTD_CHECK_ARG(n > 0 && n <= WG3G_MAX && convs, "buctd_conv3x3_wgrad_bf16x6_group: 1..%d convolutions", WG3G_MAX);
-  if (n == 1) {
-    const buctd_wg3_conv& c = convs[0];
-    WG3InBn b{c.x_mean, c.x_invstd, c.x_gamma, c.x_beta, c.x_relu};
-    return wg3_run(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.dy, c.dw, c.accumulate, c.workspace, c.workspace_bytes, stream, &b);
-  }
-  WG3Group g;
-  WG3RedGroup r;
-  WG3Plan pl[WG3G_MAX];
+// the descriptors of the group launch and of its reduction (n > 1), with the members' plans and the LDS size: all the launch
+// needs, and all buctd_conv3x3_wgrad_bf16x6_group_plan reports (dry: no tensors, no workspace)
+static int wg3_group_fill(int n, const buctd_wg3_conv* convs, WG3Group& g, WG3RedGroup& r, WG3Plan* pl, size_t* lds_out, bool dry) {
   g.n = r.n = n;
   g.first[0] = r.first[0] = 0;
   size_t lds = 0;
@@ -593,7 +587,7 @@ extern "C" int buctd_conv3x3_wgrad_bf16x6_group(int n, const buctd_wg3_conv* con
   for (int k = 0; k < n; ++k) {
     const buctd_wg3_conv& c = convs[k];
     WG3InBn b{c.x_mean, c.x_invstd, c.x_gamma, c.x_beta, c.x_relu};
-    const int rc = wg3_fill(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.dy, c.dw, c.workspace, c.workspace_bytes, &b, target, g.conv[k], pl[k]);
+    const int rc = wg3_fill(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.dy, c.dw, c.workspace, c.workspace_bytes, &b, target, g.conv[k], pl[k], dry);
     if (rc) return rc;
     BUCTD_CHECK_ARG(pl[k].CF == pl[0].CF, "buctd_conv3x3_wgrad_bf16x6_group: the convolutions must share the chunk width (48 or 32 channels)");
     const int ch = pl[k].CF * 16;
@@ -606,6 +600,22 @@ extern "C" int buctd_conv3x3_wgrad_bf16x6_group(int n, const buctd_wg3_conv* con
     if (pl[k].lds > lds) lds = pl[k].lds;
   }
   for (int k = n; k < WG3G_MAX; ++k) { g.first[k + 1] = g.first[n]; r.first[k + 1] = r.first[n]; g.ncx[k] = g.ncy[k] = g.nsplit[k] = 0; }
+  *lds_out = lds;
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_conv3x3_wgrad_bf16x6_group(int n, const buctd_wg3_conv* convs, void* stream) {
+  BUCTD_CHECK_ARG(n > 0 && n <= WG3G_MAX && convs, "buctd_conv3x3_wgrad_bf16x6_group: 1..%d convolutions", WG3G_MAX);
+  if (n == 1) {
+    const buctd_wg3_conv& c = convs[0];
+    WG3InBn b{c.x_mean, c.x_invstd, c.x_gamma, c.x_beta, c.x_relu};
+    return wg3_run(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.dy, c.dw, c.accumulate, c.workspace, c.workspace_bytes, stream, &b);
+  }
+  WG3Group g;
+  WG3RedGroup r;
+  WG3Plan pl[WG3G_MAX];
+  size_t lds = 0;
+  if (const int rc = wg3_group_fill(n, convs, g, r, pl, &lds, false)) return rc;
   hipStream_t st = (hipStream_t)stream;
   static unsigned char attr_done[2][BUCTD_MAX_DEVICES] = {{0}};
   const int cf = pl[0].CF;
@@ -635,6 +645,37 @@ extern "C" int buctd_conv3x3_wgrad_bf16x6_group_workgroups(int n, const buctd_wg
     total += (long)(c.Co / ch) * ((c.Ci + ch - 1) / ch) * pl.nsplit;
   }
   return (int)total;
+}
+
+/* What buctd_conv3x3_wgrad_bf16x6_group(n, convs) would launch (no launch; tensors and workspaces may be NULL): per member
+ * out[8 k ..] = CF, nsplit, q, rem, first workgroup, chunk pairs (ncx * ncy), first chunk pair of the reduction, slab bytes
+ * of the member's workspace; out[32] = workgroups of the launch, out[33] = LDS bytes.  n == 1 is the single launch's plan
+ * (buctd_conv3x3_wgrad_bf16x6_plan).  From the descriptors the launch itself builds. */
+extern "C" int buctd_conv3x3_wgrad_bf16x6_group_plan(int n, const buctd_wg3_conv* convs, int* out) {
+  BUCTD_CHECK_ARG(n > 0 && n <= WG3G_MAX && convs && out, "buctd_conv3x3_wgrad_bf16x6_group_plan: 1..%d convolutions", WG3G_MAX);
+  for (int i = 0; i < BUCTD_WG3_GROUP_PLAN_INTS; ++i) out[i] = -1;
+  WG3Group g;
+  WG3RedGroup r;
+  WG3Plan pl[WG3G_MAX];
+  size_t lds = 0;
+  if (n == 1) {       // as buctd_conv3x3_wgrad_bf16x6_group: the single launch (wg3_run), split for the whole chip
+    const buctd_wg3_conv& c = convs[0];
+    WG3InBn b{c.x_mean, c.x_invstd, c.x_gamma, c.x_beta, c.x_relu};
+    if (const int rc = wg3_fill(3, c.N, c.H, c.W, c.Ci, c.Co, c.x, c.dy, c.dw, c.workspace, c.workspace_bytes, &b, 0, g.conv[0], pl[0], true))
+      return rc;
+    const int ch = pl[0].CF * 16;
+    g.ncx[0] = c.Co / ch; g.ncy[0] = (c.Ci + ch - 1) / ch;
+    g.first[0] = r.first[0] = 0;
+    g.first[1] = (unsigned)(g.ncx[0] * g.ncy[0] * pl[0].nsplit); r.first[1] = (unsigned)(g.ncx[0] * g.ncy[0]);
+    lds = pl[0].lds;
+  } else if (const int rc = wg3_group_fill(n, convs, g, r, pl, &lds, true)) return rc;
+  for (int k = 0; k < n; ++k) {
+    const int v[8] = {pl[k].CF, pl[k].nsplit, pl[k].q, pl[k].rem, (int)g.first[k], g.ncx[k] * g.ncy[k], (int)r.first[k],
+                      (int)wg3_ws_bytes(pl[k], convs[k].Ci, convs[k].Co)};
+    for (int j = 0; j < 8; ++j) out[8 * k + j] = v[j];
+  }
+  out[32] = (int)g.first[n]; out[33] = (int)lds;
+  return BUCTD_OK;
 }
 
 static size_t wg3_workspace(int np, int N, int H, int W, int Ci, int Co) {

@@ -168,6 +168,16 @@ int buctd_conv3x3_bf16x6_group_eval(int n, const buctd_c3_conv_eval* convs, void
 /* The number of workgroups buctd_conv3x3_bf16x6_group(n, convs) launches as ONE kernel (0: the members share no kernel and go
  * out one launch each; < 0: error).  No launch - for tools that find a launch in a kernel trace by its grid (bench.py). */
 int buctd_conv3x3_bf16x6_group_workgroups(int n, const buctd_c3_conv* convs);
+/* What buctd_conv3x3_bf16x6_group(n, convs) would launch (host code only, no launch; the answer is the descriptor the launch
+ * hands to its kernel).  Nothing is read through the tensor pointers; x, wprep and y must be non-NULL and the optional ones set
+ * as in the call, since which of them are set decides the option set.  Entries with none of stats_acc / in_bn / residual /
+ * relu / bn_acc are what buctd_conv3x3_bf16x6_group_eval makes of its entries: n > 1 of them give the plan of that call.
+ * out[BUCTD_C3_GROUP_PLAN_INTS]: [0] 1 = one kernel, 0 = one launch per member (then all that follows but [5] is -1);
+ * [1] the train-mode option set (C3M_* mask), -1 = the general group kernel; [2] kernel family; [3] grid (workgroups);
+ * [4] dynamic LDS bytes; [5] n; then per member IN LAUNCH ORDER (costliest tile first) six values from [6 + 6 i]: its index in
+ * convs, variant (index into the family's tile table), gx (position tiles), gy (column tiles), tiles = gx * gy, col_major. */
+#define BUCTD_C3_GROUP_PLAN_INTS 30
+int buctd_conv3x3_bf16x6_group_plan(int n, const buctd_c3_conv* convs, int* out);
 /* Which tile plan and which kernel a bf16x6 launch of this shape takes (host code only, no launch; computed by the functions
  * the launch itself goes through, so the answer cannot drift from it).  option_set: the train-mode option set of the launch
  * as the C3M_* mask of csrc/c3_lean.h - 2 STATS (_acc with stats_acc), 3 STATS | IN_BN (+ in_bn), 8 BS_REBUILD (_bnstat_acc,
@@ -233,6 +243,13 @@ size_t buctd_conv3x3_wgrad_bf16x6_group_workspace(int n, int N, int H, int W, in
 int buctd_conv3x3_wgrad_bf16x6_group(int n, const buctd_wg3_conv* convs, void* stream);
 /* workgroups of the weight-gradient kernel that call launches (no launch; tools that search a kernel trace by grid: bench.py) */
 int buctd_conv3x3_wgrad_bf16x6_group_workgroups(int n, const buctd_wg3_conv* convs);
+/* What that call would launch (host code only, no launch; tensors and workspaces may be NULL; from the descriptors the launch
+ * builds).  out[BUCTD_WG3_GROUP_PLAN_INTS]: per member eight values from [8 k]: CF, nsplit, q, rem (as
+ * buctd_conv3x3_wgrad_bf16x6_plan, for the member's share of the group), its first workgroup, its chunk pairs, its first chunk
+ * pair in the reduction launch, the bytes of its workspace the launch writes; unused members -1.  [32] workgroups of the
+ * launch, [33] dynamic LDS bytes.  Mixed chunk widths: BUCTD_EINVAL, as the launch. */
+#define BUCTD_WG3_GROUP_PLAN_INTS 34
+int buctd_conv3x3_wgrad_bf16x6_group_plan(int n, const buctd_wg3_conv* convs, int* out);
 int buctd_conv3x3_wgrad_bf16x3_supported(int N, int H, int W, int Ci, int Co);
 size_t buctd_conv3x3_wgrad_bf16x3_workspace(int N, int H, int W, int Ci, int Co);
 int buctd_conv3x3_wgrad_bf16x3(int N, int H, int W, int Ci, int Co, const float* x, const float* dy, float* dw,

@@ -12,6 +12,7 @@ import re
 import pytest
 
 from tests.helpers import c3_cases as T
+from tests.helpers import c3_group_cases as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "buctd_amd", "csrc")
@@ -88,21 +89,14 @@ def source_instances():
     return inst, tabs
 
 
-# instances that no single launch reaches from any grid shape, and why.  The only place where cases are left out.
+# instances that no launch reaches from any grid shape, and why.  The only place where cases are left out.  (What only a group
+# launch reaches - the 128 x 32 and 64 x 32 tiles as family-1 members, the 48-column tiles of the eval-mode group kernel - is
+# reached by the group table, tests/helpers/c3_group_cases.py.)
 UNREACHED = {
     ("x6", 8, 3, 2, 2): "dead: c3_plan takes the single-buffer tiles (MF = 7 / 8) only with wn == 1",
     ("x6", 1, 3, 2, 2): "dead: 2x2 waves with NF = 3 need >= 200 tiles of 128 positions per 96 columns (else the 32-column "
                         "tiles take over), and then MF = 2 always finds its 224 workgroups",
 }
-for _m in LEAN_SETS:
-    UNREACHED[("lean", _m, 1, 0)] = "128 x 32 tile: family 0 (searched first) has it as variant 4; only a group launch of " \
-                                    "family-1 members takes this entry"
-    UNREACHED[("lean", _m, 1, 2)] = "64 x 32 tile: family 0 has it as variant 2; only a group launch of family-1 members " \
-                                    "takes this entry"
-for _v in (6, 7):
-    UNREACHED[("group", 1, _v)] = "48-column tiles of the eval-mode group kernel (buctd_conv3x3_bf16x6_group_eval with " \
-                                  "n > 1); no single launch and no train-mode kernel has them"
-
 
 def reached_instances(conv):
     got = set()
@@ -170,8 +164,12 @@ def test_every_kernel_instance_is_reached_or_listed(grid_keys):
         for (kernel, MF, NF, WM, WN, single, col, fam, var) in keys:
             if kernel == 1:
                 assert tabs[fam][var] == (MF, NF, WM, WN), (m, fam, var)
-    unlisted = sorted(inst - got - set(UNREACHED))
-    assert not unlisted, f"kernel instances that no grid shape reaches and UNREACHED does not explain: {unlisted}"
+    groups = G.reached_instances()
+    assert groups <= inst | {("group", f, v) for f in tabs for v in range(len(tabs[f]))}, \
+        f"the group query reports kernels the source does not have: {sorted(groups - inst)}"
+    unlisted = sorted(inst - got - groups - set(UNREACHED))
+    assert not unlisted, f"kernel instances that neither a grid shape nor a group of the table reaches and UNREACHED does not explain: {unlisted}"
+    assert len(UNREACHED) == 2 and all(k[0] == "x6" for k in UNREACHED), "UNREACHED holds the two dead x6 instances only"
     stale = sorted(set(UNREACHED) & got)
     assert not stale, f"UNREACHED lists instances the grid search does reach: {stale}"
     assert set(UNREACHED) <= inst, f"UNREACHED lists instances the source does not have: {sorted(set(UNREACHED) - inst)}"

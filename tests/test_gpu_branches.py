@@ -36,6 +36,11 @@ def _make_chains(dev, shapes, n, seed):
     [(2, 16, 12, 32), (2, 8, 6, 64), (2, 4, 3, 128)],
     [(32, 96, 72, 48), (32, 48, 36, 96), (32, 24, 18, 192), (32, 12, 9, 384)],
 ], ids=["w48x2", "w48x4", "w32x3", "w48_full"])
+# Which of these really run a train-mode GROUP kernel (tests/test_conv3x3_group_cover.py asserts it by name, from
+# buctd_conv3x3_bf16x6_group_plan): w32x3 and w48_full do (as does the unused-branch test below).  w48x2, w48x4 and the module
+# test do not - their branch 0 plans MF = 1, NF = 3, a tile the train-mode tables lack, so the group entry point launches every
+# member on its own and "bit-identical to the chains" compares the same launches on both sides for the convolutions (the
+# BatchNorm and weight-gradient group launches still run).  The group kernels themselves: tests/test_gpu_conv3x3_groups.py.
 def test_branches_node_equals_chains(dev, shapes):
     """Forward outputs, running statistics, input gradients and BatchNorm gradients: the same element arithmetic in the same
     order per tile -> bit-identical.  Weight gradients: the group launch cuts every convolution into fewer position splits

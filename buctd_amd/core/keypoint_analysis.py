@@ -53,7 +53,8 @@ def _ranks(key):
 
 class CrowdingAnalysis:
     """See the module's docstring.  `evaluator` is a KeypointEvaluator: its ground-truth tables, sigmas, suppression
-    settings, detection limit and device are used, and it is left as it was.  num_overlaps / valid / bin_of_gt are per
+    settings (suppression='soft' included: the persons analysed are the ones its soft OKS NMS selects), detection limit
+    and device are used, and it is left as it was.  num_overlaps / valid / bin_of_gt are per
     annotation in evaluator.gt_ids order: valid as check_valid_annotations decides it, num_overlaps the stored count
     of an annotation that carries one, otherwise the number of other valid annotations of the image whose box IoU is
     > iou_for_overlap (-1 where not valid), bin_of_gt = overlap group * len(num_kpt_groups) + key point group, -1 for

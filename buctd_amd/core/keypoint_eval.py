@@ -3,8 +3,8 @@ step the reference's data set classes implement in `evaluate` with Python loops 
 pycocotools.COCOeval (lib/dataset/dataloader.py:538-735).  No pycocotools object is involved.
 
 What runs where
-  device (csrc/keypoint_eval.hip, fp64): rescoring, OKS NMS grouped by image, the per-image OKS matrices and the
-      3 x 10 greedy matchings of COCOeval.evaluateImg;
+  device (csrc/keypoint_eval.hip, fp64): rescoring, OKS NMS (hard or soft) grouped by image, the per-image OKS
+      matrices and the 3 x 10 greedy matchings of COCOeval.evaluateImg;
   host: grouping persons by image, the results JSON, and the accumulation over the small match tables (numpy, fp64).
 
 A data set class opts in by delegating:
@@ -83,17 +83,25 @@ class KeypointEvaluator:
     image_id, id; one category).  sigmas: per-joint OKS sigmas of the evaluation (default nms.COCO_SIGMAS);
     nms_sigmas: those of the suppression (the reference passes joints_weight / 10, dataloader.py:614-625; default: sigmas).
     use_nms=False is the BUCTD setting `keep = []`: every person is kept.  nms_in_vis_thre: joint-score threshold inside
-    the suppression's OKS (the reference passes none).  img_path entries are mapped to image ids through `image_ids`, a
+    the suppression's OKS (the reference passes none).  suppression='soft' is TEST.SOFT_NMS: soft_oks_nms instead of
+    oks_nms (dataloader.py:614-625) - at most max_dets persons per image are chosen by decayed scores (`tables` gains
+    soft_rank / soft_score per input row); the scores that are written and matched stay the rescored ones.  img_path entries are mapped to image ids through `image_ids`, a
     dict or callable path -> id; by default the dict {join(image_dir, file_name): id} of gt['images'].
     `tables` holds what the last call produced."""
 
     def __init__(self, gt, sigmas=None, nms_sigmas=None, oks_thre=0.5, in_vis_thre=0.0, use_nms=True, max_dets=20,
                  device=None, *, image_dir='', image_ids=None, soft_nms=False, nms_in_vis_thre=None, mode='val',
-                 category_id=1):
+                 category_id=1, suppression='hard'):
         import torch
         from ..nms.nms import COCO_SIGMAS
         if soft_nms:
-            raise NotImplementedError("soft OKS NMS stays on the host path (nms.soft_oks_nms); the evaluator does not run it")
+            raise NotImplementedError("soft_nms is not an option of the evaluator: pass suppression='soft' for the "
+                                      "device's soft OKS NMS (nms.soft_oks_nms is the host form)")
+        if suppression not in ('hard', 'soft'):
+            raise ValueError(f"suppression is 'hard' or 'soft', not {suppression!r}")
+        if suppression == 'soft' and not use_nms:
+            raise ValueError("suppression='soft' needs use_nms=True: without the suppression every person is kept")
+        self.suppression = suppression
         self.sigmas = np.asarray(COCO_SIGMAS if sigmas is None else sigmas, dtype=np.float64).reshape(-1)
         self.nms_sigmas = self.sigmas if nms_sigmas is None else np.asarray(nms_sigmas, dtype=np.float64).reshape(-1)
         self.K = self.sigmas.shape[0]
@@ -189,19 +197,30 @@ class KeypointEvaluator:
             kp_s = preds_t[order].contiguous()
             # 2. OKS NMS within every image
             keep_s = torch.ones(N, dtype=torch.int32, device=dev)
+            soft = {}
             if self.use_nms and N:
                 off_t = torch.as_tensor(offsets).to(dev)
                 area_s = area_t[order].contiguous()
-                use_vis = self.nms_in_vis_thre is not None
-                check(lib().buctd_oks_nms_grouped(ptr(off_t), I, int(counts.max()), ptr(kp_s), ptr(area_s),
-                                                  ptr(d['nms_sigmas']), K, self.oks_thre, int(use_vis),
-                                                  float(self.nms_in_vis_thre) if use_vis else 0.0, ptr(keep_s), st),
-                      "oks_nms_grouped")
+                if self.suppression == 'soft':
+                    # the decayed scores choose the persons and nothing else: the reference takes indices only
+                    from ..nms.nms import soft_oks_nms_grouped
+                    rank_s, soft_s = soft_oks_nms_grouped(off_t, kp_s, area_s, score[order], d['nms_sigmas'], self.oks_thre,
+                                                          in_vis_thre=self.nms_in_vis_thre, max_keep=self.max_dets)
+                    keep_s = (rank_s >= 0).to(torch.int32)
+                    soft = dict(soft_rank_s=rank_s.cpu().numpy(), soft_score_s=soft_s.cpu().numpy())
+                else:
+                    use_vis = self.nms_in_vis_thre is not None
+                    check(lib().buctd_oks_nms_grouped(ptr(off_t), I, int(counts.max()), ptr(kp_s), ptr(area_s),
+                                                      ptr(d['nms_sigmas']), K, self.oks_thre, int(use_vis),
+                                                      float(self.nms_in_vis_thre) if use_vis else 0.0, ptr(keep_s), st),
+                          "oks_nms_grouped")
+            elif self.suppression == 'soft':
+                soft = dict(soft_rank_s=np.zeros(0, dtype=np.int32), soft_score_s=np.zeros(0))
             order_h = order.cpu().numpy()
             keep_h = keep_s.cpu().numpy().astype(bool)
             return dict(preds=preds, all_boxes=all_boxes, person_image_id=person_image_id, img=img, order_h=order_h,
                         keep_h=keep_h, offsets=offsets, counts=counts, kp_s=kp_s, score_h=score.cpu().numpy(),
-                        box_score_h=box_score.cpu().numpy(), kpt_score_h=kpt_score.cpu().numpy())
+                        box_score_h=box_score.cpu().numpy(), kpt_score_h=kpt_score.cpu().numpy(), **soft)
 
     def _match(self, dt_kpts, dt_counts, gt_counts, gt=None):
         """Step 3 of evaluate(), shared with core.keypoint_analysis: the OKS matrices and the A x T greedy matchings of
@@ -270,6 +289,10 @@ class KeypointEvaluator:
             oks=[oks_h[oks_offsets[i]:oks_offsets[i + 1]].reshape(int(dt_counts[i]), int(self.gt_counts[i]))
                  for i in range(I)],
             dt_matched=dtm_h, dt_ignored=dti_h, precision=precision, recall=recall, stats=stats)
+        if self.suppression == 'soft':                      # per input row: the round a person was taken in, its live score
+            soft_rank, soft_score = np.full(N, -1, dtype=np.int32), np.zeros(N)
+            soft_rank[order_h], soft_score[order_h] = p['soft_rank_s'], p['soft_score_s']
+            self.tables.update(soft_rank=soft_rank, soft_score=soft_score)
         if output_dir:
             self._write_results(cfg, output_dir, epoch, preds, all_boxes, img_path, person_image_id)
         name_value = OrderedDict(zip(STATS_NAMES, stats))

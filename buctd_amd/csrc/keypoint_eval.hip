@@ -1,5 +1,5 @@
-// Keypoint evaluation on the device (core/keypoint_eval.py): the rescoring and grouped OKS NMS of the reference's
-// data set classes (lib/dataset/dataloader.py:590-634 around lib/nms/nms.py:75-124) and the per-image part of the
+// Keypoint evaluation on the device (core/keypoint_eval.py): the rescoring and grouped OKS NMS, hard and soft, of the
+// reference's data set classes (lib/dataset/dataloader.py:590-634 around lib/nms/nms.py:75-200) and the per-image part of the
 // published COCO keypoint evaluation (computeOks + evaluateImg).  Everything is fp64: a match is a comparison against
 // a threshold, and the data is a few MB.  The crowding analysis (core/keypoint_analysis.py, the reference's
 // lib/analysis/evaluation.py) adds the overlap count per ground truth and a per-segment accumulate + summarize.
@@ -88,6 +88,56 @@ __global__ __launch_bounds__(64) void oks_nms_grouped_kernel(int K, int cap_word
     }
   }
   for (int p = lane; p < n_all; p += 64) keep[base + p] = p < n ? (int)((alive[p >> 6] >> (p & 63)) & 1ull) : 0;
+}
+
+// Soft suppression (soft_oks_nms / rescore of nms/nms.py:150-200), one wavefront per image; persons [off[i], off[i+1])
+// in the caller's grouped order.  min(n, max_keep) rounds: the head of a round is the untaken person with the largest
+// live score (equal scores: the lowest position), every other untaken person's live score is multiplied by the decay of
+// its OKS to the head.  The live scores sit in soft_score and rank >= 0 marks a taken person, so n has no bound.  Lane l
+// alone reads and writes positions l, l + 64, ... of both arrays (the head's rank is written by the lane that owns it):
+// no LDS, no barrier, no atomics.  A latency kernel like the others of this file; not tuned.
+__global__ __launch_bounds__(64) void soft_oks_nms_grouped_kernel(int K, double thresh, int decay_type, int use_vis,
+                                                                  double in_vis_thre, int max_keep,
+                                                                  const int* __restrict__ off, const float* __restrict__ kpts,
+                                                                  const double* __restrict__ areas,
+                                                                  const double* __restrict__ scores,
+                                                                  const double* __restrict__ sigmas, double* soft_score,
+                                                                  int* rank) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int base = off[img];
+  const int n = off[img + 1] - base;
+  double best = 0.0;
+  int best_p = -1;                                                  // this lane's best untaken (score, position)
+  for (int p = lane; p < n; p += 64) {
+    const double s = scores[base + p];
+    soft_score[base + p] = s;
+    rank[base + p] = -1;
+    if (best_p < 0 || s > best) { best = s; best_p = p; }           // ascending p: the lowest position of equal scores
+  }
+  const int rounds = min(n, max_keep);
+  for (int r = 0; r < rounds; ++r) {
+    for (int o = 32; o > 0; o >>= 1) {
+      const double s = __shfl_xor(best, o, 64);
+      const int p = __shfl_xor(best_p, o, 64);
+      if (p >= 0 && (best_p < 0 || s > best || (s == best && p < best_p))) { best = s; best_p = p; }
+    }
+    const int head = __shfl(best_p, 0, 64);
+    if (head < 0) break;                                            // cannot happen while r < n; uniform
+    if ((head & 63) == lane) rank[base + head] = r;
+    const float* g = kpts + (long)(base + head) * K * 3;
+    const double a_g = areas[base + head];
+    best = 0.0;
+    best_p = -1;
+    for (int c = lane; c < n; c += 64) {
+      if (c == head || rank[base + c] >= 0) continue;
+      const double oks = nms_oks(g, kpts + (long)(base + c) * K * 3, a_g, areas[base + c], sigmas, K, use_vis, in_vis_thre);
+      double s = soft_score[base + c];
+      if (decay_type == 0) s = s * exp(-(oks * oks) / thresh);
+      else if (oks >= thresh) s = s * (1 - oks);
+      soft_score[base + c] = s;
+      if (best_p < 0 || s > best) { best = s; best_p = c; }
+    }
+  }
 }
 
 struct KptMatchArgs {
@@ -341,6 +391,22 @@ extern "C" int buctd_oks_nms_grouped(const int* offsets, int images, int max_per
   hipLaunchKernelGGL(oks_nms_grouped_kernel, dim3(images), dim3(64), (size_t)cap_words * 8, (hipStream_t)stream, K,
                      cap_words, thresh, use_vis, in_vis_thre, offsets, kpts, areas, sigmas, keep);
   BUCTD_CHECK_LAUNCH("buctd_oks_nms_grouped");
+  return BUCTD_OK;
+}
+
+extern "C" int buctd_soft_oks_nms_grouped(const int* offsets, int images, const float* kpts, const double* areas,
+                                          const double* scores, const double* sigmas, int K, double thresh,
+                                          int decay_type, int use_vis, double in_vis_thre, int max_keep,
+                                          double* soft_score, int* rank, void* stream) {
+  BUCTD_CHECK_ARG(images >= 0 && K > 0 && max_keep > 0, "buctd_soft_oks_nms_grouped: bad argument");
+  BUCTD_CHECK_ARG(thresh > 0, "buctd_soft_oks_nms_grouped: thresh must be > 0 (it divides the gaussian exponent)");
+  BUCTD_CHECK_ARG(decay_type == 0 || decay_type == 1, "buctd_soft_oks_nms_grouped: decay_type is 0 (gaussian) or 1 (linear)");
+  BUCTD_CHECK_ARG(offsets && kpts && areas && scores && sigmas && soft_score && rank,
+                  "buctd_soft_oks_nms_grouped: null pointer");
+  if (images == 0) return BUCTD_OK;
+  hipLaunchKernelGGL(soft_oks_nms_grouped_kernel, dim3(images), dim3(64), 0, (hipStream_t)stream, K, thresh, decay_type,
+                     use_vis, in_vis_thre, max_keep, offsets, kpts, areas, scores, sigmas, soft_score, rank);
+  BUCTD_CHECK_LAUNCH("buctd_soft_oks_nms_grouped");
   return BUCTD_OK;
 }
 

@@ -166,3 +166,95 @@ def soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None):
         order, scores = order[rank], decayed[rank]
         keep.append(head)
     return np.array(keep, dtype=np.intp)
+
+
+# ---- OKS suppression on the device (csrc/keypoint_eval.hip)
+def _decay_type(decay):
+    if decay not in ('gaussian', 'linear'):
+        raise ValueError(f"decay is 'gaussian' or 'linear', not {decay!r}")
+    return 0 if decay == 'gaussian' else 1
+
+
+def soft_oks_nms_grouped(offsets, kpts, areas, scores, sigmas, thresh, *, decay='gaussian', in_vis_thre=None,
+                         max_keep=20):
+    """Soft OKS suppression of every image at once (buctd_soft_oks_nms_grouped, one wavefront per image).  Device
+    tensors: offsets int32 [images + 1] (CSR of the groups), kpts float32 [N][K][3], areas / scores fp64 [N] in grouped
+    order, sigmas fp64 [K].  Returns (rank, soft_score): rank int32 [N], the round in which a person was taken (-1: never;
+    at most max_keep per image); soft_score fp64 [N], its live score at that moment, or after the last round.  In every
+    round the head is the untaken person with the largest live score, the lowest position among equal ones."""
+    import torch
+    from .._C import check, lib, ptr, stream_ptr
+    decay_type = _decay_type(decay)
+    if kpts.dim() != 3 or kpts.shape[2] != 3:
+        raise ValueError(f"kpts is {tuple(kpts.shape)}, expected [N, K, 3]")
+    N, K = int(kpts.shape[0]), int(kpts.shape[1])
+    images = int(offsets.numel()) - 1
+    if areas.numel() != N or scores.numel() != N or sigmas.numel() != K or images < 0:
+        raise ValueError(f"areas ({areas.numel()}) / scores ({scores.numel()}) / sigmas ({sigmas.numel()}) / offsets "
+                         f"({offsets.numel()}) do not describe {N} persons with {K} key points")
+    dev = kpts.device
+    with torch.cuda.device(dev):
+        f64 = lambda t: t.to(dev, torch.float64).contiguous()
+        off_t = offsets.to(dev, torch.int32).contiguous()
+        kp_t = kpts.to(torch.float32).contiguous()
+        area_t, score_t, sig_t = f64(areas), f64(scores), f64(sigmas)
+        rank = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        soft_score = score_t.clone()
+        if N and images:
+            use_vis = in_vis_thre is not None
+            check(lib().buctd_soft_oks_nms_grouped(ptr(off_t), images, ptr(kp_t), ptr(area_t), ptr(score_t), ptr(sig_t), K,
+                                                   float(thresh), decay_type, int(use_vis),
+                                                   float(in_vis_thre) if use_vis else 0.0, int(max_keep), ptr(soft_score),
+                                                   ptr(rank), stream_ptr()), "soft_oks_nms_grouped")
+    return rank, soft_score
+
+
+def _one_image_group(kpts_db, sigmas, device_id):
+    """The poses of one image on the device, in descending score order (stable): order, offsets, kpts, areas, scores,
+    sigmas."""
+    import torch
+    scores, kpts, areas = _db_arrays(kpts_db)
+    n = scores.shape[0]
+    kpts = kpts.reshape(n, -1, 3)
+    sig = COCO_SIGMAS if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    if sig.shape[0] != kpts.shape[1]:
+        raise ValueError(f"sigmas has {sig.shape[0]} entries, the poses {kpts.shape[1]} key points")
+    dev = torch.device("cuda", device_id)
+    with torch.cuda.device(dev):
+        score_t = torch.as_tensor(np.ascontiguousarray(scores, dtype=np.float64)).to(dev)
+        order = torch.argsort(score_t, descending=True, stable=True)
+        kp_t = torch.as_tensor(np.ascontiguousarray(kpts, dtype=np.float32)).to(dev)[order].contiguous()
+        area_t = torch.as_tensor(np.ascontiguousarray(areas, dtype=np.float64)).to(dev)[order].contiguous()
+        off_t = torch.tensor([0, n], dtype=torch.int32, device=dev)
+        return order, off_t, kp_t, area_t, score_t[order].contiguous(), torch.as_tensor(sig).to(dev)
+
+
+def gpu_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0):
+    """oks_nms on the device (buctd_oks_nms_grouped over a one-image group): the kept indices into kpts_db in score
+    order; equal scores in input order.  The key points enter as float32."""
+    if len(kpts_db) == 0:
+        return []
+    import torch
+    from .._C import check, lib, ptr, stream_ptr
+    order, off_t, kp_t, area_t, _, sig_t = _one_image_group(kpts_db, sigmas, device_id)
+    n, K = int(kp_t.shape[0]), int(kp_t.shape[1])
+    with torch.cuda.device(kp_t.device):
+        keep = torch.zeros(n, dtype=torch.int32, device=kp_t.device)
+        use_vis = in_vis_thre is not None
+        check(lib().buctd_oks_nms_grouped(ptr(off_t), 1, n, ptr(kp_t), ptr(area_t), ptr(sig_t), K, float(thresh),
+                                          int(use_vis), float(in_vis_thre) if use_vis else 0.0, ptr(keep), stream_ptr()),
+              "oks_nms_grouped")
+        return [int(i) for i in order[keep != 0].cpu()]
+
+
+def gpu_soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0):
+    """soft_oks_nms on the device (soft_oks_nms_grouped over a one-image group): the indices into kpts_db in selection
+    order, at most 20; equal live scores in input order.  The key points enter as float32."""
+    if len(kpts_db) == 0:
+        return []
+    import torch
+    order, off_t, kp_t, area_t, score_t, sig_t = _one_image_group(kpts_db, sigmas, device_id)
+    rank, _ = soft_oks_nms_grouped(off_t, kp_t, area_t, score_t, sig_t, thresh, in_vis_thre=in_vis_thre, max_keep=20)
+    taken = torch.nonzero(rank >= 0).reshape(-1)
+    taken = taken[torch.argsort(rank[taken])]
+    return order[taken].cpu().numpy().astype(np.intp)

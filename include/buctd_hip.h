@@ -1062,6 +1062,22 @@ int buctd_kpt_rescore(const float* preds, const double* box_in, int n, int K, do
 int buctd_oks_nms_grouped(const int* offsets, int images, int max_per_image, const float* kpts, const double* areas,
                           const double* sigmas, int K, double thresh, int use_vis, double in_vis_thre, int* keep,
                           void* stream);
+/* Soft OKS suppression within every image (soft_oks_nms / rescore of lib/nms/nms.py:150-200): one wavefront per image,
+ * persons [offsets[i], offsets[i + 1]) in the caller's grouped order, n of them.  Every person's live score starts at
+ * scores[p].  min(n, max_keep) rounds; in round r the head is the person not yet taken with the largest live score -
+ * among equal live scores the lowest grouped position - and gets rank r; every other person not yet taken has its live
+ * score multiplied by exp(-oks^2 / thresh) (decay_type 0, gaussian) or, decay_type 1 (linear), by 1 - oks where
+ * oks >= thresh.  oks is the OKS of buctd_oks_nms_grouped against the head (use_vis / in_vis_thre look at the
+ * candidate's joint scores).  This is the reference's re-sort per round written as an arg-max; the two agree whenever
+ * no two live scores are equal.
+ * kpts float32 [total][K][3], areas / scores [total], sigmas [K].  Outputs, both written for every person:
+ * rank int32 [total] - the round in which the person was taken, -1 if it never was; soft_score [total] - the live score
+ * the person had when it was taken, or after the last round if it was not.  soft_score holds the live scores during the
+ * run, so n is unbounded; no LDS, no atomics.
+ * BUCTD_EINVAL before any launch: a NULL pointer, images < 0, K <= 0, thresh <= 0, max_keep <= 0, decay_type not 0 / 1. */
+int buctd_soft_oks_nms_grouped(const int* offsets, int images, const float* kpts, const double* areas,
+                               const double* scores, const double* sigmas, int K, double thresh, int decay_type,
+                               int use_vis, double in_vis_thre, int max_keep, double* soft_score, int* rank, void* stream);
 /* COCO keypoint matching, per image: (a) the D x G matrix of COCOeval.computeOks - variances (2 sigma)^2, denominator
  * gt area + spacing(1), the visible ground-truth joints where there are any, otherwise the distance to the doubled
  * box (x0 = bx - bw, x1 = bx + 2 bw, likewise y) - written row-major to oks + oks_offsets[image]; (b) the greedy

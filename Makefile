@@ -9,7 +9,7 @@ OBJS := $(CSRC)/conv.o $(CSRC)/conv3x3.o $(CSRC)/conv3x3_lean.o $(CSRC)/conv_gat
 
 all: $(OUT)
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_core.h $(CSRC)/c3_common.h $(CSRC)/c3_lean.h $(CSRC)/bn_acc.h $(CSRC)/split_bf16.h $(CSRC)/box_iou.h $(CSRC)/step_math.h include/buctd_hip.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_core.h $(CSRC)/c3_common.h $(CSRC)/c3_lean.h $(CSRC)/bn_acc.h $(CSRC)/split_bf16.h $(CSRC)/box_iou.h $(CSRC)/oks.h $(CSRC)/step_math.h include/buctd_hip.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(CSRC)/error.o: $(CSRC)/error.cpp

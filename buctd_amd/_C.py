@@ -98,6 +98,16 @@ class RefineArgs(C.Structure):          # mirrors buctd_refine_args
                 [(n, C.c_double) for n in ("margin", "aspect_ratio", "in_vis_thre", "scale_thre")])
 
 
+class TrackArgs(C.Structure):           # mirrors buctd_track_args
+    _fields_ = ([(n, C.c_void_p) for n in ("coords", "maxvals", "offset", "ids", "misses", "next_id", "pose", "center",
+                                           "scale", "items", "cond_trunc", "dets", "det_offsets", "frame_src", "sigmas",
+                                           "hist_ids", "hist_preds", "hist_score", "hist_born", "hist_died")] +
+                [(n, C.c_int) for n in ("M", "K", "frame", "frames", "max_dets", "max_misses", "heatmap_w", "heatmap_h",
+                                        "crop_w", "crop_h")] +
+                [(n, C.c_double) for n in ("margin", "aspect_ratio", "in_vis_thre", "scale_thre", "birth_oks", "merge_oks",
+                                           "death_score")])
+
+
 class SampleGeomArgs(C.Structure):      # mirrors buctd_sample_geom_args
     _fields_ = ([(n, C.c_void_p) for n in ("joints", "joints_vis", "cond", "cond_vis", "center", "scale", "bbox",
                                            "half_body", "draws", "bbox_draws", "flags", "pair", "items", "out_joints",
@@ -297,6 +307,7 @@ SIGNATURES = {
     "buctd_cond_mirror": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P]),
     "buctd_mirror_rows": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P]),
     "buctd_refine_step": (_I, [C.POINTER(RefineArgs), _P]),
+    "buctd_track_step": (_I, [C.POINTER(TrackArgs), _P]),
     "buctd_sample_geometry": (_I, [C.POINTER(SampleGeomArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
     "buctd_gconv_x6_supported": (_I, [_I] * 7),

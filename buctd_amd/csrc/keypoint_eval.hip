@@ -9,9 +9,8 @@
 // runs each of the (area range, threshold) greedy matchings.  These are latency kernels; nothing here is tuned.
 #include "common.h"
 #include "box_iou.h"
+#include "oks.h"
 #include "../../include/buctd_hip.h"
-
-#define KPT_SPACING1 2.220446049250313e-16   // np.spacing(1)
 
 // Per person: mean of the joint scores above in_vis_thre (0 if none), summed in joint order; score = mean * box score.
 __global__ __launch_bounds__(64) void kpt_rescore_kernel(int n, int K, double in_vis_thre, const float* __restrict__ preds,
@@ -36,24 +35,7 @@ __global__ __launch_bounds__(64) void kpt_rescore_kernel(int n, int K, double in
   keypoint_score[p] = s;
 }
 
-// oks_iou of nms/nms.py:86-105 for one (head, candidate) pair; kp rows are [K][3] float32.
-__device__ __forceinline__ double nms_oks(const float* __restrict__ g, const float* __restrict__ d, double a_g, double a_d,
-                                          const double* __restrict__ sigmas, int K, int use_vis, double in_vis_thre) {
-  const double scale = (a_g + a_d) / 2 + KPT_SPACING1;
-  double sum = 0.0;
-  int cnt = 0;
-  for (int j = 0; j < K; ++j) {
-    if (use_vis && !((double)d[j * 3 + 2] > in_vis_thre)) continue;
-    const double dx = (double)d[j * 3 + 0] - (double)g[j * 3 + 0];
-    const double dy = (double)d[j * 3 + 1] - (double)g[j * 3 + 1];
-    const double var = (sigmas[j] * 2) * (sigmas[j] * 2);
-    const double e = (dx * dx + dy * dy) / var / scale / 2;
-    sum += exp(-e);
-    ++cnt;
-  }
-  return cnt > 0 ? sum / cnt : 0.0;
-}
-
+// nms_oks (oks.h): oks_iou of nms/nms.py:86-105 for one (head, candidate) pair; kp rows are [K][3] float32.
 // One wavefront per image; persons [off[i], off[i+1]) are in descending score order.  The alive set is a bitmap in LDS
 // (cap_words words); a kept head clears the later candidates it overlaps by more than thresh, 64 candidates per step.
 __global__ __launch_bounds__(64) void oks_nms_grouped_kernel(int K, int cap_words, double thresh, int use_vis,

@@ -10,6 +10,7 @@
 // (sum + 2^14) >> 15; BORDER_CONSTANT 0.  HBM-bound: one pass, ~4 source bytes read (L2-served neighbours) and 12 bytes
 // written per destination pixel.
 #include "common.h"
+#include "oks.h"
 #include "../../include/buctd_hip.h"
 
 struct WarpParams {
@@ -429,6 +430,272 @@ extern "C" int buctd_refine_step(const buctd_refine_args* a, void* stream) {
                   "buctd_refine_step: sizes and the aspect ratio must be positive");
   hipLaunchKernelGGL(refine_step_kernel, dim3(ceil_div(a->B, 4)), dim3(256), 0, (hipStream_t)stream, *a);
   BUCTD_CHECK_LAUNCH("buctd_refine_step");
+  return BUCTD_OK;
+}
+
+// One frame boundary of CTD tracking (dataset/pipeline.py SequenceTracker; no reference call site: the reference leaves
+// this loop to the host).  The slot of a person is its identity; the pose of frame t is the condition of frame t + 1.  One
+// workgroup of four wavefronts runs the whole step, in this order:
+//   A  per slot (a wavefront per slot, lanes over joints, as refine_step_kernel): predictions of frame `frame`, key-point
+//      score, the box around the predictions; the pose goes to the state, the box to LDS;
+//   B  death (one thread per slot), then the M x M OKS table of the survivors (all threads, LDS), then the merge walk in
+//      ascending id order (wavefront 0: lanes over the older slots, one ballot per slot);
+//   C  the detections of frame + 1: box and mean score, rank by (score descending, index), the M x D table against the
+//      live slots and the triangle of detection pairs (all threads, LDS), then the birth walk (wavefront 0: lanes over the
+//      slots, one ballot per detection);
+//   E  per slot: centre, scale, crop affine, source image and truncated condition of frame + 1, and the history rows.
+// The walks read LDS only; nothing is accumulated across threads, so the result does not depend on scheduling.  The OKS
+// is symmetric bit for bit without a visibility threshold (squares of differences, a commutative sum of the two areas):
+// detection pairs are kept as a triangle.  LDS: 32 KiB + 15.75 KiB of tables, 6 KiB of per-slot and per-detection rows.
+#define TRACK_MAX 64
+struct TrackShared {
+  double oks[TRACK_MAX * TRACK_MAX];              // [M][M] for the merge, then [M][D] for the birth
+  double tri[TRACK_MAX * (TRACK_MAX - 1) / 2];    // detections i < j at j * (j - 1) / 2 + i
+  double box[TRACK_MAX][4], dbox[TRACK_MAX][4];   // x0, y0, w, h of the slots' predictions and of the detections
+  double score[TRACK_MAX], dmean[TRACK_MAX];
+  int id[TRACK_MAX], alive[TRACK_MAX], nobox[TRACK_MAX], died[TRACK_MAX], src[TRACK_MAX], order[TRACK_MAX], dbad[TRACK_MAX];
+  int n_order, next_id;
+};
+
+__device__ __forceinline__ void put_box(double* dst, const KeypointBox& b) {
+  dst[0] = b.x0; dst[1] = b.y0; dst[2] = b.w; dst[3] = b.h;
+}
+__device__ __forceinline__ KeypointBox get_box(const double* src) {
+  KeypointBox b;
+  b.empty = false; b.x0 = src[0]; b.y0 = src[1]; b.w = src[2]; b.h = src[3];
+  return b;
+}
+
+__global__ __launch_bounds__(256) void track_step_kernel(buctd_track_args p) {
+  __shared__ TrackShared sh;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int M = p.M, K = p.K, f = p.frame;
+  const bool decode = f >= 0, next = f + 1 < p.frames;
+  const bool on = lane < K;
+  const double W = (double)p.items[0].W, H = (double)p.items[0].H;        // one size for all frames
+  if (tid < M) {
+    const int id = p.ids[tid];
+    sh.id[tid] = id; sh.alive[tid] = id >= 0; sh.died[tid] = 0; sh.src[tid] = -1; sh.nobox[tid] = 0; sh.score[tid] = 0.0;
+  }
+  if (tid == 0) { sh.next_id = *p.next_id; sh.n_order = 0; }
+  __syncthreads();
+  // ---- A: predictions, score and box of frame f, per slot ----------------------------------------------------------
+  if (decode) {
+    for (int s = wave; s < M; s += 4) {                                    // wave-uniform
+      const bool live = sh.alive[s] != 0;
+      const long row = (long)f * M + s;
+      float px = 0.f, py = 0.f, mv = 0.f;
+      if (live && on) {
+        const CropAffine back = crop_affine(p.center[2 * s], p.center[2 * s + 1], p.scale[2 * s], p.heatmap_w, p.heatmap_h, true);
+        const long i = (long)s * K + lane;
+        float hx = p.coords[2 * i], hy = p.coords[2 * i + 1];
+        if (p.offset) {
+          hx = hx + p.offset[2 * i];
+          hy = hy + p.offset[2 * i + 1];
+        }
+        mv = p.maxvals[i];
+        px = (float)__dadd_rn(__dmul_rn((double)hx, back.sx), back.tx);
+        py = (float)__dadd_rn(__dmul_rn((double)hy, back.sy), back.ty);
+      }
+      if (on) {
+        float* hp = p.hist_preds + (row * K + lane) * 3;
+        hp[0] = px; hp[1] = py; hp[2] = mv;
+        double* ps = p.pose + ((long)s * K + lane) * 3;
+        if (live) { ps[0] = (double)px; ps[1] = (double)py; ps[2] = (double)mv; }
+      }
+      const bool counted = live && on && mv > (float)p.in_vis_thre;          // IterativeRefiner.rescore, box score 1
+      const int n = __popcll(__ballot(counted));
+      const double sum = wave_sum_f64(counted ? (double)mv : 0.0);
+      const double kpt_score = n > 0 ? sum / (double)n : 0.0;
+      const KeypointBox box = keypoint_box((double)px, (double)py, live && on, p.margin, W, H);
+      const CenterScale cs = xywh2cs(box, p.aspect_ratio, p.scale_thre);
+      const CropAffine fwd = crop_affine(cs.cx, cs.cy, cs.s0, p.crop_w, p.crop_h, false);
+      if (lane == 0) {
+        put_box(sh.box[s], box);
+        sh.nobox[s] = live && (box.empty || !fwd.ok);
+        sh.score[s] = kpt_score;
+        p.hist_score[row] = kpt_score;
+      }
+    }
+    __syncthreads();
+    // ---- B: death, then merge ----------------------------------------------------------------------------------------
+    if (tid < M && sh.alive[tid]) {
+      int misses = p.misses[tid];
+      bool dies = sh.nobox[tid] != 0;
+      if (!dies) {
+        misses = sh.score[tid] < p.death_score ? misses + 1 : 0;
+        dies = misses >= p.max_misses;
+      }
+      p.misses[tid] = dies ? 0 : misses;
+      if (dies) { sh.alive[tid] = 0; sh.died[tid] = 1; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < M * M; idx += 256) {
+      const int i = idx / M, j = idx - i * M;
+      if (i < j && sh.alive[i] && sh.alive[j]) {
+        const double v = nms_oks(p.pose + (long)i * K * 3, p.pose + (long)j * K * 3, __dmul_rn(sh.box[i][2], sh.box[i][3]),
+                                 __dmul_rn(sh.box[j][2], sh.box[j][3]), p.sigmas, K, 0, 0.0);
+        sh.oks[i * M + j] = v;
+        sh.oks[j * M + i] = v;
+      }
+    }
+    if (tid < M && sh.alive[tid]) {                                          // rank among the survivors by id (ids are unique)
+      int rank = 0;
+      for (int q = 0; q < M; ++q) rank += (sh.alive[q] && sh.id[q] < sh.id[tid]) ? 1 : 0;
+      sh.order[rank] = tid;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const unsigned long long alive = __ballot(lane < M && sh.alive[lane]);
+      const int n = __popcll(alive);
+      unsigned long long kept = 0ull;
+      for (int r = 0; r < n; ++r) {
+        const int s = sh.order[r];                                           // same address in every lane
+        const bool hit = ((kept >> lane) & 1ull) && sh.oks[s * M + lane] >= p.merge_oks;
+        if (__ballot(hit) == 0ull) kept |= 1ull << s;
+      }
+      if (((alive & ~kept) >> lane) & 1ull) { sh.alive[lane] = 0; sh.died[lane] = 1; }
+    }
+    __syncthreads();
+  }
+  // ---- C: birth for frame f + 1 ------------------------------------------------------------------------------------
+  if (next) {
+    const int base = p.det_offsets[f + 1];
+    const int D = min(max(p.det_offsets[f + 2] - base, 0), p.max_dets);     // beyond the stated maximum: never indexed
+    const double* dets = p.dets + (long)base * K * 3;
+    for (int d = wave; d < D; d += 4) {
+      const double x = on ? dets[((long)d * K + lane) * 3] : 0.0, y = on ? dets[((long)d * K + lane) * 3 + 1] : 0.0;
+      const KeypointBox box = keypoint_box(x, y, on, p.margin, W, H);
+      const CenterScale cs = xywh2cs(box, p.aspect_ratio, p.scale_thre);
+      const CropAffine fwd = crop_affine(cs.cx, cs.cy, cs.s0, p.crop_w, p.crop_h, false);
+      if (lane == 0) {
+        put_box(sh.dbox[d], box);
+        sh.dbad[d] = box.empty || !fwd.ok;
+      }
+    }
+    if (tid < D) {                                                           // mean score: summed in joint order
+      double sum = 0.0;
+      for (int j = 0; j < K; ++j) sum = __dadd_rn(sum, dets[((long)tid * K + j) * 3 + 2]);
+      sh.dmean[tid] = sum / (double)K;
+    }
+    __syncthreads();
+    if (tid < D) {
+      int rank = 0;
+      const double mine = sh.dmean[tid];
+      for (int q = 0; q < D; ++q) {
+        const double other = sh.dmean[q];
+        rank += (other > mine || (other == mine && q < tid)) ? 1 : 0;
+      }
+      sh.order[rank] = tid;
+    }
+    for (int idx = tid; idx < (M + D) * D; idx += 256) {
+      const int r = idx / D, d = idx - r * D;
+      const double a_d = __dmul_rn(sh.dbox[d][2], sh.dbox[d][3]);
+      if (r < M) {
+        if (sh.alive[r])
+          sh.oks[r * D + d] = nms_oks(p.pose + (long)r * K * 3, dets + (long)d * K * 3,
+                                      __dmul_rn(sh.box[r][2], sh.box[r][3]), a_d, p.sigmas, K, 0, 0.0);
+      } else if (r - M < d) {
+        const int i = r - M;
+        sh.tri[d * (d - 1) / 2 + i] = nms_oks(dets + (long)i * K * 3, dets + (long)d * K * 3,
+                                              __dmul_rn(sh.dbox[i][2], sh.dbox[i][3]), a_d, p.sigmas, K, 0, 0.0);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      unsigned long long live = __ballot(lane < M && sh.alive[lane]);
+      const unsigned long long slots = M == 64 ? ~0ull : (1ull << M) - 1ull;
+      int mysrc = -1, born = 0;
+      for (int r = 0; r < D; ++r) {
+        const int d = sh.order[r];                                           // same address in every lane
+        if (sh.dbad[d]) continue;
+        bool hit = false;
+        if ((live >> lane) & 1ull) {
+          const double v = mysrc < 0 ? sh.oks[lane * D + d]
+                                     : (mysrc < d ? sh.tri[d * (d - 1) / 2 + mysrc] : sh.tri[mysrc * (mysrc - 1) / 2 + d]);
+          hit = v >= p.birth_oks;
+        }
+        const unsigned long long free_slots = ~live & slots;
+        if (__ballot(hit) == 0ull && free_slots != 0ull) {
+          const int slot = __ffsll((long long)free_slots) - 1;               // the lowest free slot
+          if (lane == slot) {
+            mysrc = d;
+            sh.src[lane] = d; sh.id[lane] = sh.next_id + born; sh.alive[lane] = 1;
+          }
+          live |= 1ull << slot;
+          ++born;
+        }
+      }
+      if (lane == 0) sh.next_id = sh.next_id + born;                         // after every read of it above: one wavefront
+    }
+    __syncthreads();
+  }
+  // ---- E: the slots of frame f + 1 and the history rows -------------------------------------------------------------
+  for (int s = wave; s < M; s += 4) {
+    const bool alive = sh.alive[s] != 0;
+    const int src = sh.src[s];
+    if (lane == 0) {
+      if (decode) p.hist_died[(long)f * M + s] = (unsigned char)sh.died[s];
+      p.ids[s] = alive ? sh.id[s] : -1;
+      if (!alive || src >= 0) p.misses[s] = 0;
+    }
+    if (!next) continue;
+    KeypointBox box;
+    double x = 0.0, y = 0.0;
+    double* ps = p.pose + ((long)s * K + lane) * 3;
+    if (alive && src >= 0) {                                                 // newborn: the detection is its pose
+      box = get_box(sh.dbox[src]);
+      if (on) {
+        const double* dp = p.dets + ((long)(p.det_offsets[f + 1] + src) * K + lane) * 3;
+        x = dp[0]; y = dp[1];
+        ps[0] = x; ps[1] = y; ps[2] = dp[2];
+      }
+    } else if (alive) {
+      box = get_box(sh.box[s]);
+      if (on) { x = ps[0]; y = ps[1]; }
+    } else {                                                                 // empty: the whole image, no condition
+      box.empty = false; box.x0 = 0.0; box.y0 = 0.0; box.w = W; box.h = H;
+    }
+    const CenterScale cs = xywh2cs(box, p.aspect_ratio, p.scale_thre);
+    const CropAffine fwd = crop_affine(cs.cx, cs.cy, cs.s0, p.crop_w, p.crop_h, false);
+    if (lane == 0) {
+      const long row = (long)(f + 1) * M + s;
+      p.hist_ids[row] = alive ? sh.id[s] : -1;
+      p.hist_born[row] = (unsigned char)(alive && src >= 0);
+      p.center[2 * s] = cs.cx; p.center[2 * s + 1] = cs.cy;
+      p.scale[2 * s] = cs.s0; p.scale[2 * s + 1] = cs.s1;
+      buctd_warp_item* it = p.items + s;
+      it->src = p.frame_src[f + 1];
+      it->m[0] = fwd.sx; it->m[1] = 0.0; it->m[2] = fwd.tx;
+      it->m[3] = 0.0; it->m[4] = fwd.sy; it->m[5] = fwd.ty;
+    }
+    if (on) {
+      double qx = 0.0, qy = 0.0;
+      if (alive) {
+        qx = __dadd_rn(__dmul_rn(fwd.sx, x), fwd.tx);
+        qy = __dadd_rn(__dmul_rn(fwd.sy, y), fwd.ty);
+      }
+      store_trunc(p.cond_trunc + ((long)s * K + lane) * 2, qx, qy);
+    }
+  }
+  if (tid == 0) *p.next_id = sh.next_id;
+}
+
+extern "C" int buctd_track_step(const buctd_track_args* a, void* stream) {
+  BUCTD_CHECK_ARG(a && a->ids && a->misses && a->next_id && a->pose && a->center && a->scale && a->items && a->cond_trunc &&
+                      a->dets && a->det_offsets && a->frame_src && a->sigmas && a->hist_ids && a->hist_preds &&
+                      a->hist_score && a->hist_born && a->hist_died,
+                  "buctd_track_step: NULL argument (only coords, maxvals and offset may be NULL, before the first frame)");
+  BUCTD_CHECK_ARG(a->M > 0 && a->M <= TRACK_MAX, "buctd_track_step: 0 < M <= 64 track slots");
+  BUCTD_CHECK_ARG(a->K > 0 && a->K <= 32, "buctd_track_step: 0 < K <= 32 joints");
+  BUCTD_CHECK_ARG(a->max_dets >= 0 && a->max_dets <= TRACK_MAX, "buctd_track_step: at most 64 detections per frame");
+  BUCTD_CHECK_ARG(a->frames > 0 && a->frame >= -1 && a->frame < a->frames, "buctd_track_step: frame outside [-1, frames)");
+  BUCTD_CHECK_ARG(a->frame < 0 || (a->coords && a->maxvals), "buctd_track_step: frame >= 0 needs its decode outputs");
+  BUCTD_CHECK_ARG(a->heatmap_w > 0 && a->heatmap_h > 0 && a->crop_w > 0 && a->crop_h > 0 && a->aspect_ratio > 0.0 &&
+                      a->max_misses > 0,
+                  "buctd_track_step: sizes, the aspect ratio and max_misses must be positive");
+  hipLaunchKernelGGL(track_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
+  BUCTD_CHECK_LAUNCH("buctd_track_step");
   return BUCTD_OK;
 }
 

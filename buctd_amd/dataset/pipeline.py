@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._C import RefineArgs, SampleGeomArgs, check, lib, ptr, stream_ptr
+from .._C import RefineArgs, SampleGeomArgs, TrackArgs, check, lib, ptr, stream_ptr
 from ..core.inference import get_final_preds
 from ..utils.transforms import (_swap_table, affine_transform, flip_hm, flip_perm, fliplr_joints, get_affine_transform,
                                 mirror_condition)
@@ -1000,3 +1000,248 @@ class IterativeRefiner:
         return [dict(preds=got["preds"][p].copy(), score=got["score"][p].copy(), box_score=got["box_score"][p].copy(),
                      keypoint_score=got["keypoint_score"][p].copy(), center=got["center"][p].copy(),
                      scale=got["scale"][p].copy()) for p in range(passes)]
+
+
+# ---- CTD tracking: the pose of frame t - 1 is the condition of frame t -------------------------------------------------
+MAX_TRACK_SLOTS = 64           # buctd_track_step: slots, and detections of one frame
+
+
+def track_history_layout(T, M, K):
+    """The sections of SequenceTracker's history buffer, what buctd_track_step writes per frame: for _layout()."""
+    return [("score", np.float64, (T, M)), ("ids", np.int32, (T, M)), ("preds", np.float32, (T, M, K, 3)),
+            ("born", np.uint8, (T, M)), ("died", np.uint8, (T, M))]
+
+
+def mean_keypoint_score(pose):
+    """The score a detection is ranked by at birth: its joints' scores summed in joint order, over K (float64)."""
+    return np.cumsum(np.asarray(pose, dtype=np.float64)[:, 2])[-1] / pose.shape[0]
+
+
+class SequenceTracker:
+    """CTD tracking of persons (animals) through a frame sequence: max_tracks slots, the slot a person occupies is its
+    identity, the pose found in frame t - 1 is the condition of frame t, bottom-up detections only start tracks.
+
+    run(frames, detections): frames = T uint8 [H, W, 3] device tensors of one size; detections = per frame a bottom-up
+    pose array [n_t, K, 3] (x, y, score; n_t may be 0).  Returns per frame dict(ids [M] int64 (-1 = empty slot), preds
+    [M, K, 3] float32, score [M] float64, born [M] bool, died [M] bool); the rows of empty slots are zeros.  Every frame
+    runs the model on exactly M rows - an empty slot carries the whole-image box and an all-zero condition - so an
+    engine.ForwardGraph replays.  Per frame:
+
+      birth  the frame's detections by descending mean_keypoint_score, equal ones by index: one whose OKS against every
+             live slot's pose - the detections born before it in this frame included - is below birth_oks takes the lowest
+             free slot and the next id (ids count up from 0 and are never reused); without a free slot it is dropped.  OKS =
+             nms.oks_iou without a visibility threshold, areas = w * h of box_from_keypoints with the pipeline's margin,
+             sigmas default nms.COCO_SIGMAS (17 joints; any other K must pass its own).
+      pose   the condition of a live slot is its pose - the previous frame's prediction, or the detection it was born
+             from; box, crop, condition, forward pass, decode and rescoring (box score 1) are IterativeRefiner's.
+      death  a slot whose prediction has no non-zero x or no non-zero y, or a box without extent, dies at once; otherwise a
+             keypoint score below death_score is a miss (else the misses reset) and the slot dies at max_misses of them in
+             a row.
+      merge  the surviving slots in ascending id order: one whose OKS against an older kept slot is >= merge_oks dies.
+    A slot freed in frame t can be taken from frame t + 1 on; `died` marks it in frame t, where it still has its id.
+
+    on_device=True: one upload before the first frame (state, all detections with an offsets table, the frame pointers),
+    one buctd_track_step launch per frame boundary, one copy back after the last frame; the host never waits inside the
+    loop.  M <= 64, K <= 32, at most 64 detections per frame.  Same return value as the host path."""
+
+    def __init__(self, cfg, model, pipeline, max_tracks=16, birth_oks=0.3, merge_oks=0.7, death_score=0.2, max_misses=2,
+                 sigmas=None, in_vis_thre=None, use_dark=False, on_device=False):
+        from ..nms.nms import COCO_SIGMAS
+        self.cfg, self.model, self.pipe = cfg, model, pipeline
+        self.max_tracks, self.max_misses = int(max_tracks), int(max_misses)
+        self.birth_oks, self.merge_oks, self.death_score = float(birth_oks), float(merge_oks), float(death_score)
+        self.use_dark, self.on_device = bool(use_dark), bool(on_device)
+        K = pipeline.num_joints
+        if sigmas is None:
+            if K != COCO_SIGMAS.shape[0]:
+                raise ValueError(f"SequenceTracker: the default sigmas are COCO's {COCO_SIGMAS.shape[0]}; a config with "
+                                 f"{K} joints must pass its own")
+            sigmas = COCO_SIGMAS
+        self.sigmas = np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+        if self.sigmas.shape[0] != K:
+            raise ValueError(f"SequenceTracker: sigmas has {self.sigmas.shape[0]} entries, MODEL.NUM_JOINTS is {K}")
+        if self.max_tracks < 1 or self.max_misses < 1:
+            raise ValueError("SequenceTracker: max_tracks and max_misses must be positive")
+        if pipeline.is_train or not pipeline.conditional:
+            raise ValueError("SequenceTracker needs an eval pipeline (is_train=False) of a conditional config "
+                             "(MODEL.CONDITIONAL_TOPDOWN): the previous pose is the condition")
+        if self.on_device and (self.max_tracks > MAX_TRACK_SLOTS or K > MAX_DEVICE_JOINTS):
+            raise ValueError(f"SequenceTracker(on_device=True) handles at most {MAX_TRACK_SLOTS} tracks and "
+                             f"{MAX_DEVICE_JOINTS} joints (max_tracks {self.max_tracks}, MODEL.NUM_JOINTS {K})")
+        self.refiner = IterativeRefiner(cfg, model, pipeline, in_vis_thre=in_vis_thre, use_dark=use_dark)
+        self.in_vis_thre = self.refiner.in_vis_thre
+
+    # ---- the pieces of the specification ----------------------------------------------------------------------------
+    def pose_box(self, pose, iw, ih):
+        """(x, y, w, h) of a pose's box, or None where there is none: no non-zero x, no non-zero y, or no extent (the crop
+        affine of utils.transforms.crop_affine_closed_form is singular)."""
+        from ..utils.transforms import crop_affine_closed_form
+        pose = np.asarray(pose, dtype=np.float64)
+        if not (pose[:, 0] != 0).any() or not (pose[:, 1] != 0).any():
+            return None
+        box = box_from_keypoints(pose, self.pipe.bu_bbox_margin, iw, ih)
+        c, s = xywh2cs(*box, self.pipe.aspect_ratio, self.pipe.scale_thre)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ok = np.isfinite(crop_affine_closed_form(c, s, self.pipe.image_size)).all()
+        return box if ok else None
+
+    def oks(self, pose, area, others, areas):
+        """OKS of one pose against others [n, K, 3] (nms.oks_iou, every joint counts)."""
+        from ..nms.nms import oks_iou
+        others = np.asarray(others, dtype=np.float64)
+        return oks_iou(np.asarray(pose, dtype=np.float64).reshape(-1), others.reshape(others.shape[0], -1), area,
+                       np.asarray(areas, dtype=np.float64), self.sigmas)
+
+    def _check_inputs(self, frames, detections):
+        T, K = len(frames), self.pipe.num_joints
+        if T == 0 or len(detections) != T:
+            raise ValueError(f"SequenceTracker.run: {T} frames, {len(detections)} detection arrays")
+        _check_images(frames)
+        if any(f.shape != frames[0].shape or f.device != frames[0].device for f in frames):
+            raise ValueError("SequenceTracker.run: the frames of a sequence have one size and one device")
+        ih, iw = int(frames[0].shape[0]), int(frames[0].shape[1])
+        dets = [np.asarray(d, dtype=np.float64).reshape(-1, K, 3) for d in detections]
+        for t, d in enumerate(dets):
+            if self.on_device and d.shape[0] > MAX_TRACK_SLOTS:
+                raise ValueError(f"SequenceTracker(on_device=True): frame {t} has {d.shape[0]} detections, at most "
+                                 f"{MAX_TRACK_SLOTS} per frame")
+            bad = [i for i in range(d.shape[0]) if self.pose_box(d[i], iw, ih) is None]
+            if bad:
+                raise ValueError(f"SequenceTracker.run: detection(s) {bad} of frame {t} have no non-zero x or y coordinate, "
+                                 "or a box without extent: there is no box to crop")
+        return dets, iw, ih
+
+    def _records(self, frame, ids, pose, iw, ih):
+        """The M records of one frame: IterativeRefiner.next_records for the live slots, the whole-image box and an
+        invisible all-zero condition for the empty ones."""
+        K = self.pipe.num_joints
+        base = dict(image=frame)
+        c, s = xywh2cs(0, 0, iw, ih, self.pipe.aspect_ratio, self.pipe.scale_thre)
+        zero = np.zeros((K, 3), dtype=np.float64)
+        empty = dict(base, center=c, scale=s, score=1.0, cond_joints=zero, cond_joints_vis=zero, joints_3d=zero,
+                     joints_3d_vis=np.ones((K, 3), dtype=np.float64), use_bu_bbox=False)
+        live = np.nonzero(ids >= 0)[0]
+        recs = [empty] * len(ids)
+        for s_, r in zip(live, self.refiner.next_records([base] * len(live), pose[live], np.ones(len(live)))):
+            recs[s_] = r
+        return recs
+
+    @torch.no_grad()
+    def run(self, frames, detections):
+        dets, iw, ih = self._check_inputs(frames, detections)
+        if self.on_device:
+            return self.run_on_device(frames, dets)
+        self.model.eval()
+        pipe, M, K = self.pipe, self.max_tracks, self.pipe.num_joints
+        ids, misses, next_id = np.full(M, -1, dtype=np.int64), np.zeros(M, dtype=np.int64), 0
+        pose, area = np.zeros((M, K, 3), dtype=np.float64), np.zeros(M, dtype=np.float64)
+        history = []
+        for frame, det in zip(frames, dets):
+            # birth
+            born = np.zeros(M, dtype=bool)
+            means = np.array([mean_keypoint_score(d) for d in det], dtype=np.float64)
+            for i in sorted(range(det.shape[0]), key=lambda i: (-means[i], i)):
+                x, y, w, h = self.pose_box(det[i], iw, ih)
+                live, free = np.nonzero(ids >= 0)[0], np.nonzero(ids < 0)[0]
+                if live.size and self.oks(det[i], w * h, pose[live], area[live]).max() >= self.birth_oks:
+                    continue
+                if free.size:
+                    s = free[0]
+                    ids[s], misses[s], pose[s], area[s], born[s] = next_id, 0, det[i], w * h, True
+                    next_id += 1
+            # pose
+            recs = self._records(frame, ids, pose, iw, ih)
+            geos = [pipe.geometry(r) for r in recs]
+            x, _, _ = pipe.render([frame] * M, geos)
+            hm = self.refiner._forward(x, M)
+            center, scale = np.stack([g["center"] for g in geos]), np.stack([g["scale"] for g in geos])
+            coords, maxvals = get_final_preds(self.cfg, hm, center, scale, use_dark=self.use_dark)
+            score, _ = IterativeRefiner.rescore(maxvals, np.ones(M), self.in_vis_thre)
+            preds = np.concatenate([coords, maxvals], axis=2).astype(np.float32)
+            was = ids >= 0
+            preds[~was], score = 0, np.where(was, score, 0.0).astype(np.float64)
+            out = dict(ids=ids.copy(), preds=preds, score=score, born=born, died=np.zeros(M, dtype=bool))
+            # death
+            for s in np.nonzero(was)[0]:
+                pose[s] = preds[s]
+                box = self.pose_box(pose[s], iw, ih)
+                if box is not None:
+                    area[s] = box[2] * box[3]
+                    misses[s] = misses[s] + 1 if score[s] < self.death_score else 0
+                if box is None or misses[s] >= self.max_misses:
+                    out["died"][s] = True
+            # merge
+            kept = []
+            for s in sorted(np.nonzero(was & ~out["died"])[0], key=lambda s: ids[s]):
+                if kept and self.oks(pose[s], area[s], pose[kept], area[kept]).max() >= self.merge_oks:
+                    out["died"][s] = True
+                else:
+                    kept.append(s)
+            ids[out["died"]], misses[out["died"]] = -1, 0
+            history.append(out)
+        return history
+
+    # ---- the device loop ----------------------------------------------------------------------------------------------
+    def track_step(self, decoded, sv, out, frame, frames, max_dets):
+        """One buctd_track_step launch: decoded = (coords [M, K, 2], maxvals [M, K, 1], offsets [M, K, 2] or None) of
+        frame `frame`, None for frame = -1; sv: the views of the state upload; out: those of track_history_layout()."""
+        pipe = self.pipe
+        a = TrackArgs()
+        if decoded is not None:
+            a.coords, a.maxvals, a.offset = (ptr(t) for t in decoded)
+        for k in ("ids", "misses", "next_id", "pose", "center", "scale", "items", "cond_trunc", "dets", "det_offsets",
+                  "frame_src", "sigmas"):
+            setattr(a, k, ptr(sv[k]))
+        a.hist_ids, a.hist_preds, a.hist_score = ptr(out["ids"]), ptr(out["preds"]), ptr(out["score"])
+        a.hist_born, a.hist_died = ptr(out["born"]), ptr(out["died"])
+        a.M, a.K, a.frame, a.frames = self.max_tracks, pipe.num_joints, int(frame), int(frames)
+        a.max_dets, a.max_misses = int(max_dets), self.max_misses
+        a.heatmap_w, a.heatmap_h = int(pipe.heatmap_size[0]), int(pipe.heatmap_size[1])
+        a.crop_w, a.crop_h = int(pipe.image_size[0]), int(pipe.image_size[1])
+        a.margin, a.aspect_ratio = float(pipe.bu_bbox_margin), float(pipe.aspect_ratio)
+        a.in_vis_thre, a.scale_thre = float(self.in_vis_thre), float(pipe.scale_thre)
+        a.birth_oks, a.merge_oks, a.death_score = self.birth_oks, self.merge_oks, self.death_score
+        check(lib().buctd_track_step(C.byref(a), stream_ptr()), "track_step")
+
+    @staticmethod
+    def state_layout(T, M, K, n_dets):
+        """The sections of the one upload: the slots' state (all empty), the packed detections, the frame pointers."""
+        f32, f64, i32 = np.float32, np.float64, np.int32
+        return [("pose", f64, (M, K, 3)), ("dets", f64, (max(n_dets, 1), K, 3)), ("sigmas", f64, (K,)),
+                ("frame_src", np.uint64, (T,)), ("items", np.uint64, (M, WARP_ITEM.itemsize // 8)), ("center", f32, (M, 2)),
+                ("scale", f32, (M, 2)), ("cond_trunc", f32, (M, K, 2)), ("ids", i32, (M,)), ("misses", i32, (M,)),
+                ("next_id", i32, (1,)), ("det_offsets", i32, (T + 1,))]
+
+    def run_on_device(self, frames, dets):
+        """run() with on_device=True: one upload before the first frame, one copy back after the last."""
+        self.model.eval()
+        pipe, cfg = self.pipe, self.cfg
+        T, M, K = len(frames), self.max_tracks, pipe.num_joints
+        dev = frames[0].device
+        counts = [d.shape[0] for d in dets]
+        at_in, n_in = _layout(self.state_layout(T, M, K, sum(counts)))
+        host = np.zeros(n_in, dtype=np.uint8)
+        hv = _views(host, at_in)
+        hv["ids"][:] = -1
+        hv["sigmas"][:] = self.sigmas
+        hv["det_offsets"][:] = np.concatenate([[0], np.cumsum(counts)])
+        if sum(counts):
+            hv["dets"][:sum(counts)] = np.concatenate(dets)
+        hv["frame_src"][:] = [f.data_ptr() for f in frames]
+        warp_items([frames[0]] * M, items=hv["items"].reshape(-1).view(WARP_ITEM))
+        sv = _views(torch.from_numpy(host).to(dev), at_in)
+        at_out, n_out = _layout(track_history_layout(T, M, K))
+        result = torch.zeros(n_out, dtype=torch.uint8, device=dev)
+        out = _views(result, at_out)
+        colors = pipe.condition_colors(dev)
+        refine = bool(cfg.TEST.POST_PROCESS)
+        max_dets = max(counts)
+        self.track_step(None, sv, out, -1, T, max_dets)                   # the birth of frame 0
+        for t in range(T):
+            x = pipe.warp_and_condition(sv["items"], sv["cond_trunc"], colors)
+            hm = self.refiner._forward(x, M)
+            res = ops.dark_decode(hm) if self.use_dark else ops.argmax_decode(hm, refine=refine)
+            self.track_step((res[0], res[1], res[3] if (self.use_dark or refine) else None), sv, out, t, T, max_dets)
+        got = _views(result.cpu().numpy(), at_out)
+        return [dict(ids=got["ids"][t].astype(np.int64), preds=got["preds"][t].copy(), score=got["score"][t].copy(),
+                     born=got["born"][t].astype(bool), died=got["died"][t].astype(bool)) for t in range(T)]

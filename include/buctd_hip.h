@@ -942,6 +942,58 @@ typedef struct {
   double margin, aspect_ratio, in_vis_thre, scale_thre;
 } buctd_refine_args;
 int buctd_refine_step(const buctd_refine_args* a, void* stream);
+/* One frame boundary of CTD tracking (dataset.pipeline.SequenceTracker; reference call site: none: host loop - the
+ * reference tracks by running its data loader once per frame).  M slots; the slot of a person is its identity, ids count
+ * up from 0 and are never reused; the pose found in frame t is the condition of frame t + 1.  The call with `frame` = f
+ * takes the decode outputs of frame f and leaves everything frame f + 1 needs, in this order:
+ *   preds, score   of every live slot as buctd_refine_step forms them (box score 1); the float32 preds, widened, become
+ *              the slot's pose.  An empty slot gets zeros.
+ *   death      a live slot without a non-zero x or without a non-zero y among its preds, or whose box has no extent, dies
+ *              at once; otherwise a keypoint score < death_score is one more miss (else misses = 0) and the slot dies at
+ *              max_misses misses.
+ *   merge      the survivors in ascending id order: a slot whose OKS against an older slot that is kept is >= merge_oks
+ *              dies.  OKS: nms.oks_iou without a visibility threshold (nms_oks of csrc/oks.h, shared with
+ *              buctd_oks_nms_grouped), areas = w * h of the pose boxes (box_from_keypoints with `margin`), fp64.
+ *   birth      (f + 1 < frames) the detections [det_offsets[f + 1], det_offsets[f + 2]) by descending mean score (summed
+ *              in joint order, / K), equal means by index: one whose OKS against every live slot - detections born before
+ *              it in this call included - is < birth_oks takes the lowest free slot and the id *next_id, which counts up.
+ *              Without a free slot it is dropped; so is one without a box.  The slots freed above are free here.
+ *   next frame for every slot: center, scale (xywh2cs of the pose's box; an empty slot: of the whole image), items[s].m (the
+ *              closed-form crop affine) and items[s].src = frame_src[f + 1]; cond_trunc = trunc() of the pose through m, zeros
+ *              for an empty slot.  H, W, flip and the rectangle of an item are read, never written; all frames have the size
+ *              of items[0].
+ * History: row f receives preds, score and died; row f + 1 ids (-1: empty) and born.  `frame` = -1 is the birth of frame 0:
+ * every slot must be empty (ids = -1) and coords / maxvals / offset are not read.  `frame` = frames - 1 ends with the merge.
+ * Limits: M <= 64, K <= 32, max_dets <= 64 - the caller's statement of the largest detection count of a frame; detections
+ * of a frame beyond it are never indexed.  One workgroup; the OKS tables (M x M, then M x D and the D x D triangle) are
+ * built by all its lanes in LDS, the two greedy walks read LDS only; no atomics; deterministic.  One launch, no allocation,
+ * no synchronisation. */
+typedef struct {
+  const float* coords;      /* [M][K][2] heat-map coordinates of the decode kernels, frame `frame` */
+  const float* maxvals;     /* [M][K] */
+  const float* offset;      /* [M][K][2] quarter-pixel or DARK offsets, NULL: none */
+  int32_t* ids;             /* [M] in / out, -1: empty */
+  int32_t* misses;          /* [M] in / out */
+  int32_t* next_id;         /* [1] in / out */
+  double* pose;             /* [M][K][3] in / out: x, y, score of every live slot */
+  float* center;            /* [M][2] in / out */
+  float* scale;             /* [M][2] in / out */
+  buctd_warp_item* items;   /* [M]: H, W read; src, m written */
+  float* cond_trunc;        /* [M][K][2] out */
+  const double* dets;       /* [det_offsets[frames]][K][3]: x, y, score, image coordinates */
+  const int32_t* det_offsets; /* [frames + 1] */
+  const unsigned char* const* frame_src; /* [frames] device addresses of the frames, uint8 [H][W][3] */
+  const double* sigmas;     /* [K] */
+  int32_t* hist_ids;        /* [frames][M] */
+  float* hist_preds;        /* [frames][M][K][3] */
+  double* hist_score;       /* [frames][M] */
+  unsigned char* hist_born; /* [frames][M] */
+  unsigned char* hist_died; /* [frames][M] */
+  int M, K, frame, frames, max_dets, max_misses;
+  int heatmap_w, heatmap_h, crop_w, crop_h;
+  double margin, aspect_ratio, in_vis_thre, scale_thre, birth_oks, merge_oks, death_score;
+} buctd_track_args;
+int buctd_track_step(const buctd_track_args* a, void* stream);
 /* Scalar geometry of a TRAIN batch on the device (JointsDataset.py:217-295, as DeviceSamplePipeline.geometry restates
  * them on the host): from the records, the augmentation draws and (for generative sampling) the pose
  * buctd_synthesize_pose left on the device to the table buctd_warp_affine_norm reads and the inputs of

@@ -310,6 +310,7 @@ SIGNATURES = {
     "buctd_track_step": (_I, [C.POINTER(TrackArgs), _P]),
     "buctd_sample_geometry": (_I, [C.POINTER(SampleGeomArgs), _P]),
     "buctd_synthesize_pose": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _P]),
+    "buctd_pose_error_types": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "buctd_gconv_x6_supported": (_I, [_I] * 7),
     "buctd_gconv_x6_prep_bytes": (_SZ, [_I, _I, _I, _I]),
     "buctd_gconv_x6_prep": (_I, [_I, _I, _I, _P, _I, _P, _P]),

@@ -30,7 +30,7 @@ from .._C import RefineArgs, SampleGeomArgs, TrackArgs, check, lib, ptr, stream_
 from ..core.inference import get_final_preds
 from ..utils.transforms import (_swap_table, affine_transform, flip_hm, flip_perm, fliplr_joints, get_affine_transform,
                                 mirror_condition)
-from .pose_synthesis import synthesize_pose_batch
+from .pose_synthesis import make_tables, synthesize_pose_batch
 
 _M64 = (1 << 64) - 1
 MAX_DEVICE_JOINTS = 32         # buctd_sample_geometry, buctd_refine_step, buctd_cond_geometry, buctd_cond_mirror
@@ -216,7 +216,9 @@ class DeviceSamplePipeline:
     (same result, slower; meta['cond_joints'] / ['cond_joints_vis'] are host tensors there).  With is_train=False the
     flag changes nothing.  Without the flag a conditional train pipeline refuses records that lack 'cond_joints'.
     The variant of the synthesis is cfg.DATASET.DATASET's: 'coco', 'crowdpose', or the generic one for any other name
-    (fish, marmosets, multimouse, a custom data set; pose_synthesis.py:798-816).
+    (fish, marmosets, multimouse, a custom data set; pose_synthesis.py:798-816).  synth_ladders: the probability ladders of
+    the synthesis (pose_synthesis.make_tables; None = the reference's), e.g. ErrorProfile.ladders() of
+    dataset.error_diagnosis: the error mix measured on the bottom-up model whose poses condition the network at test time.
 
     geometry_on_device=True (train pipelines, NUM_JOINTS <= 32): the scalar geometry leaves the host as well.  __call__
     makes the augmentation draws with the same generators in the same order as the host path (draw(); aug = a list of
@@ -241,7 +243,8 @@ class DeviceSamplePipeline:
     it is not looked at."""
 
     def __init__(self, cfg, flip_pairs=(), upper_body_ids=(), kpt_colors=None, mean=(0.485, 0.456, 0.406),
-                 std=(0.229, 0.224, 0.225), is_train=False, seed=0, joints_weight=None, geometry_on_device=False):
+                 std=(0.229, 0.224, 0.225), is_train=False, seed=0, joints_weight=None, geometry_on_device=False,
+                 synth_ladders=None):
         self.cfg = cfg
         self.is_train = is_train
         self.num_joints = cfg.MODEL.NUM_JOINTS
@@ -273,6 +276,9 @@ class DeviceSamplePipeline:
         self.dataset = getattr(ds, "DATASET", None)
         self.seed = int(seed)
         self.synth_calls = 0
+        self.synth_ladders = synth_ladders
+        if synth_ladders is not None:
+            make_tables(self.dataset, self.num_joints, synth_ladders)      # refuse a malformed value here, not mid-epoch
         self._pair_dev = {}
         self._perm_dev, self._colors_dev = {}, {}                          # the flip test's tables, uploaded once
         self.joints_weight = None
@@ -747,7 +753,7 @@ class DeviceSamplePipeline:
             self.synth_calls += 1
         J, E, V, near, area = self.synthesis_inputs(records)
         synth = synthesize_pose_batch(self.dataset, J, E, near, area, np.zeros(len(records), dtype=np.int32), seed,
-                                      device=records[0]["image"].device)
+                                      device=records[0]["image"].device, ladders=self.synth_ladders)
         return synth, V
 
     @staticmethod

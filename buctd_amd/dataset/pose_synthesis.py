@@ -62,16 +62,62 @@ def _joint_classes(dataset, k):
     return jit, miss, inv, swap, sym, np.array(sig) / 10.0, vis
 
 
+def default_ladders(dataset):
+    """A copy of the ladders `dataset` takes without a `ladders` argument (the reference's numbers)."""
+    lad = _HUMAN_LADDERS if dataset in ("coco", "crowdpose") else _GENERIC_LADDERS
+    return {k: _thaw(_freeze(v)) for k, v in lad.items()}
+
+
+def _freeze(v):
+    """Nested lists / tuples / arrays -> nested tuples of Python numbers (hashable: the key of the tables' cache)."""
+    if isinstance(v, (list, tuple, np.ndarray)):
+        return tuple(_freeze(x) for x in v)
+    return v.item() if isinstance(v, np.generic) else v
+
+
+def _thaw(v):
+    return [_thaw(x) for x in v] if isinstance(v, tuple) else v
+
+
+_LADDER_SHAPES = dict(jitter_p=(2, 3), miss_p=(3, 3), inv_p=(3,), swap_p=(2, 3), jitter_nv=(), miss_nv=(2,), crowd=(2, 2))
+
+
+def _ladders_key(ladders):
+    """ladders (a dict with keys of _HUMAN_LADDERS: the four probability ladders alone, or the row thresholds as well) ->
+    a sorted tuple of (key, nested tuples), checked for keys, shapes and 0 <= p <= 1."""
+    unknown = sorted(set(ladders) - set(_LADDER_SHAPES))
+    if unknown:
+        raise ValueError(f"ladders: unknown keys {unknown}; known: {sorted(_LADDER_SHAPES)}")
+    key = []
+    for name in sorted(ladders):
+        val = _freeze(ladders[name])
+        if np.shape(val) != _LADDER_SHAPES[name]:
+            raise ValueError(f"ladders[{name!r}] has shape {np.shape(val)}, expected {_LADDER_SHAPES[name]}")
+        if name.endswith("_p") and not all(0.0 <= p <= 1.0 for p in np.ravel(val)):
+            raise ValueError(f"ladders[{name!r}] holds a probability outside [0, 1]")
+        key.append((name, val))
+    return tuple(key)
+
+
+def make_tables(dataset, num_joints, ladders=None):
+    """Per-dataset constants of the kernel (buctd_synth_tables), built once per (dataset, K, ladders); callers do not
+    modify it.  dataset: 'coco', 'crowdpose', or any other name for the generic variant with num_joints (1...32) key
+    points.  ladders: None = the reference's numbers; or a dict with keys of default_ladders(dataset) - the probability
+    ladders jitter_p / miss_p / inv_p / swap_p, any subset, and optionally the row thresholds - that replaces those
+    entries (ErrorProfile.ladders of dataset.error_diagnosis makes one from a bottom-up model's measured errors)."""
+    return _make_tables(dataset, num_joints, None if ladders is None else _ladders_key(ladders))
+
+
 @functools.lru_cache(maxsize=None)
-def make_tables(dataset, num_joints):
-    """Per-dataset constants of the kernel (buctd_synth_tables), built once per (dataset, K); callers do not modify it.
-    dataset: 'coco', 'crowdpose', or any other name for the generic variant with num_joints (1...32) key points."""
+def _make_tables(dataset, num_joints, ladders_key):
     if not 1 <= num_joints <= _MAXK:
         raise ValueError(f"pose synthesis takes 1 to {_MAXK} key points, MODEL.NUM_JOINTS is {num_joints}")
     jit, miss, inv, swap, sym, sig, vis = _joint_classes(dataset, num_joints)
     if len(sig) != num_joints:
         raise ValueError(f"{dataset} has {len(sig)} key points, MODEL.NUM_JOINTS is {num_joints}")
     lad = _HUMAN_LADDERS if dataset in ("coco", "crowdpose") else _GENERIC_LADDERS
+    if ladders_key is not None:
+        lad = dict(lad, **dict(ladders_key))
     t = _Tables()
     pair = [-1] * _MAXK
     for a, b in sym:
@@ -97,9 +143,11 @@ def make_tables(dataset, num_joints):
     return t
 
 
-def synthesize_pose_batch(dataset, joints, estimated_joints, near_joints, area, num_overlap, seed, device=None):
+def synthesize_pose_batch(dataset, joints, estimated_joints, near_joints, area, num_overlap, seed, device=None,
+                          ladders=None):
     """joints, estimated_joints [B, K, 3]; near_joints [B, M, K, 3] (pad absent neighbours with visibility 0);
-    area [B]; num_overlap [B].  numpy arrays or tensors; returns a float64 device tensor [B, K, 3]."""
+    area [B]; num_overlap [B].  numpy arrays or tensors; returns a float64 device tensor [B, K, 3].
+    ladders: see make_tables (None: the reference's)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
 
     def dev64(a):
@@ -110,7 +158,7 @@ def synthesize_pose_batch(dataset, joints, estimated_joints, near_joints, area, 
     M = 0 if NR is None else NR.shape[1]
     ov = torch.as_tensor(np.asarray(num_overlap), dtype=torch.int32).to(dev).contiguous()
     out = torch.empty((B, K, 3), dtype=torch.float64, device=dev)
-    tables = make_tables(dataset, K)
+    tables = make_tables(dataset, K, ladders)
     check(lib().buctd_synthesize_pose(C.byref(tables), ptr(J), ptr(E), ptr(NR), ptr(A), ptr(ov), B, K, M,
                                       C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ptr(out), stream_ptr()),
           "synthesize_pose")

@@ -1080,6 +1080,25 @@ typedef struct {
 int buctd_synthesize_pose(const buctd_synth_tables* tables, const double* joints, const double* estimated,
                           const double* near_joints, const double* area, const int* num_overlap, int B, int K, int M,
                           unsigned long long seed, double* out, void* stream);
+/* Pose error diagnosis: the inverse of buctd_synthesize_pose.  Same inputs (`estimated` is the pose to diagnose, e.g. a
+ * bottom-up model's), same limits (K <= 32, M <= 31).  With the synthesiser's sigmas, pairs, d85 / d50 rings (ks 0.85 and
+ * 0.50 of sqrt(-2 area (2 sigma_j)^2 ln ks)) and sources, per person b and joint j - r0, rI, rS the float64 distances
+ * sqrt(dx dx + dy dy) of estimated[j] to joints[j], to joints[pair[j]] (labelled) and to the nearest neighbours' joint j
+ * or pair[j] (visibility > 0), +inf where there is none:
+ *   code [B][K] int32   -1 joints[j] unlabelled (visibility <= 0) | 5 absent: estimated[j] is (0, 0) |
+ *                       4 miss: min(r0, rI, rS) >= d50 | else the nearest source, ties own, inversion, swap:
+ *                       r0 <= rI and r0 <= rS: 0 good (r0 < d85) or 1 jitter | rI <= rS: 2 inversion | 3 swap
+ *   ks [B][K] float64   exp(-r0^2 / (2 area (2 sigma_j)^2)) where labelled and present, else 0
+ *   hist [4][3][3][2] int64   type jitter / miss / inversion / swap x ladder row (the row buctd_synthesize_pose takes
+ *                       for the person's num_valid and num_overlap; inversion: row 0) x the joint's class of that type x
+ *                       {hits, eligible}.  Eligible: labelled and present - jitter and miss always, inversion where
+ *                       its source exists, swap where a swap source exists.
+ *   per_joint [K][6] int64   counts of the codes 0...5
+ * hist and per_joint are ADDED to (64-bit integer atomics: the result does not depend on scheduling) - the caller
+ * zeroes them, and may diagnose a data set in batches.  Classes outside [0, 3) and pairs >= K are refused. */
+int buctd_pose_error_types(const buctd_synth_tables* tables, const double* joints, const double* estimated,
+                           const double* near_joints, const double* area, const int* num_overlap, int B, int K, int M,
+                           int* code, double* ks, long long* hist, long long* per_joint, void* stream);
 
 /* ------------------------------------------------------------------- NMS --- */
 /* Greedy box NMS - replaces _nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num, int boxes_dim,

@@ -36,7 +36,8 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         if self.training and x.is_cuda and torch.is_grad_enabled() and _native_block(self):
-            return ops.BasicBlockFn.apply(x, *_block_params(self))
+            params = _block_params(self)
+            return ops.BasicBlockFn.apply(x, *params, ops.block_anchor([[params]]))
         residual = x if self.downsample is None else self.downsample(x)
         out = nn.conv_bn_act(x, self.conv1, self.bn1, relu=True)
         return nn.conv_bn_act(out, self.conv2, self.bn2, relu=True, residual=residual)
@@ -79,7 +80,7 @@ class Bottleneck(nn.Module):
                 and (self.downsample is None or type(self.downsample) is nn.ConvBN and not self.downsample._relu)):
             for c in (self.conv1, self.conv2, self.conv3) + (() if self.downsample is None else (self.downsample[0],)):
                 nn._as_channels_last_(c.weight)
-            return ops.BottleneckFn.apply(x, self.conv1.weight, self)
+            return ops.BottleneckFn.apply(x, ops.grad_anchor(self.parameters()), self)
         residual = x if self.downsample is None else self.downsample(x)
         out = nn.conv_bn_act(x, self.conv1, self.bn1, relu=True)
         out = nn.conv_bn_act(out, self.conv2, self.bn2, relu=True)
@@ -94,7 +95,8 @@ class BlockChain(nn.Chain):
         if (len(self) > 1 and self.training and x.is_cuda and torch.is_grad_enabled() and ops.native_chain_ok(tuple(x.shape))
                 and all(_native_block(m) and m.bn1.track_running_stats == self[0].bn1.track_running_stats for m in self)
                 and ops.bn_in_fusable(tuple(x.shape), self[0].conv1.weight)):
-            return ops.BasicChainFn.apply(x, self[0].conv1.weight, [_block_params(m) for m in self])
+            blocks = [_block_params(m) for m in self]
+            return ops.BasicChainFn.apply(x, ops.block_anchor([blocks]), blocks)
         return super().forward(x)
 
 
@@ -187,10 +189,11 @@ class HighResolutionModule(nn.Module):
             return None
         parts = ops.group_branch_partition(nb)
         if len(parts) == 1:
-            return list(ops.BasicBranchesFn.apply(chains[0][0][0], chains, *xs))
+            return list(ops.BasicBranchesFn.apply(ops.block_anchor(chains), chains, *xs))
         # several groups side by side on the branch streams: the streaming BatchNorm kernels of one group run under the
         # convolutions of the other
-        outs = ops.fork_join([lambda p=p: ops.BasicBranchesFn.apply(chains[p[0]][0][0], [chains[i] for i in p], *[xs[i] for i in p])
+        outs = ops.fork_join([lambda p=p: ops.BasicBranchesFn.apply(ops.block_anchor([chains[i] for i in p]), [chains[i] for i in p],
+                                                                    *[xs[i] for i in p])
                               for p in parts], [[xs[i] for i in p] for p in parts])
         ys = [None] * nb
         for p, o in zip(parts, outs):
@@ -316,7 +319,8 @@ class HRNetTrunk(nn.Module):
                 # every new branch starts with a conv + BN + ReLU on the same tensor: one autograd node (ops.ForkConvBnFn)
                 for h in heads:
                     nn._as_channels_last_(h[0].weight)
-                ys = ops.ForkConvBnFn.apply(prev, heads[0][0].weight, [(h[0], h[1], h._relu) for h in heads])
+                ys = ops.ForkConvBnFn.apply(prev, ops.grad_anchor(p for h in heads for p in h.parameters()),
+                                            [(h[0], h[1], h._relu) for h in heads])
                 out = []
                 for i in range(n):
                     y = ys[i]

@@ -90,12 +90,12 @@ class TransformerEncoderLayer(nn.Module):
         else:
             src2 = self.self_attn(qin, src)
         src2 = ops_seq.Dropout.apply(src2, float(self.dropout1.p), self.training)
-        src = ops_seq.AddLayerNorm.apply(src, src2, self.norm1)
+        src = ops_seq.AddLayerNorm.apply(src, src2, self.norm1, ops.grad_anchor(self.norm1.parameters()))
         ff = self.linear1(src, relu=True)
         ff = ops_seq.Dropout.apply(ff, float(self.dropout.p), self.training)
         ff = self.linear2(ff)
         ff = ops_seq.Dropout.apply(ff, float(self.dropout2.p), self.training)
-        src = ops_seq.AddLayerNorm.apply(src, ff, self.norm2)
+        src = ops_seq.AddLayerNorm.apply(src, ff, self.norm2, ops.grad_anchor(self.norm2.parameters()))
         return (src, att_map) if self.return_atten_map else src
 
 

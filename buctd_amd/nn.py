@@ -128,13 +128,14 @@ class Sequential(tnn.Sequential):
 def conv_bn_act(x, conv, bn, relu=False, residual=None):
     """Fused conv -> BN -> (+residual) -> (ReLU) on NHWC tensors (train or eval)."""
     _as_channels_last_(conv.weight)
+    anchor = ops.grad_anchor((conv.weight, conv.bias, bn.weight, bn.bias))
     if isinstance(conv, ConvTranspose2d):
         k, s, p, op = conv._geom()
         # ConvTranspose2d(Cin->Cout) == data gradient of a Conv2d(Cout->Cin) with the same weight
         return ops.ConvBnAct.apply(x, conv.weight, conv.bias, bn, residual, relu, s, p, bn.training,
-                                   conv.out_shape(tuple(x.shape)))
+                                   conv.out_shape(tuple(x.shape)), anchor)
     stride, pad = conv._geom()
-    return ops.ConvBnAct.apply(x, conv.weight, conv.bias, bn, residual, relu, stride, pad, bn.training, None)
+    return ops.ConvBnAct.apply(x, conv.weight, conv.bias, bn, residual, relu, stride, pad, bn.training, None, anchor)
 
 
 class ConvBN(Sequential):

@@ -378,7 +378,16 @@ def grad_done(*params):
 
 
 def grad_target(p):
-    """Returns (tensor to write the gradient into, accumulate flag)."""
+    """Returns (tensor to write the gradient into, accumulate flag).  A frozen parameter (requires_grad False) gets a scratch
+    tensor: the kernels that write several gradients at once have somewhere to write, p.grad stays None and the arena slot
+    is not touched - as with torch.optim, an optimizer never sees it.  The scratch stays with the parameter: a native
+    sequence takes the targets of many parameters before it launches (and runs part of them on a side stream), so a
+    temporary would be back in the allocator - and handed out as the next target - before any kernel wrote it."""
+    if not p.requires_grad:
+        g = getattr(p, "_grad_scratch", None)
+        if g is None or g.shape != p.shape or g.stride() != p.stride() or g.device != p.device:
+            g = p._grad_scratch = torch.empty_like(p, memory_format=torch.preserve_format)
+        return g, 0
     if p.grad is not None:
         return p.grad, 1
     g = _grad_arena(p) if _grad_arena is not None else None
@@ -386,6 +395,40 @@ def grad_target(p):
         g = torch.empty_like(p, memory_format=torch.preserve_format)
     p.grad = g
     return g, 0
+
+
+def norm_acc(gamma, acc_g, beta, acc_b):
+    """The one accumulate flag of the kernel that writes both affine gradients of a norm layer.  A frozen one of the two
+    writes into scratch and follows the other; two trainable ones must agree."""
+    if not gamma.requires_grad:
+        return acc_b
+    if not beta.requires_grad:
+        return acc_g
+    if acc_g != acc_b:
+        raise RuntimeError("norm layer with a gradient in only one of weight.grad / bias.grad: one kernel writes both with one "
+                           "accumulate flag - set both to None (zero_grad) or keep both")
+    return acc_g
+
+
+def grad_anchor(params):
+    """The tensor argument that makes autograd build a node whose parameters travel inside modules or lists, where autograd
+    does not look: the first parameter that needs a gradient, else the first one.  With it the node is built whenever its
+    input or ANY of its parameters needs a gradient."""
+    first = None
+    for p in params:
+        if p is None:
+            continue
+        if p.requires_grad:
+            return p
+        if first is None:
+            first = p
+    return first
+
+
+def block_anchor(chains):
+    """grad_anchor over chains[b] = [(w1, bn1, w2, bn2), ...]"""
+    return grad_anchor(p for chain in chains for (w1, bn1, w2, bn2) in chain
+                       for p in (w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias))
 
 
 # --------------------------------------------------------------------------------------
@@ -1736,7 +1779,8 @@ class ConvBnAct(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, conv_w, conv_b, bn, residual, relu, stride, pad, training, transposed_shape):
+    def forward(ctx, x, conv_w, conv_b, bn, residual, relu, stride, pad, training, transposed_shape, anchor=None):
+        # anchor (grad_anchor): bn's parameters are invisible to autograd - it builds the node for them
         gamma, beta = bn.weight, bn.bias
         eps = bn.eps
         ctx.meta = (bn, conv_w, conv_b, relu, stride, pad, training, transposed_shape, tuple(x.shape))
@@ -1773,7 +1817,7 @@ class ConvBnAct(torch.autograd.Function):
         dy = _contig(dy)
         dgamma, acc_g = grad_target(bn.weight)
         dbeta, acc_b = grad_target(bn.bias)
-        assert acc_g == acc_b
+        acc_g = norm_acc(bn.weight, acc_g, bn.bias, acc_b)
         dz, dres = bn_bwd(dy, y, z, mean, invstd, bn.weight, relu, ctx.has_res and relu, dgamma, dbeta, acc_g, beta=bn.bias)
         if ctx.has_res and not relu:
             dres = dy
@@ -1783,20 +1827,22 @@ class ConvBnAct(torch.autograd.Function):
                 # dx_residual: a gradient that reaches x on another path of the same autograd node (BottleneckFn) - added
                 # in the epilogue of the data-gradient kernel instead of by an accumulation pass of autograd
                 dx = conv_dgrad(dz, conv_w, x_shape, stride, pad, residual=getattr(ctx, "dx_residual", None))
-            dw, acc_w = grad_target(conv_w)
-            conv_wgrad_async(x, dz, conv_w, stride, pad, dw, acc_w)
+            if conv_w.requires_grad:
+                dw, acc_w = grad_target(conv_w)
+                conv_wgrad_async(x, dz, conv_w, stride, pad, dw, acc_w)
         else:
             # forward was a transposed conv: its data gradient is a plain conv, its weight gradient
             # swaps the roles of input and output gradient
             if ctx.needs_input_grad[0]:
                 dx = conv_fwd(dz, conv_w, None, stride, pad)
-            dw, acc_w = grad_target(conv_w)
-            conv_wgrad_async(dz, x, conv_w, stride, pad, dw, acc_w)
-        if conv_b is not None:
+            if conv_w.requires_grad:
+                dw, acc_w = grad_target(conv_w)
+                conv_wgrad_async(dz, x, conv_w, stride, pad, dw, acc_w)
+        if conv_b is not None and conv_b.requires_grad:
             db, acc = grad_target(conv_b)
             colsum(dz, dz.shape[-1], db, acc)
         grad_done(bn.weight, bn.bias, conv_w, conv_b)
-        return dx, None, None, None, dres, None, None, None, None, None
+        return dx, None, None, None, dres, None, None, None, None, None, None
 
 
 class _SubCtx:
@@ -1843,7 +1889,7 @@ class BottleneckFn(torch.autograd.Function):
     block at CoAM-W48) - and the host walks one node instead of four."""
 
     @staticmethod
-    def forward(ctx, x, w1, m):
+    def forward(ctx, x, anchor, m):
         need = ctx.needs_input_grad[0]
         c1, c2, c3 = _SubCtx(need), _SubCtx(), _SubCtx()
         cd = None
@@ -1888,7 +1934,7 @@ class ForkConvBnFn(torch.autograd.Function):
     accumulation pass of autograd.  Same kernels as the separate ConvBnAct nodes."""
 
     @staticmethod
-    def forward(ctx, x, w0, groups):
+    def forward(ctx, x, anchor, groups):
         need = ctx.needs_input_grad[0]
         subs, outs = [], []
         for conv, bn, relu in groups:
@@ -1924,7 +1970,8 @@ class BasicBlockFn(torch.autograd.Function):
     tensor passes per block), and the host walks one node instead of two plus an accumulation."""
 
     @staticmethod
-    def forward(ctx, x, w1, bn1, w2, bn2):
+    def forward(ctx, x, w1, bn1, w2, bn2, anchor=None):
+        # anchor (grad_anchor): builds the node for the BatchNorm parameters, which autograd does not see
         # In the bf16x6 mode conv2 applies bn1 + ReLU while it stages its input: the tensor y1 = relu(bn1(conv1(x)))
         # never exists in HBM (one kernel and two tensor passes less per block; conv2's weight gradient rebuilds it the
         # same way).  Bit-identical to the unfused sequence: the staged value is bn_apply's own expression.
@@ -1960,32 +2007,34 @@ class BasicBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         if ctx.native:
-            return _chain_backward(ctx, dy, ctx.needs_input_grad[0]), None, None, None, None
+            return _chain_backward(ctx, dy, ctx.needs_input_grad[0]), None, None, None, None, None
         w1, bn1, w2, bn2, fuse = ctx.meta
         x, z1, mean1, invstd1, y1, z2, mean2, invstd2, y2 = ctx.saved_tensors
         dy = _contig(dy)
         # conv2 / bn2 (+ skip): dres = masked upstream gradient
         dg, acc_g = grad_target(bn2.weight)
         db, acc_b = grad_target(bn2.bias)
-        assert acc_g == acc_b
+        acc_g = norm_acc(bn2.weight, acc_g, bn2.bias, acc_b)
         dz2, dres = bn_bwd(dy, y2, z2, mean2, invstd2, bn2.weight, True, True, dg, db, acc_g)
         dy1 = conv_dgrad(dz2, w2, tuple(z1.shape), 1, 1)
-        dw, acc_w = grad_target(w2)
-        if fuse:
-            conv_wgrad_async(z1, dz2, w2, 1, 1, dw, acc_w, x_bn=(mean1, invstd1, bn1.weight, bn1.bias, True))
-        else:
-            conv_wgrad_async(y1, dz2, w2, 1, 1, dw, acc_w)
+        if w2.requires_grad:
+            dw, acc_w = grad_target(w2)
+            if fuse:
+                conv_wgrad_async(z1, dz2, w2, 1, 1, dw, acc_w, x_bn=(mean1, invstd1, bn1.weight, bn1.bias, True))
+            else:
+                conv_wgrad_async(y1, dz2, w2, 1, 1, dw, acc_w)
         grad_done(bn2.weight, bn2.bias, w2)
         # conv1 / bn1: ReLU mask rebuilt from z1; the skip gradient joins in the dgrad epilogue
         dg, acc_g = grad_target(bn1.weight)
         db, acc_b = grad_target(bn1.bias)
-        assert acc_g == acc_b
+        acc_g = norm_acc(bn1.weight, acc_g, bn1.bias, acc_b)
         dz1, _ = bn_bwd(dy1, None, z1, mean1, invstd1, bn1.weight, True, False, dg, db, acc_g, beta=bn1.bias)
         dx = conv_dgrad(dz1, w1, tuple(x.shape), 1, 1, residual=dres) if ctx.needs_input_grad[0] else None
-        dw, acc_w = grad_target(w1)
-        conv_wgrad_async(x, dz1, w1, 1, 1, dw, acc_w)
+        if w1.requires_grad:
+            dw, acc_w = grad_target(w1)
+            conv_wgrad_async(x, dz1, w1, 1, 1, dw, acc_w)
         grad_done(bn1.weight, bn1.bias, w1)
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
 def _block_desc(d, shape, step, xin, params, act, stat, acc=None):
@@ -2031,7 +2080,8 @@ def _block_grads(g, tmp, step, dy, want_dx, params, bn_acc, ws, ws_bytes):
     dg1, acc_g1 = grad_target(bn1.weight)
     db1, acc_b1 = grad_target(bn1.bias)
     dw1, acc_w1 = grad_target(w1)
-    assert acc_g2 == acc_b2 and acc_g1 == acc_b1
+    acc_g2 = norm_acc(bn2.weight, acc_g2, bn2.bias, acc_b2)
+    acc_g1 = norm_acc(bn1.weight, acc_g1, bn1.bias, acc_b1)
     weight_rsc(dw1)
     weight_rsc(dw2)
     g.dw1, g.dw2 = dw1.data_ptr(), dw2.data_ptr()
@@ -2133,10 +2183,11 @@ def _chain_backward(ctx, dy, want_dx):
 class BasicChainFn(torch.autograd.Function):
     """A chain of residual BasicBlocks (an HRNet branch: pose_hrnet.py:165-185) as ONE autograd node and one library call
     per direction (block.hip: buctd_basic_chain_*): the launches of n BasicBlockFn nodes, a quarter of their host work
-    per block.  blocks: [(w1, bn1, w2, bn2), ...]; w_first only makes autograd build the node when x needs no gradient."""
+    per block.  blocks: [(w1, bn1, w2, bn2), ...]; anchor only makes autograd build the node when x needs no gradient: a parameter
+    of the chain that needs one (block_anchor)."""
 
     @staticmethod
-    def forward(ctx, x, w_first, blocks):
+    def forward(ctx, x, anchor, blocks):
         return _chain_forward(ctx, x, blocks)
 
     @staticmethod
@@ -2249,10 +2300,11 @@ class BasicBranchesFn(torch.autograd.Function):
     different size - as ONE autograd node and one library call per direction (block.hip: buctd_basic_branches_*).  The k-th
     convolutions of all branches are one launch (several de-phased rounds of workgroups instead of nb phase-locked rounds on
     nb streams), so are the BatchNorm applies / backwards and the weight gradients.
-    chains[b] = [(w1, bn1, w2, bn2), ...]; w_first only makes autograd build the node when no input needs a gradient."""
+    chains[b] = [(w1, bn1, w2, bn2), ...]; anchor only makes autograd build the node when no input needs a gradient: a
+    parameter of the chains that needs one (block_anchor)."""
 
     @staticmethod
-    def forward(ctx, w_first, chains, *xs):
+    def forward(ctx, anchor, chains, *xs):
         nb, n = len(xs), len(chains[0])
         descs = (_C.BasicBlockDesc * (nb * n))()
         acts, stats = zip(*(_Chain(x, chains[b], descs, b * n).forward() for b, x in enumerate(xs)))
@@ -2704,17 +2756,19 @@ class SmallQKAttention(torch.autograd.Function):
         dw4t = torch.empty_like(w4t)
         matmul(dkp, k, dw4t, batch=1, M=R4, N=Cn, K=B * T, a_layout=1, b_layout=1, lda=R4, ldb=Cn, ldc=Cn)
         dyq = dqp[:, :, :d].contiguous() if ctx.needs_input_grad[0] else None
-        gw, acc = grad_target(wq)
-        if acc:
-            gw.add_(dw4t[:d].t())
-        else:
-            gw.copy_(dw4t[:d].t())
+        if wq.requires_grad:
+            gw, acc = grad_target(wq)
+            if acc:
+                gw.add_(dw4t[:d].t())
+            else:
+                gw.copy_(dw4t[:d].t())
         grad_done(wq)
-        gb, acc = grad_target(bq)
-        if acc:
-            gb.add_(dw4t[d])
-        else:
-            gb.copy_(dw4t[d])
+        if bq.requires_grad:
+            gb, acc = grad_target(bq)
+            if acc:
+                gb.add_(dw4t[d])
+            else:
+                gb.copy_(dw4t[d])
         grad_done(bq)
         return dyq, None, None, dk, dv, None, None
 

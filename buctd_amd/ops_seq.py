@@ -148,8 +148,9 @@ class AddLayerNorm(torch.autograd.Function):
     """LayerNorm(a + b) with affine parameters (post-norm residual, transpose_h.py:204-209)."""
 
     @staticmethod
-    def forward(ctx, a, b, ln):
-        keep = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])     # backward() runs only then (it also owns ln's gradients)
+    def forward(ctx, a, b, ln, anchor=None):
+        # anchor (ops.grad_anchor): builds the node for ln's parameters, which autograd does not see
+        keep = any(ctx.needs_input_grad)     # backward() runs only then (it also owns ln's gradients)
         y, mean, invstd, s = ops.add_layernorm_fwd(a.contiguous(), b.contiguous(), ln.weight, ln.bias, ln.eps, keep_sum=keep)
         ctx.ln = ln
         if keep:
@@ -162,10 +163,10 @@ class AddLayerNorm(torch.autograd.Function):
         ln = ctx.ln
         dg, acc = ops.grad_target(ln.weight)
         db, acc2 = ops.grad_target(ln.bias)
-        assert acc == acc2
+        acc = ops.norm_acc(ln.weight, acc, ln.bias, acc2)
         ds = ops.layernorm_bwd(dy.contiguous(), s, mean, invstd, ln.weight, dg, db, acc)
         ops.grad_done(ln.weight, ln.bias)
-        return ds, ds, None
+        return ds, ds, None, None
 
 
 class InProjection(torch.autograd.Function):
@@ -193,12 +194,14 @@ class InProjection(torch.autograd.Function):
         x4 = (B, 1, T, d)
         dqin = ops.conv_dgrad(dqk, w[: 2 * d], x4, 1, 0).view(B, T, d)
         dsrc = ops.conv_dgrad(dv, w[2 * d:], x4, 1, 0).view(B, T, d)
-        gw, acc = ops.grad_target(w)
-        gb, accb = ops.grad_target(b)
-        ops.conv_wgrad(qin.view(x4), dqk, w[: 2 * d], 1, 0, out=gw[: 2 * d], accumulate=acc)
-        ops.conv_wgrad(src.view(x4), dv, w[2 * d:], 1, 0, out=gw[2 * d:], accumulate=acc)
-        ops.colsum(dqk, 2 * d, gb[: 2 * d], accb)
-        ops.colsum(dv, d, gb[2 * d:], accb)
+        if w.requires_grad:
+            gw, acc = ops.grad_target(w)
+            ops.conv_wgrad(qin.view(x4), dqk, w[: 2 * d], 1, 0, out=gw[: 2 * d], accumulate=acc)
+            ops.conv_wgrad(src.view(x4), dv, w[2 * d:], 1, 0, out=gw[2 * d:], accumulate=acc)
+        if b.requires_grad:
+            gb, accb = ops.grad_target(b)
+            ops.colsum(dqk, 2 * d, gb[: 2 * d], accb)
+            ops.colsum(dv, d, gb[2 * d:], accb)
         ops.grad_done(w, b)
         return dqin, dsrc, None, None
 

@@ -15,7 +15,9 @@ def get_last_layer_optimizer(cfg, model):
     and run Adam(cfg.TRAIN.LR) over what is left - here a grouped engine.FusedAdam with that one group, so the frozen trunk
     is never read or written by a step (and its backward kernels are not launched).  The model stays as it is otherwise:
     in train mode BatchNorm running statistics keep moving, as in the reference.  `model` may be an engine.DataParallel in
-    a world of one; under a gradient exchange the grouped form refuses a partly frozen arena."""
+    a world of one; under a gradient exchange the grouped form refuses a partly frozen arena.  A partial freeze made by
+    hand (some parameters of a node frozen, others not) gives the frozen ones no .grad either: the nodes write their
+    gradients to scratch (ops.grad_target), so any optimizer on the arena leaves them alone."""
     from .. import engine
     for name, param in model.named_parameters():
         if 'final_layer' not in name:

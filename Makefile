@@ -5,7 +5,7 @@ CSRC  := buctd_amd/csrc
 OUT   := buctd_amd/lib/libbuctd_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result
 OBJS := $(CSRC)/conv.o $(CSRC)/conv3x3.o $(CSRC)/conv3x3_lean.o $(CSRC)/conv_gather_x6.o $(CSRC)/conv_gather_wgrad.o $(CSRC)/conv3x3_wgrad.o $(CSRC)/matmul.o $(CSRC)/bn.o $(CSRC)/elementwise.o $(CSRC)/attention.o $(CSRC)/attn_smallqk.o $(CSRC)/attn_mha.o $(CSRC)/attn_mha_train.o $(CSRC)/attn_rows.o $(CSRC)/gemm_x6.o $(CSRC)/block.o $(CSRC)/conv_bf16.o \
-        $(CSRC)/loss_decode.o $(CSRC)/optim_groups.o $(CSRC)/grad_norm.o $(CSRC)/weight_avg.o $(CSRC)/nms.o $(CSRC)/keypoint_eval.o $(CSRC)/conditions.o $(CSRC)/sample.o $(CSRC)/synth.o $(CSRC)/synth_diag.o $(CSRC)/vis.o $(CSRC)/vis_pose.o $(CSRC)/error.o
+        $(CSRC)/loss_decode.o $(CSRC)/optim_groups.o $(CSRC)/grad_norm.o $(CSRC)/weight_avg.o $(CSRC)/nms.o $(CSRC)/keypoint_eval.o $(CSRC)/oks_merge.o $(CSRC)/conditions.o $(CSRC)/sample.o $(CSRC)/synth.o $(CSRC)/synth_diag.o $(CSRC)/vis.o $(CSRC)/vis_pose.o $(CSRC)/error.o
 
 all: $(OUT)
 

@@ -340,6 +340,7 @@ SIGNATURES = {
     "buctd_kpt_rescore": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P]),
     "buctd_oks_nms_grouped": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, _I, _D, _P, _P]),
     "buctd_soft_oks_nms_grouped": (_I, [_P, _I, _P, _P, _P, _P, _I, _D, _I, _I, _D, _I, _P, _P, _P]),
+    "buctd_oks_merge_grouped": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _D, _I, _D, _P, _P, _P, _P]),
     "buctd_coco_kpt_match_workspace": (_SZ, [_L, _I, _I]),
     "buctd_coco_kpt_match": (_I, [C.POINTER(KptMatchArgs), _P, _SZ, _P]),
     "buctd_kpt_crowding": (_I, [_P, _I, _L, _I, _P, _P, _P, _P, _D, _P, _P, _P]),

@@ -87,7 +87,8 @@ class KeypointEvaluator:
     oks_nms (dataloader.py:614-625) - at most max_dets persons per image are chosen by decayed scores (`tables` gains
     soft_rank / soft_score per input row); the scores that are written and matched stay the rescored ones.  img_path entries are mapped to image ids through `image_ids`, a
     dict or callable path -> id; by default the dict {join(image_dir, file_name): id} of gt['images'].
-    `tables` holds what the last call produced."""
+    `tables` holds what the last call produced.  evaluate_merged(cfg, sets, output_dir, epoch) scores an ensemble of
+    prediction sets, merged per image by the reference's oks_merge on the device."""
 
     def __init__(self, gt, sigmas=None, nms_sigmas=None, oks_thre=0.5, in_vis_thre=0.0, use_nms=True, max_dets=20,
                  device=None, *, image_dir='', image_ids=None, soft_nms=False, nms_in_vis_thre=None, mode='val',
@@ -257,8 +258,78 @@ class KeypointEvaluator:
         return oks_offsets, oks, dt_matched, dt_ignored
 
     def evaluate(self, cfg, preds, output_dir, all_boxes, img_path, epoch=-1, *args, **kwargs):
+        return self._finish(cfg, self._kept_persons(preds, all_boxes, img_path), img_path, output_dir, epoch)
+
+    def evaluate_merged(self, cfg, sets, output_dir, epoch=-1, *, min_oks_thres=0.5, merge_in_vis_thre=None):
+        """evaluate() of an ensemble: sets = [(preds, all_boxes, img_path), ...] in priority order, each a table like
+        evaluate()'s.  Every set is rescored and suppressed on its own, as configured; its kept persons are level l of
+        their image, and one launch of nms.oks_merge_grouped chains the reference's oks_merge (lib/nms/nms.py:127-148)
+        over the levels: a person of a later set is accepted iff its largest OKS to the accepted persons of the earlier
+        sets in its image is <= min_oks_thres (areas all_boxes[:, 4], nms_sigmas - the merge is a suppression;
+        merge_in_vis_thre: joint-score threshold on the accepted pose, none by default).  The accepted persons of an image
+        are ordered by rescored score (equal scores: by level, then by position within the set's own order), cut at
+        max_dets, matched and summarised as in evaluate(); the results file holds them, within an image in that order
+        (with one set and use_nms=False: in input order, like evaluate()).  Rows are those of the concatenated sets.
+        `tables` gains per row: level, merge_keep (accepted by the merge; False where the set's own suppression dropped
+        the row, which then never entered the merge), merge_max_oks and merge_best (the row that gave it, or -1).
+        With one set every figure, table and the results file equal evaluate()'s."""
         import torch
-        p = self._kept_persons(preds, all_boxes, img_path)
+        from ..nms.nms import oks_merge_grouped
+        sets = list(sets)
+        if not sets:
+            raise ValueError("evaluate_merged needs at least one (preds, all_boxes, img_path) set")
+        ps = [self._kept_persons(*s) for s in sets]
+        L, I, dev = len(ps), len(self.image_ids), self.device
+        sizes = [q['preds'].shape[0] for q in ps]
+        base = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        N = int(base[-1])
+        cat = lambda k: np.concatenate([q[k] for q in ps])
+        all_boxes, score_h = cat('all_boxes'), cat('score_h')
+        # per position of the sets' grouped orders, one after the other: input row, level, position, image, kept by its set
+        row_g = np.concatenate([base[l] + q['order_h'] for l, q in enumerate(ps)]).astype(np.int64)
+        lvl_g = np.repeat(np.arange(L, dtype=np.int64), sizes)
+        pos_g = np.concatenate([np.arange(n, dtype=np.int64) for n in sizes])
+        img_g = np.concatenate([q['img'][q['order_h']] for q in ps]).astype(np.int64)
+        kept_g = cat('keep_h')
+        # the merge: kept persons in cells, image-major and level-major, within a cell in the set's own order
+        cell_order = np.lexsort((pos_g, lvl_g, img_g))
+        m_idx = cell_order[kept_g[cell_order]]
+        cells = np.concatenate([[0], np.cumsum(np.bincount(img_g[m_idx] * L + lvl_g[m_idx], minlength=I * L))])
+        rows_m = row_g[m_idx]
+        with torch.cuda.device(dev):
+            kp_g = torch.cat([q['kp_s'] for q in ps])
+            keep_m, max_m, best_m = oks_merge_grouped(
+                torch.as_tensor(cells.astype(np.int32)), L, kp_g[torch.as_tensor(m_idx).to(dev)],
+                torch.as_tensor(np.ascontiguousarray(all_boxes[rows_m, 4])).to(dev), self._d['nms_sigmas'], min_oks_thres,
+                in_vis_thre=merge_in_vis_thre)
+            keep_m, max_m, best_m = keep_m.cpu().numpy() != 0, max_m.cpu().numpy(), best_m.cpu().numpy()
+        level, merge_keep = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=bool)
+        merge_max_oks, merge_best = np.full(N, -1.0), np.full(N, -1, dtype=np.int64)
+        level[row_g] = lvl_g
+        merge_keep[rows_m], merge_max_oks[rows_m] = keep_m, max_m
+        merge_best[rows_m] = np.where(best_m >= 0, rows_m[np.maximum(best_m, 0)], -1) if rows_m.size else rows_m
+        # the merged set in evaluate()'s grouped form: images by id, within an image by score, then level, then position
+        accepted_g = np.zeros(N, dtype=bool)
+        accepted_g[m_idx] = keep_m
+        final = np.lexsort((pos_g, lvl_g, -score_h[row_g], img_g))
+        counts = np.sum([q['counts'] for q in ps], axis=0)
+        with torch.cuda.device(dev):
+            kp_s = kp_g[torch.as_tensor(final).to(dev)].contiguous()
+        p = dict(preds=cat('preds'), all_boxes=all_boxes, person_image_id=[i for q in ps for i in q['person_image_id']],
+                 img=cat('img'), order_h=row_g[final], keep_h=accepted_g[final],
+                 offsets=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), counts=counts, kp_s=kp_s,
+                 score_h=score_h, box_score_h=cat('box_score_h'), kpt_score_h=cat('kpt_score_h'))
+        if self.suppression == 'soft':
+            p.update(soft_rank_s=cat('soft_rank_s')[final], soft_score_s=cat('soft_score_s')[final])
+        img_path = [path for s in sets for path in s[2]]
+        return self._finish(cfg, p, img_path, output_dir, epoch, by_score=self.use_nms or L > 1,
+                            extra=dict(level=level, merge_keep=merge_keep, merge_max_oks=merge_max_oks,
+                                       merge_best=merge_best))
+
+    def _finish(self, cfg, p, img_path, output_dir, epoch, by_score=None, extra=None):
+        """Steps 3-5 of evaluate() on what _kept_persons returned: the detections, the matching, the figures, `tables` and
+        the results file."""
+        import torch
         preds, all_boxes, person_image_id = p['preds'], p['all_boxes'], p['person_image_id']
         N, I, dev = preds.shape[0], len(self.image_ids), self.device
         order_h, keep_h, offsets, counts, score_h = p['order_h'], p['keep_h'], p['offsets'], p['counts'], p['score_h']
@@ -293,21 +364,24 @@ class KeypointEvaluator:
             soft_rank, soft_score = np.full(N, -1, dtype=np.int32), np.zeros(N)
             soft_rank[order_h], soft_score[order_h] = p['soft_rank_s'], p['soft_score_s']
             self.tables.update(soft_rank=soft_rank, soft_score=soft_score)
+        if extra:
+            self.tables.update(extra)
         if output_dir:
-            self._write_results(cfg, output_dir, epoch, preds, all_boxes, img_path, person_image_id)
+            self._write_results(cfg, output_dir, epoch, preds, all_boxes, img_path, person_image_id,
+                                self.use_nms if by_score is None else by_score)
         name_value = OrderedDict(zip(STATS_NAMES, stats))
         return name_value, name_value['AP']
 
-    def _write_results(self, cfg, output_dir, epoch, preds, all_boxes, img_path, person_image_id):
+    def _write_results(self, cfg, output_dir, epoch, preds, all_boxes, img_path, person_image_id, by_score):
         """The reference's results file (dataloader.py:541-553, 652-717): the kept persons, images in order of first
-        appearance; within an image by score where the suppression ran, in input order where it did not."""
+        appearance; within an image by score where a suppression or a merge ran (by_score), in input order where not."""
         res_file = getattr(cfg, 'OUTPUT_JSON', '') if cfg is not None else ''
         if not res_file:
             res_folder = os.path.join(output_dir, 'results')
             os.makedirs(res_folder, exist_ok=True)
             res_file = os.path.join(res_folder, 'keypoints_{}_results_epoch{}.json'.format(self.mode, epoch))
         t = self.tables
-        rows = t['order'][t['keep'][t['order']]] if self.use_nms else np.arange(preds.shape[0])
+        rows = t['order'][t['keep'][t['order']]] if by_score else np.arange(preds.shape[0])
         first = {}
         for r in range(preds.shape[0]):
             first.setdefault(person_image_id[r], len(first))

@@ -258,3 +258,108 @@ def gpu_soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0
     taken = torch.nonzero(rank >= 0).reshape(-1)
     taken = taken[torch.argsort(rank[taken])]
     return order[taken].cpu().numpy().astype(np.intp)
+
+
+# ---- OKS merge of prioritised prediction sets (csrc/oks_merge.hip)
+def _merge_images(cells, levels, N):
+    """The number of images a cell table [images * levels + 1] describes; its values are checked, they index memory."""
+    L = int(levels)
+    if L <= 0:
+        raise ValueError(f"levels is {levels!r}, expected at least one priority level")
+    if len(cells.shape) != 1 or cells.shape[0] < 1 or (cells.shape[0] - 1) % L:
+        raise ValueError(f"cells is {tuple(cells.shape)}, expected [images * {L} + 1]")
+    if int(cells[0]) != 0 or int(cells[-1]) != N or bool((cells[1:] < cells[:-1]).any()):
+        raise ValueError(f"cells does not ascend from 0 to the {N} persons")
+    return (int(cells.shape[0]) - 1) // L
+
+
+def oks_merge_levels(cells, kpts, areas, sigmas, thresh, in_vis_thre=None, levels=2):
+    """`merged = level 0; for l in 1 .. levels - 1: merged = oks_merge(level l, merged)` for every image, as one host
+    function on the layout of buctd_oks_merge_grouped - the statement the device is tested against.  Persons in grouped
+    order (image-major, within an image level-major, level 0 the highest priority); cells int [images * levels + 1], the
+    CSR offsets over the (image, level) cells; kpts [N][K][3], areas [N], sigmas [K].  Returns (keep int32 [N], max_oks
+    fp64 [N], best int32 [N]): a person of level l >= 1 is kept iff its largest OKS (oks_iou, g the person, d the kept
+    persons of the levels < l of its image) is <= thresh or there is no such person; max_oks is that OKS, best the
+    grouped index that gave it (the lowest of equal ones); -1.0 / -1 for level 0 and where nothing precedes."""
+    kpts = np.asarray(kpts, dtype=np.float64)
+    if kpts.ndim != 3 or kpts.shape[2] != 3:
+        raise ValueError(f"kpts is {kpts.shape}, expected [N, K, 3]")
+    N, K = kpts.shape[0], kpts.shape[1]
+    areas = np.asarray(areas, dtype=np.float64).reshape(-1)
+    sigmas = np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    if areas.shape[0] != N or sigmas.shape[0] != K:
+        raise ValueError(f"areas ({areas.shape[0]}) / sigmas ({sigmas.shape[0]}) do not describe {N} persons with {K} key "
+                         f"points")
+    cells = np.asarray(cells, dtype=np.int64)
+    images, L = _merge_images(cells, levels, N), int(levels)
+    flat = kpts.reshape(N, K * 3)
+    keep, max_oks, best = np.ones(N, dtype=np.int32), np.full(N, -1.0), np.full(N, -1, dtype=np.int32)
+    for i in range(images):
+        cell = cells[i * L:i * L + L + 1]
+        merged = np.arange(cell[0], cell[1])
+        for l in range(1, L):
+            if merged.size:
+                for c in range(cell[l], cell[l + 1]):
+                    oks = oks_iou(flat[c], flat[merged], areas[c], areas[merged], sigmas, in_vis_thre)
+                    at = int(np.argmax(oks))
+                    keep[c], max_oks[c], best[c] = oks[at] <= thresh, oks[at], merged[at]
+            level = np.arange(cell[l], cell[l + 1])
+            merged = np.concatenate([merged, level[keep[level] != 0]])
+    return keep, max_oks, best
+
+
+def oks_merge_grouped(cells, levels, kpts, areas, sigmas, thresh, *, in_vis_thre=None):
+    """OKS merge of every image and every priority level at once (buctd_oks_merge_grouped, one wavefront per image).
+    Device tensors in the layout of oks_merge_levels: cells int32 [images * levels + 1], kpts float32 [N][K][3], areas
+    fp64 [N], sigmas fp64 [K].  Returns (keep int32 [N], max_oks fp64 [N], best int32 [N])."""
+    import torch
+    from .._C import check, lib, ptr, stream_ptr
+    if kpts.dim() != 3 or kpts.shape[2] != 3:
+        raise ValueError(f"kpts is {tuple(kpts.shape)}, expected [N, K, 3]")
+    N, K = int(kpts.shape[0]), int(kpts.shape[1])
+    if areas.numel() != N or sigmas.numel() != K:
+        raise ValueError(f"areas ({areas.numel()}) / sigmas ({sigmas.numel()}) do not describe {N} persons with {K} key "
+                         f"points")
+    images, L = _merge_images(cells, levels, N), int(levels)
+    dev = kpts.device
+    with torch.cuda.device(dev):
+        f64 = lambda t: t.to(dev, torch.float64).contiguous()
+        cell_t = cells.to(dev, torch.int32).contiguous()
+        kp_t = kpts.to(torch.float32).contiguous()
+        area_t, sig_t = f64(areas), f64(sigmas)
+        keep = torch.ones(N, dtype=torch.int32, device=dev)
+        max_oks = torch.full((N,), -1.0, dtype=torch.float64, device=dev)
+        best = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        if N and images:
+            use_vis = in_vis_thre is not None
+            check(lib().buctd_oks_merge_grouped(ptr(cell_t), images, L, N, ptr(kp_t), ptr(area_t), ptr(sig_t), K,
+                                                float(thresh), int(use_vis), float(in_vis_thre) if use_vis else 0.0,
+                                                ptr(keep), ptr(max_oks), ptr(best), stream_ptr()), "oks_merge_grouped")
+    return keep, max_oks, best
+
+
+def gpu_oks_merge(kpts_db_mode0, kpts_db_mode1, min_oks_thres=0.5, sigmas=None, in_vis_thre=None, device_id=0):
+    """oks_merge on the device (oks_merge_grouped over one image with two levels: mode 1 is level 0, mode 0 the
+    candidates).  Same returns: kpts_db_mode0 when mode 1 is empty, otherwise kpts_db_mode1 itself, extended in place by
+    the mode-0 poses it accepts, in mode-0 order.  The key points enter as float32."""
+    if len(kpts_db_mode1) == 0:
+        return kpts_db_mode0
+    if len(kpts_db_mode0) == 0:
+        return kpts_db_mode1
+    import torch
+    _, k0, a0 = _db_arrays(kpts_db_mode0)
+    _, k1, a1 = _db_arrays(kpts_db_mode1)
+    n1, n0 = k1.shape[0], k0.shape[0]
+    kpts = np.concatenate([k1, k0]).reshape(n1 + n0, -1, 3)
+    sig = COCO_SIGMAS if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    if sig.shape[0] != kpts.shape[1]:
+        raise ValueError(f"sigmas has {sig.shape[0]} entries, the poses {kpts.shape[1]} key points")
+    dev = torch.device("cuda", device_id)
+    t = lambda a, dt: torch.as_tensor(np.array(a, dtype=dt)).to(dev)
+    keep, _, _ = oks_merge_grouped(torch.tensor([0, n1, n1 + n0], dtype=torch.int32), 2, t(kpts, np.float32),
+                                   t(np.concatenate([a1, a0]), np.float64), t(sig, np.float64), min_oks_thres,
+                                   in_vis_thre=in_vis_thre)
+    for i in np.flatnonzero(keep[n1:].cpu().numpy()):
+        kpts_db_mode1.append(kpts_db_mode0[i])
+    return kpts_db_mode1
+

@@ -1149,6 +1149,26 @@ int buctd_oks_nms_grouped(const int* offsets, int images, int max_per_image, con
 int buctd_soft_oks_nms_grouped(const int* offsets, int images, const float* kpts, const double* areas,
                                const double* scores, const double* sigmas, int K, double thresh, int decay_type,
                                int use_vis, double in_vis_thre, int max_keep, double* soft_score, int* rank, void* stream);
+/* OKS merge of prioritised prediction sets within every image (csrc/oks_merge.hip; oks_merge of lib/nms/nms.py:127-148
+ * chained over the levels: merged = level 0; for l = 1 .. levels - 1: merged = oks_merge(level l, merged)).  One
+ * wavefront per image.  The n persons are in grouped order, image-major and within an image level-major, level 0 the
+ * highest priority; cells int32 [images * levels + 1] are the CSR offsets over the (image, level) cells: persons
+ * [cells[i * levels + l], cells[i * levels + l + 1]) are level l of image i, cells[0] = 0, cells[images * levels] = n.
+ * Every level-0 person is accepted.  A person of level l >= 1 is accepted iff the largest OKS between it and the
+ * accepted persons of the levels < l of its image is <= thresh, or there is no such person.  Persons of one level are
+ * not compared with each other, and a rejected person takes part in no later comparison.  The OKS is that of
+ * buctd_oks_nms_grouped with the candidate as g and the accepted pose as d: use_vis / in_vis_thre look at the joint
+ * scores of the accepted pose (nms.py:142 into nms.py:90-91).
+ * kpts float32 [n][K][3], areas [n], sigmas [K].  Outputs, all written for every person: keep int32 [n] - 1 accepted,
+ * 0 rejected; max_oks [n] - the largest OKS found, -1.0 for level 0 and where no accepted person precedes; best int32
+ * [n] - the grouped index of the accepted person that gave max_oks, the lowest among equal values, -1 where max_oks is
+ * -1.0.  A NaN OKS makes max_oks NaN (best: the first pose that gave one) and rejects the person, like numpy's max.
+ * No workspace, no LDS, no atomics; persons per cell, levels and K are unbounded.
+ * BUCTD_EINVAL before any launch: images < 0, levels <= 0, n < 0, K <= 0, images * levels >= 2^31 - 1, a NULL pointer.
+ * images == 0 or n == 0: success, nothing is launched. */
+int buctd_oks_merge_grouped(const int* cells, int images, int levels, int n, const float* kpts, const double* areas,
+                            const double* sigmas, int K, double thresh, int use_vis, double in_vis_thre, int* keep,
+                            double* max_oks, int* best, void* stream);
 /* COCO keypoint matching, per image: (a) the D x G matrix of COCOeval.computeOks - variances (2 sigma)^2, denominator
  * gt area + spacing(1), the visible ground-truth joints where there are any, otherwise the distance to the doubled
  * box (x0 = bx - bw, x1 = bx + 2 bw, likewise y) - written row-major to oks + oks_offsets[image]; (b) the greedy

@@ -44,12 +44,15 @@ class FlatParams:
             raise ValueError("module has no parameters")
         dev = self.params[0].device
         self.offsets = {}
+        self._aligned = {}         # id(p) -> aligned_span(p)
         off = 0
         for p in self.params:
             if p.dtype != torch.float32 or p.device != dev:
                 raise ValueError("all parameters must be fp32 on one device")
+            end = off + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
             self.offsets[id(p)] = off
-            off += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            self._aligned[id(p)] = (off, end)
+            off = end
         self.numel = off
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
@@ -72,6 +75,23 @@ class FlatParams:
     def span(self, p):
         o = self.offsets[id(p)]
         return o, o + p.numel()
+
+    def aligned_span(self, p):
+        """p's slot of the arena: span(p) with the end rounded up to _ALIGN, i.e. with the padding behind it"""
+        return self._aligned[id(p)]
+
+    @staticmethod
+    def merge_spans(spans, keys=None):
+        """Ascending [start, end) spans -> (runs, the key of each run): spans that touch are merged into one run, except
+        where their keys differ (the grouped optimizers: a run belongs to one group)."""
+        runs, run_keys = [], []
+        for (s, e), k in zip(spans, keys if keys is not None else [None] * len(spans)):
+            if runs and runs[-1][1] == s and run_keys[-1] == k:
+                runs[-1] = (runs[-1][0], e)
+            else:
+                runs.append((s, e))
+                run_keys.append(k)
+        return runs, run_keys
 
     # ops.grad_target protocol -------------------------------------------------------------
     def __call__(self, p):
@@ -99,17 +119,8 @@ class FlatParams:
         (p.grad is not None) - torch.optim skips every other parameter entirely (no weight decay, no momentum), e.g.
         TransPose's frozen sine pos_embedding (transpose_h.py:129; a learnable one has a gradient like any weight) and
         constructed-but-unused modules.  One run when every parameter has a gradient (the usual case)."""
-        runs = []
-        for p in self.params:
-            if p.grad is None:
-                continue
-            s = self.offsets[id(p)]
-            e = s + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-            if runs and runs[-1][1] == s:
-                runs[-1][1] = e
-            else:
-                runs.append([s, e])
-        return [(s, e) for s, e in runs]
+        aligned = self._aligned
+        return self.merge_spans([aligned[id(p)] for p in self.params if p.grad is not None])[0]
 
 
 class _GradClip:
@@ -243,44 +254,83 @@ class _ParamGroups:
         if key == self._live_key:
             return self._live
         flat = self.flat
-        runs, owners, merged, ids = [], [], [], set()
-        for p, gi in self._members:
-            if p.grad is None:
-                continue
-            s = flat.offsets[id(p)]
-            e = s + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-            if runs and runs[-1][1] == s and owners[-1] == gi:
-                runs[-1][1] = e
-            else:
-                runs.append([s, e])
-                owners.append(gi)
-            if merged and merged[-1][1] == s:
-                merged[-1][1] = e
-            else:
-                merged.append([s, e])
-            ids.add(id(p))
+        live = [(p, gi) for p, gi in self._members if p.grad is not None]
+        spans = [flat.aligned_span(p) for p, _ in live]
+        runs, owners = flat.merge_spans(spans, [gi for _, gi in live])      # the chunk table: a run belongs to one group
         table = None
         if runs:
             table = ops.step_chunk_table(ops.step_chunks(runs, owners, flat.numel), flat.flat.device)
             self.table_builds += 1
-        self._live = _Live(table, [(s, e) for s, e in merged], sorted(set(owners)), ids)
+        self._live = _Live(table, flat.merge_spans(spans)[0], sorted(set(owners)), {id(p) for p, _ in live})
         self._live_key = key
         return self._live
 
-    def _after_step(self):
-        ops.weights_updated()
-        ops.refresh_prepared(self.flat.flat.device)
-        if self.flat.flat.is_cuda:
-            ops.acc_pool.reset(self.flat.flat.device)
 
-    def _grouped_state_dict(self, per_param, torch_class):
-        fill = torch_class([torch.zeros(1)], lr=1e-3).defaults      # the keys this torch's optimizer reads from a group
+class _FusedOptimizer(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: the arena, step() around their launches, zero_grad() and torch's checkpoint format
+    in both directions.  For a checkpoint the plain form is one group that holds every arena parameter.  A subclass names
+    its state arenas (_slots) and supplies the launches and the checkpoint hooks listed at the end of this class."""
+
+    avg = None      # the engine.WeightAverage attached to this optimizer: step() ends with avg.update()
+    _slots = ()     # (key of torch's per-parameter state, attribute that holds its arena - laid out like the parameters)
+
+    def __init__(self, flat, groups, defaults, grad_sync, max_grad_norm):
+        """groups: torch's param_groups for the grouped form (_ParamGroups), None for the plain one"""
+        if not isinstance(flat, FlatParams):
+            raise TypeError(f"{type(self).__name__} works on an engine.FlatParams arena")
+        self.grouped = groups is not None
+        if self.grouped:
+            groups, owner = self._check_groups(flat, groups, grad_sync)
+        super().__init__(groups if self.grouped else flat.params, defaults)
+        self.flat = flat
+        if self.grouped:
+            self._init_groups(owner)
+        self._init_clip(flat, max_grad_norm)       # the gradient-norm clip folded into step(): _NormClipOption
+        self.grad_sync = grad_sync  # callable returning the gradient scale (1/world) after syncing
+        self.step_count = 0
+        self.zeroed = 0             # zero_grad() calls (StepGraph: the gradient views a capture installed are gone)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise NotImplementedError("closures are not used on the BUCTD path")
+        flat = self.flat
+        flat.collect()
+        gscale = self.grad_sync() if self.grad_sync is not None else 1.0
+        if self.grouped:
+            live = self._live_set()
+            coef = self._clip_coef(gscale, live.runs)
+            self.step_count += 1
+            written = live.table is not None       # no group member holds a gradient: torch's optimizers do nothing either
+            if written:
+                self._stepped |= live.ids
+                self._step_groups(live, gscale, coef)
+        else:
+            self._step_plain(gscale, self._clip_coef(gscale))
+            written = True
+        if written:
+            ops.weights_updated()  # the kernel wrote the parameters through raw pointers: prepared filter images are stale
+            ops.refresh_prepared(flat.flat.device)    # ... and are rebuilt here, by one launch behind the step kernel
+            if flat.flat.is_cuda:
+                ops.acc_pool.reset(flat.flat.device)  # BatchNorm accumulators of the step: one fill, every stream is joined here
+        if self.avg is not None:
+            self.avg.update()      # the averaged weights follow the step: one launch behind it (WeightAverage)
+
+    def zero_grad(self, set_to_none=True):
+        self.zeroed += 1
+        for p in self.flat.params:
+            p.grad = None
+
+    def state_dict(self):
+        """torch's checkpoint format: the per-parameter state keyed by the parameter's index in the concatenation of the
+        param_groups, and the groups with every key that torch's optimizer reads from one."""
+        fill = self._group_defaults()
         state, groups, idx = {}, [], 0
         for gi, g in enumerate(self.param_groups):
             ids = []
             for p in g["params"]:
-                if id(p) in self._stepped:
-                    state[idx] = per_param(p, gi)
+                if self._has_state(p, gi):
+                    state[idx] = self._param_state(p, gi)
                 ids.append(idx)
                 idx += 1
             d = {k: v for k, v in g.items() if k != "params"}
@@ -290,25 +340,74 @@ class _ParamGroups:
             groups.append(d)
         return {"state": state, "param_groups": groups}
 
-    def _grouped_entries(self, sd):
-        """[(group index, parameter, its state or None)] of a torch-format state_dict with this optimizer's group layout"""
+    def load_state_dict(self, sd):
+        """Takes a state_dict of the matching torch optimizer (the grouped form: with the same groups).  Everything is
+        checked before anything is written; a parameter that comes without state gets zeros."""
+        for _, src in zip(self.param_groups, sd["param_groups"]):
+            self._refuse_group(src)
+        self._load_state(sd)
+        for g, src in zip(self.param_groups, sd["param_groups"]):
+            g.update({k: v for k, v in src.items() if k != "params"})
+
+    def _load_state(self, sd):
+        entries = self._entries(sd)
+        for _, p, st, label in entries:
+            for key, _ in self._slots if st is not None else ():
+                if tuple(st[key].shape) != tuple(p.shape):
+                    raise ValueError(f"optimizer state of parameter {label}: shape {tuple(st[key].shape)} != {tuple(p.shape)}")
+        self._load_counters(entries)
+        for key, attr in self._slots:
+            arena = getattr(self, attr)
+            for _, p, st, _ in entries if arena is not None else ():
+                view = self.flat._view(arena, p)
+                if st is None:
+                    view.zero_()
+                else:
+                    view.copy_(st[key])
+        if self.grouped:
+            self._stepped = {id(p) for _, p, st, _ in entries if st is not None}
+
+    def _entries(self, sd):
+        """[(group index, parameter, its state or None, the parameter's name in a message)] of a torch-format state_dict.
+        The grouped form wants its own group layout; the plain form reads the state by arena index."""
+        who, state = type(self).__name__, sd.get("state", {})
+
+        def state_of(i):
+            st = state.get(i, state.get(str(i)))
+            return None if st is None or all(st.get(key) is None for key, _ in self._slots) else st
+        if not self.grouped:
+            return [(0, p, state_of(i), i) for i, p in enumerate(self.flat.params)]
         if "state" not in sd or len(sd["param_groups"]) != len(self.param_groups):
-            raise ValueError(f"{type(self).__name__}: the state_dict has {len(sd.get('param_groups', []))} parameter groups, "
-                             f"this optimizer {len(self.param_groups)}")
+            raise ValueError(f"{who}: the state_dict has {len(sd.get('param_groups', []))} parameter groups, this optimizer "
+                             f"{len(self.param_groups)}")
         out = []
         for gi, (g, src) in enumerate(zip(self.param_groups, sd["param_groups"])):
             if len(src["params"]) != len(g["params"]):
-                raise ValueError(f"{type(self).__name__}: group {gi} of the state_dict has {len(src['params'])} parameters, "
-                                 f"this optimizer's {len(g['params'])}")
-            for p, i in zip(g["params"], src["params"]):
-                out.append((gi, p, sd["state"].get(i, sd["state"].get(str(i)))))
+                raise ValueError(f"{who}: group {gi} of the state_dict has {len(src['params'])} parameters, this optimizer's "
+                                 f"{len(g['params'])}")
+            out += [(gi, p, state_of(i), repr(self.flat.names.get(id(p), "?"))) for p, i in zip(g["params"], src["params"])]
         return out
 
-    def _arena_view(self, arena, p):
-        return torch.as_strided(arena, p.shape, p.stride(), self.flat.offsets[id(p)])
+    def _has_state(self, p, gi):
+        """whether a checkpoint carries state for p: torch keeps state for the parameters it has stepped"""
+        return id(p) in self._stepped if self.grouped else self.step_count > 0
+
+    def _param_state(self, p, gi):
+        return {key: self.flat._view(getattr(self, attr), p).clone() for key, attr in self._slots}
+
+    # What a subclass supplies:
+    #   _step_plain(gscale, coef)         count the step and launch it over the arena
+    #   _step_groups(live, gscale, coef)  count the step of the groups live.groups, launch it over the chunk table live.table
+    #   _group_defaults()                 the keys a written param_group gets where it lacks them
+    #   _refuse_group(src)                ValueError for a loaded param_group that asks for what the class does not implement
+    #   _load_counters(entries)           refuse state the class cannot hold, then set the step counters from it
 
 
-class FusedAdam(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
+def _torch_defaults(torch_class):
+    return torch_class([torch.zeros(1)], lr=1e-3).defaults      # the keys this torch's optimizer reads from a group
+
+
+class FusedAdam(_FusedOptimizer):
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) semantics on the flat arena.
 
     One step counter for the whole arena, and every step updates the whole arena: a parameter without a gradient is stepped
@@ -328,176 +427,82 @@ class FusedAdam(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     per parameter) - put parameters that are unfrozen at different times into different groups.  Without groups and with
     weight_decay 0 nothing of this applies: the class is the plain one above."""
 
-    avg = None      # the engine.WeightAverage attached to this optimizer: step() ends with avg.update()
+    _slots = (("exp_avg", "exp_avg"), ("exp_avg_sq", "exp_avg_sq"))
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_sync=None, max_grad_norm=None, *, groups=None,
                  weight_decay=0.0, decoupled_weight_decay=False):
-        if not isinstance(flat, FlatParams):
-            raise TypeError("FusedAdam works on an engine.FlatParams arena")
-        self.grouped = groups is not None or weight_decay != 0
+        defaults = dict(lr=lr, betas=betas, eps=eps)
+        if groups is None and weight_decay != 0 and isinstance(flat, FlatParams):
+            groups = [{"params": flat.params}]     # a decay makes one group of every parameter
+        if groups is not None:
+            defaults.update(weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay))
+        super().__init__(flat, groups, defaults, grad_sync, max_grad_norm)
         if self.grouped:
-            groups, owner = self._check_groups(flat, [{"params": flat.params}] if groups is None else groups, grad_sync)
-            super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                          decoupled_weight_decay=bool(decoupled_weight_decay)))
-            self.flat = flat
-            self._init_groups(owner)
             self.group_steps = [0] * len(self.param_groups)
-        else:
-            super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps))
-        self.flat = flat
-        self._init_clip(flat, max_grad_norm)       # the gradient-norm clip folded into step(): _NormClipOption
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self.step_count = 0
-        self.grad_sync = grad_sync  # callable returning the gradient scale (1/world) after syncing
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        if closure is not None:
-            raise NotImplementedError("closures are not used on the BUCTD path")
-        self.flat.collect()
-        gscale = self.grad_sync() if self.grad_sync is not None else 1.0
-        if self.grouped:
-            self._step_groups(gscale)
-        else:
-            self._step_plain(gscale)
-        if self.avg is not None:
-            self.avg.update()      # the averaged weights follow the step: one launch behind it (WeightAverage)
-
-    def _step_plain(self, gscale):
-        coef = self._clip_coef(gscale)
+    def _step_plain(self, gscale, coef):
         self.step_count += 1
         g = self.param_groups[0]
         ops.adam_step(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
                       g["betas"][1], g["eps"], self.step_count, gscale, coef)
-        ops.weights_updated()  # the kernel wrote the parameters through raw pointers: prepared filter images are stale
-        ops.refresh_prepared(self.flat.flat.device)   # ... and are rebuilt here, by one launch behind the Adam kernel
-        if self.flat.flat.is_cuda:
-            ops.acc_pool.reset(self.flat.flat.device)  # BatchNorm accumulators of the step: one fill, every stream is joined here
 
-    def _step_groups(self, gscale):
-        live = self._live_set()
-        coef = self._clip_coef(gscale, live.runs)
-        self.step_count += 1
-        if live.table is None:         # no group member holds a gradient: torch.optim.Adam does nothing either
-            return
+    def _step_groups(self, live, gscale, coef):
         for gi in live.groups:
             self.group_steps[gi] += 1
-        self._stepped |= live.ids
         table = (_C.AdamGroup * len(self.param_groups))()
         for t, g, n in zip(table, self.param_groups, self.group_steps):
             t.lr, t.beta1, t.beta2, t.eps, t.weight_decay = g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]
             t.decoupled, t.step = int(bool(g["decoupled_weight_decay"])), n
         ops.adam_step_groups(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, live.table, table, gscale, coef)
-        self._after_step()
 
-    def zero_grad(self, set_to_none=True):
-        self.zeroed = getattr(self, "zeroed", 0) + 1      # (StepGraph: the gradient views a capture installed are gone)
-        for p in self.flat.params:
-            p.grad = None
+    # Checkpoints: torch.optim.Adam's format (what the reference stores under checkpoint['optimizer'], tools/train.py:243-266),
+    # per-parameter 'step' / 'exp_avg' / 'exp_avg_sq'; a parameter's step is its group's counter (the plain form: the arena's).
+    # Loading accepts a torch.optim.Adam state_dict (reference checkpoints) or this class's round-1 flat format; the grouped
+    # form a torch.optim.Adam / AdamW state_dict with the same groups.
+    def _param_state(self, p, gi):
+        step = self.group_steps[gi] if self.grouped else self.step_count
+        return {"step": torch.tensor(float(step)), **super()._param_state(p, gi)}
 
-    def _state_dict_groups(self):
-        def per_param(p, gi):
-            return {"step": torch.tensor(float(self.group_steps[gi])), "exp_avg": self._arena_view(self.exp_avg, p).clone(),
-                    "exp_avg_sq": self._arena_view(self.exp_avg_sq, p).clone()}
+    def _group_defaults(self):
+        if not self.grouped:
+            return {"weight_decay": 0, "amsgrad": False, "maximize": False}
         decoupled = any(g["decoupled_weight_decay"] for g in self.param_groups)
-        return self._grouped_state_dict(per_param, torch.optim.AdamW if decoupled else torch.optim.Adam)
+        return _torch_defaults(torch.optim.AdamW if decoupled else torch.optim.Adam)
 
-    def _load_state_dict_groups(self, sd):
-        entries = self._grouped_entries(sd)
-        for src in sd["param_groups"]:
-            for k in ("amsgrad", "maximize"):
-                if src.get(k):
-                    raise ValueError(f"FusedAdam does not implement {k}")
+    def _refuse_group(self, src):
+        if not self.grouped and src.get("weight_decay", 0) not in (0, 0.0):
+            raise ValueError("FusedAdam implements Adam without weight decay (the BUCTD recipe)")
+        for k in ("amsgrad", "maximize"):
+            if src.get(k):
+                raise ValueError(f"FusedAdam does not implement {k}")
+
+    def _load_state(self, sd):
+        if self.grouped or "state" in sd:
+            return super()._load_state(sd)
+        self.step_count = int(sd["step"])          # round-1 private format: flat arenas
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+
+    def _load_counters(self, entries):
         steps = [set() for _ in self.param_groups]
-        for gi, p, st in entries:
+        for gi, _, st, _ in entries:
             if st is not None:
-                for name in ("exp_avg", "exp_avg_sq"):
-                    if tuple(st[name].shape) != tuple(p.shape):
-                        raise ValueError(f"optimizer state of parameter {self.flat.names.get(id(p), '?')!r}: shape "
-                                         f"{tuple(st[name].shape)} != {tuple(p.shape)}")
                 steps[gi].add(int(float(st["step"])))
         for gi, ss in enumerate(steps):
+            if len(ss) > 1 and not self.grouped:
+                raise ValueError("FusedAdam keeps one step counter: per-parameter steps differ in this state_dict")
             if len(ss) > 1:
                 raise ValueError(f"FusedAdam keeps one step counter per group: the steps of group {gi} differ in this "
                                  f"state_dict ({sorted(ss)})")
-        self._stepped = set()
-        for gi, p, st in entries:
-            for name, arena in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
-                view = self._arena_view(arena, p)
-                if st is None:
-                    view.zero_()
-                else:
-                    view.copy_(st[name])
-            if st is not None:
-                self._stepped.add(id(p))
-        self.group_steps = [ss.pop() if ss else 0 for ss in steps]
-        self.step_count = max(self.group_steps)
-        for g, src in zip(self.param_groups, sd["param_groups"]):
-            g.update({k: v for k, v in src.items() if k != "params"})
-
-    def state_dict(self):
-        """torch.optim.Adam's checkpoint format (what the reference stores under checkpoint['optimizer'],
-        tools/train.py:243-266): per-parameter 'step' / 'exp_avg' / 'exp_avg_sq' keyed by parameter index.  The grouped form
-        writes several param_groups, indices running over their concatenation, each parameter's step its group's counter."""
+        counts = [ss.pop() if ss else 0 for ss in steps]
         if self.grouped:
-            return self._state_dict_groups()
-        state = {}
-        if self.step_count > 0:
-            for i, p in enumerate(self.flat.params):
-                o, e = self.flat.span(p)
-                state[i] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": torch.as_strided(self.exp_avg, p.shape, p.stride(), o).clone(),
-                            "exp_avg_sq": torch.as_strided(self.exp_avg_sq, p.shape, p.stride(), o).clone()}
-        groups = []
-        for g in self.param_groups:
-            d = {k: v for k, v in g.items() if k != "params"}
-            for k, v in (("weight_decay", 0), ("amsgrad", False), ("maximize", False)):
-                d.setdefault(k, v)
-            d["params"] = list(range(len(self.flat.params)))
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        """Accepts a torch.optim.Adam state_dict (reference checkpoints) or this class's round-1 flat format; the grouped form
-        a torch.optim.Adam / AdamW state_dict with the same groups."""
-        if self.grouped:
-            return self._load_state_dict_groups(sd)
-        if "state" not in sd:                      # round-1 private format: flat arenas
-            self.step_count = int(sd["step"])
-            self.exp_avg.copy_(sd["exp_avg"])
-            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        else:
-            state = sd["state"]
-            steps = set()
-            self.exp_avg.zero_()
-            self.exp_avg_sq.zero_()
-            for i, p in enumerate(self.flat.params):
-                st = state.get(i, state.get(str(i)))
-                if st is None:
-                    continue
-                o, _ = self.flat.span(p)
-                for name, arena in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
-                    src = st[name]
-                    if tuple(src.shape) != tuple(p.shape):
-                        raise ValueError(f"optimizer state of parameter {i}: shape {tuple(src.shape)} != {tuple(p.shape)}")
-                    torch.as_strided(arena, p.shape, p.stride(), o).copy_(src)
-                steps.add(int(float(st["step"])))
-            if len(steps) > 1:
-                raise ValueError("FusedAdam keeps one step counter: per-parameter steps differ in this state_dict")
-            self.step_count = steps.pop() if steps else 0
-        for g, src in zip(self.param_groups, sd["param_groups"]):
-            for k, v in src.items():
-                if k == "params":
-                    continue
-                if k in ("weight_decay",) and v not in (0, 0.0):
-                    raise ValueError("FusedAdam implements Adam without weight decay (the BUCTD recipe)")
-                if k in ("amsgrad", "maximize") and v:
-                    raise ValueError(f"FusedAdam does not implement {k}")
-                g[k] = v
+            self.group_steps = counts
+        self.step_count = max(counts)
 
 
-class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
+class FusedSGD(_FusedOptimizer):
     """torch.optim.SGD(lr, momentum, weight_decay, nesterov) semantics on the flat arena (one kernel per step) - the 'sgd'
     branch of the reference's get_optimizer (lib/utils/utils.py:260-267).  Reads and writes torch.optim.SGD state_dicts.
 
@@ -505,50 +510,24 @@ class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
     (_ParamGroups): every group steps with its own values and a step is one launch however many gradient runs there are
     (the plain form launches once per run)."""
 
-    avg = None      # as in FusedAdam
+    _slots = (("momentum_buffer", "buf"),)
 
     def __init__(self, flat, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, grad_sync=None, max_grad_norm=None, *,
                  groups=None):
-        if not isinstance(flat, FlatParams):
-            raise TypeError("FusedSGD works on an engine.FlatParams arena")
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=nesterov)
-        self.grouped = groups is not None
-        if self.grouped:
-            groups, owner = self._check_groups(flat, groups, grad_sync)
-            super().__init__(groups, defaults)
-            self.flat = flat
-            self._init_groups(owner)
-            for gi, g in enumerate(self.param_groups):
-                if g["nesterov"] and g["momentum"] <= 0:
-                    raise ValueError(f"FusedSGD: group {gi}: Nesterov momentum requires a momentum and zero dampening")
-                if g["dampening"] not in (0, 0.0):
-                    raise ValueError(f"FusedSGD: group {gi}: dampening = 0 is what FusedSGD implements")
-            momentum = any(g["momentum"] for g in self.param_groups)
-        else:
-            super().__init__(flat.params, defaults)
-        self.flat = flat
-        self.buf = torch.zeros_like(flat.flat) if momentum else None
-        self.step_count = 0
-        self.grad_sync = grad_sync
-        self._init_clip(flat, max_grad_norm)
+        if groups is not None:
+            groups = [dict(g) for g in groups]
+        for gi, g in enumerate(groups or ()):
+            if g.get("nesterov", nesterov) and g.get("momentum", momentum) <= 0:
+                raise ValueError(f"FusedSGD: group {gi}: Nesterov momentum requires a momentum and zero dampening")
+            if g.get("dampening", 0) not in (0, 0.0):
+                raise ValueError(f"FusedSGD: group {gi}: dampening = 0 is what FusedSGD implements")
+        super().__init__(flat, groups, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=nesterov),
+                         grad_sync, max_grad_norm)
+        self.buf = torch.zeros_like(flat.flat) if any(g["momentum"] for g in self.param_groups) else None
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        if closure is not None:
-            raise NotImplementedError("closures are not used on the BUCTD path")
-        self.flat.collect()
-        gscale = self.grad_sync() if self.grad_sync is not None else 1.0
-        if self.grouped:
-            self._step_groups(gscale)
-        else:
-            self._step_plain(gscale)
-        if self.avg is not None:
-            self.avg.update()
-
-    def _step_plain(self, gscale):
-        coef = self._clip_coef(gscale)
+    def _step_plain(self, gscale, coef):
         g = self.param_groups[0]
         # torch.optim.SGD touches only parameters that hold a gradient: a parameter with p.grad None keeps its value (no
         # weight decay) and its momentum buffer.  A zero momentum buffer makes "buf = momentum * buf + g" the first-step
@@ -557,103 +536,37 @@ class FusedSGD(_NormClipOption, _ParamGroups, torch.optim.Optimizer):
             ops.sgd_step(self.flat.flat[s:e], self.flat.grad[s:e], None if self.buf is None else self.buf[s:e], g["lr"],
                          g["momentum"], g["weight_decay"], g["nesterov"], False, gscale, coef)
         self.step_count += 1
-        ops.weights_updated()
-        ops.refresh_prepared(self.flat.flat.device)
-        if self.flat.flat.is_cuda:
-            ops.acc_pool.reset(self.flat.flat.device)
 
-    def _step_groups(self, gscale):
-        live = self._live_set()
-        coef = self._clip_coef(gscale, live.runs)
-        self.step_count += 1
-        if live.table is None:
-            return
-        self._stepped |= live.ids
+    def _step_groups(self, live, gscale, coef):
         table = (_C.SgdGroup * len(self.param_groups))()
         for t, g in zip(table, self.param_groups):
             t.lr, t.momentum, t.weight_decay, t.nesterov = g["lr"], g["momentum"], g["weight_decay"], int(bool(g["nesterov"]))
         # a zero momentum buffer makes "buf = momentum * buf + g" the first-step "buf = g", as in the plain form
         ops.sgd_step_groups(self.flat.flat, self.flat.grad, self.buf, live.table, table, gscale, coef)
-        self._after_step()
-
-    def zero_grad(self, set_to_none=True):
-        self.zeroed = getattr(self, "zeroed", 0) + 1
-        for p in self.flat.params:
-            p.grad = None
-
-    def _state_dict_groups(self):
-        sd = self._grouped_state_dict(lambda p, gi: {"momentum_buffer": self._arena_view(self.buf, p).clone()}
-                                      if self.param_groups[gi]["momentum"] else None, torch.optim.SGD)
-        sd["state"] = {i: st for i, st in sd["state"].items() if st is not None}     # torch: no state without momentum
-        return sd
-
-    def _load_state_dict_groups(self, sd):
-        entries = self._grouped_entries(sd)
-        for gi, src in enumerate(sd["param_groups"]):
-            if src.get("dampening", 0) not in (0, 0.0):
-                raise ValueError("FusedSGD implements dampening = 0 (the reference's recipe)")
-            if src.get("maximize"):
-                raise ValueError("FusedSGD does not implement maximize")
-        if self.buf is None and any(st is not None and st.get("momentum_buffer") is not None for _, _, st in entries):
-            raise ValueError("FusedSGD was built without momentum but the state_dict carries momentum buffers")
-        self._stepped = set()
-        for gi, p, st in entries:
-            has = st is not None and st.get("momentum_buffer") is not None
-            if self.buf is not None:
-                view = self._arena_view(self.buf, p)
-                if has:
-                    view.copy_(st["momentum_buffer"])
-                else:
-                    view.zero_()
-            if has:
-                self._stepped.add(id(p))
-        self.step_count = 1 if self._stepped else 0
-        for g, src in zip(self.param_groups, sd["param_groups"]):
-            g.update({k: v for k, v in src.items() if k != "params"})
-        if self.buf is None and any(g["momentum"] for g in self.param_groups):
-            self.buf = torch.zeros_like(self.flat.flat)
-
-    def state_dict(self):
-        if self.grouped:
-            return self._state_dict_groups()
-        state = {}
-        if self.buf is not None and self.step_count > 0:
-            for i, p in enumerate(self.flat.params):
-                o, _ = self.flat.span(p)
-                state[i] = {"momentum_buffer": torch.as_strided(self.buf, p.shape, p.stride(), o).clone()}
-        groups = []
-        for g in self.param_groups:
-            d = {k: v for k, v in g.items() if k != "params"}
-            for k, v in (("maximize", False), ("foreach", None), ("differentiable", False), ("fused", None)):
-                d.setdefault(k, v)
-            d["params"] = list(range(len(self.flat.params)))
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
-        if self.grouped:
-            return self._load_state_dict_groups(sd)
-        state = sd.get("state", {})
-        loaded = 0
-        for i, p in enumerate(self.flat.params):
-            st = state.get(i, state.get(str(i)))
-            if st is None or st.get("momentum_buffer") is None:
-                continue
-            if self.buf is None:
-                raise ValueError("FusedSGD was built without momentum but the state_dict carries momentum buffers")
-            o, _ = self.flat.span(p)
-            torch.as_strided(self.buf, p.shape, p.stride(), o).copy_(st["momentum_buffer"])
-            loaded += 1
+        super().load_state_dict(sd)
+        if self.buf is None and any(g["momentum"] for g in self.param_groups):
+            self.buf = torch.zeros_like(self.flat.flat)    # a loaded group brought a momentum
+
+    def _has_state(self, p, gi):
+        momentum = self.param_groups[gi]["momentum"] if self.grouped else self.buf is not None
+        return bool(momentum) and super()._has_state(p, gi)        # torch: no state without momentum
+
+    def _group_defaults(self):
+        return _torch_defaults(torch.optim.SGD)    # the plain form lacks maximize, foreach, differentiable, fused
+
+    def _refuse_group(self, src):
+        if src.get("dampening", 0) not in (0, 0.0):
+            raise ValueError("FusedSGD implements dampening = 0 (the reference's recipe)")
+        if src.get("maximize"):
+            raise ValueError("FusedSGD does not implement maximize")
+
+    def _load_counters(self, entries):
+        loaded = any(st is not None for _, _, st, _ in entries)
+        if loaded and self.buf is None:
+            raise ValueError("FusedSGD was built without momentum but the state_dict carries momentum buffers")
         self.step_count = 1 if loaded else 0
-        for g, src in zip(self.param_groups, sd["param_groups"]):
-            for k, v in src.items():
-                if k == "params":
-                    continue
-                if k == "dampening" and v not in (0, 0.0):
-                    raise ValueError("FusedSGD implements dampening = 0 (the reference's recipe)")
-                if k == "maximize" and v:
-                    raise ValueError("FusedSGD does not implement maximize")
-                g[k] = v
 
 
 class GradBuckets:
@@ -672,8 +585,7 @@ class GradBuckets:
             cur_ids, cur_end = set(), None
 
         for p in reversed(flat.params):
-            s, _ = flat.span(p)
-            e = flat.offsets[id(p)] + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            s, e = flat.aligned_span(p)
             if e - s >= target:
                 # a tensor as large as a bucket (CoAM fc_o: 191 MB of the 462 MB) travels alone, so that its
                 # all-reduce starts the moment its gradient GEMM is enqueued instead of waiting for neighbours

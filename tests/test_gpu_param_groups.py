@@ -327,7 +327,7 @@ def compare_with_torch(kind, fused, ref, twins64, sim, start, index_groups, tag)
                                     ("exp_avg_sq", getattr(fused, "exp_avg_sq", None), sim.b)):
                 if st.get(key) is None or arena is None:
                     continue
-                x = fused._arena_view(arena, q).cpu().double()
+                x = fused.flat._view(arena, q).cpu().double()
                 sc = st[key].abs().max().clamp_min(1e-300)
                 err = ((x - st[key]).abs() / sc).max().item()
                 e32 = ((s32[i].double() - st[key]).abs() / sc).max().item()
@@ -360,7 +360,7 @@ def test_three_groups_against_torch_in_float64(dev, kind):
         arena = getattr(fused, name, None)
         if arena is not None:
             for i in frozen + ungrouped:
-                fused._arena_view(arena, flat.params[i]).fill_(0.25)
+                flat._view(arena, flat.params[i]).fill_(0.25)
     before = arenas(fused)
     start = [p.detach().clone() for p in net.parameters()]
     twins64 = [torch.nn.Parameter(p.detach().double().clone()) for p in net.parameters()]

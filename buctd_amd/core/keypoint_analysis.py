@@ -114,15 +114,15 @@ class CrowdingAnalysis:
         input row, image position, and the row of the annotation column 6 of all_boxes names (-1: none)."""
         ev = self.evaluator
         p = ev._kept_persons(preds, all_boxes, img_path)
-        pos = np.flatnonzero(p['keep_h'])
-        rows = p['order_h'][pos]
-        ann = p['all_boxes'][rows, 6].astype(np.int64)
+        pos = np.flatnonzero(p.keep_h)
+        rows = p.order_h[pos]
+        ann = p.all_boxes[rows, 6].astype(np.int64)
         gt = np.full(rows.shape[0], -1, dtype=np.int64)
         if ev.gt_ids.shape[0]:
             at = np.minimum(np.searchsorted(ev.gt_ids, ann, sorter=self._sorted_ids), ev.gt_ids.shape[0] - 1)
             cand = self._sorted_ids[at]
             gt = np.where(ev.gt_ids[cand] == ann, cand, -1)
-        return p, pos, rows, p['img'][rows], gt
+        return p, pos, rows, p.img[rows], gt
 
     def _cut(self, cand, key):
         """Candidates (indices into the kept persons, in their order) with a pseudo-image key each: sorted by key, equal keys
@@ -148,7 +148,7 @@ class CrowdingAnalysis:
         sel, key = self._cut(cand, b[cand] * I + img[cand])
         dt_counts = np.bincount(key, minlength=NB * I)
         with torch.cuda.device(dev):
-            dt_kpts = p['kp_s'][torch.as_tensor(pos[sel]).to(dev)].contiguous()
+            dt_kpts = p.kp_s[torch.as_tensor(pos[sel]).to(dev)].contiguous()
             _, _, dt_matched, dt_ignored = ev._match(dt_kpts, dt_counts, self._bin_gt_counts, gt=self._bin_gt_dev)
             dtm, dti = dt_matched.cpu().numpy(), dt_ignored.cpu().numpy()
         dt_end = np.cumsum(dt_counts.reshape(NB, I).sum(1))
@@ -162,7 +162,7 @@ class CrowdingAnalysis:
             gts = self._bin_gt[(int(gt_end[k - 1]) if k else 0):int(gt_end[k])]
             npig = np.count_nonzero(self._counts_in_range[gts], axis=0)
             dt_rows = rows[sel[d0:d1]]
-            precision, recall = accumulate(p['score_h'][dt_rows], dtm[:, :, d0:d1], dti[:, :, d0:d1], npig)
+            precision, recall = accumulate(p.score_h[dt_rows], dtm[:, :, d0:d1], dti[:, :, d0:d1], npig)
             stats = summarize(precision, recall)
             i, j = divmod(k, shape[1])
             tables['num_instances'][i, j] = gts.shape[0]
@@ -191,7 +191,7 @@ class CrowdingAnalysis:
         dt_counts = np.bincount(key, minlength=S)
         npig = np.ascontiguousarray(self._counts_in_range[self._seg_gt].astype(np.int32)).reshape(S, A)
         with torch.cuda.device(dev):
-            dt_kpts = p['kp_s'][torch.as_tensor(pos[sel]).to(dev)].contiguous()
+            dt_kpts = p.kp_s[torch.as_tensor(pos[sel]).to(dev)].contiguous()
             _, _, dt_matched, dt_ignored = ev._match(dt_kpts, dt_counts, np.ones(S, dtype=np.int64), gt=self._seg_gt_dev)
             seg_off = torch.as_tensor(np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int32)).to(dev)
             npig_t = torch.as_tensor(npig).to(dev)

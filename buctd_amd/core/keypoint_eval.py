@@ -15,7 +15,7 @@ import ctypes as C
 import json
 import logging
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -74,6 +74,14 @@ def summarize(precision, recall):
     return [mean(precision[:, :, 0]), mean(precision[half, :, 0]), mean(precision[three_q, :, 0]),
             mean(precision[:, :, 1]), mean(precision[:, :, 2]),
             mean(recall[:, 0]), mean(recall[half, 0]), mean(recall[three_q, 0]), mean(recall[:, 1]), mean(recall[:, 2])]
+
+
+# What the suppression leaves of one prediction table, or of a merged ensemble: preds / all_boxes as checked,
+# person_image_id, img (image position per person), order_h (input row of each grouped person), keep_h (mask over the
+# grouped persons), offsets / counts (CSR of the groups), kp_s (the grouped key points on the device), the three score
+# vectors on the host per input row and, under soft suppression, rank and live score per grouped person (else None).
+KeptPersons = namedtuple('KeptPersons', 'preds all_boxes person_image_id img order_h keep_h offsets counts kp_s score_h '
+                                        'box_score_h kpt_score_h soft_rank_s soft_score_s', defaults=(None, None))
 
 
 class KeypointEvaluator:
@@ -161,11 +169,10 @@ class KeypointEvaluator:
     def _kept_persons(self, preds, all_boxes, img_path):
         """Steps 1-2 of evaluate(), shared with core.keypoint_analysis: the tables are checked, every person is rescored,
         the persons are grouped (images by id, descending score within an image, equal scores in input order) and the
-        suppression runs within every image.  Returns a dict: preds / all_boxes as checked, person_image_id, img (image
-        position per person), order_h (input row of each grouped person), keep_h (mask over the grouped persons), offsets /
-        counts (CSR of the groups), kp_s (the grouped key points on the device) and the three score vectors on the host."""
+        suppression runs within every image.  Returns a KeptPersons."""
         import torch
         from .._C import check, lib, ptr, stream_ptr
+        from ..nms import nms
         preds = np.ascontiguousarray(preds, dtype=np.float32)
         all_boxes = np.asarray(all_boxes, dtype=np.float64)
         N = preds.shape[0]
@@ -181,14 +188,13 @@ class KeypointEvaluator:
         I, K, dev, d = len(self.image_ids), self.K, self.device, self._d
 
         with torch.cuda.device(dev):
-            st = stream_ptr()
             # 1. rescoring
             preds_t = torch.as_tensor(preds).to(dev)
             box_in = torch.as_tensor(np.ascontiguousarray(all_boxes[:, 5])).to(dev)
             area_t = torch.as_tensor(np.ascontiguousarray(all_boxes[:, 4])).to(dev)
             score, box_score, kpt_score = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
             check(lib().buctd_kpt_rescore(ptr(preds_t), ptr(box_in), N, K, self.in_vis_thre, ptr(score), ptr(box_score),
-                                          ptr(kpt_score), st), "kpt_rescore")
+                                          ptr(kpt_score), stream_ptr()), "kpt_rescore")
             # grouping: images by id, persons by descending score within an image, equal scores in input order
             img_t = torch.as_tensor(img).to(dev)
             by_score = torch.sort(score, descending=True, stable=True).indices
@@ -197,31 +203,23 @@ class KeypointEvaluator:
             offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
             kp_s = preds_t[order].contiguous()
             # 2. OKS NMS within every image
-            keep_s = torch.ones(N, dtype=torch.int32, device=dev)
-            soft = {}
-            if self.use_nms and N:
+            keep_s, soft = torch.ones(N, dtype=torch.int32, device=dev), ()
+            if self.use_nms:
                 off_t = torch.as_tensor(offsets).to(dev)
                 area_s = area_t[order].contiguous()
                 if self.suppression == 'soft':
                     # the decayed scores choose the persons and nothing else: the reference takes indices only
-                    from ..nms.nms import soft_oks_nms_grouped
-                    rank_s, soft_s = soft_oks_nms_grouped(off_t, kp_s, area_s, score[order], d['nms_sigmas'], self.oks_thre,
-                                                          in_vis_thre=self.nms_in_vis_thre, max_keep=self.max_dets)
-                    keep_s = (rank_s >= 0).to(torch.int32)
-                    soft = dict(soft_rank_s=rank_s.cpu().numpy(), soft_score_s=soft_s.cpu().numpy())
+                    rank_s, soft_s = nms.soft_oks_nms_grouped(off_t, kp_s, area_s, score[order], d['nms_sigmas'],
+                                                              self.oks_thre, in_vis_thre=self.nms_in_vis_thre,
+                                                              max_keep=self.max_dets)
+                    keep_s, soft = (rank_s >= 0).to(torch.int32), (rank_s.cpu().numpy(), soft_s.cpu().numpy())
                 else:
-                    use_vis = self.nms_in_vis_thre is not None
-                    check(lib().buctd_oks_nms_grouped(ptr(off_t), I, int(counts.max()), ptr(kp_s), ptr(area_s),
-                                                      ptr(d['nms_sigmas']), K, self.oks_thre, int(use_vis),
-                                                      float(self.nms_in_vis_thre) if use_vis else 0.0, ptr(keep_s), st),
-                          "oks_nms_grouped")
-            elif self.suppression == 'soft':
-                soft = dict(soft_rank_s=np.zeros(0, dtype=np.int32), soft_score_s=np.zeros(0))
-            order_h = order.cpu().numpy()
-            keep_h = keep_s.cpu().numpy().astype(bool)
-            return dict(preds=preds, all_boxes=all_boxes, person_image_id=person_image_id, img=img, order_h=order_h,
-                        keep_h=keep_h, offsets=offsets, counts=counts, kp_s=kp_s, score_h=score.cpu().numpy(),
-                        box_score_h=box_score.cpu().numpy(), kpt_score_h=kpt_score.cpu().numpy(), **soft)
+                    keep_s = nms.oks_nms_grouped(off_t, kp_s, area_s, d['nms_sigmas'], self.oks_thre,
+                                                 in_vis_thre=self.nms_in_vis_thre,
+                                                 max_per_image=int(counts.max(initial=0)))
+            return KeptPersons(preds, all_boxes, person_image_id, img, order.cpu().numpy(),
+                               keep_s.cpu().numpy().astype(bool), offsets, counts, kp_s, score.cpu().numpy(),
+                               box_score.cpu().numpy(), kpt_score.cpu().numpy(), *soft)
 
     def _match(self, dt_kpts, dt_counts, gt_counts, gt=None):
         """Step 3 of evaluate(), shared with core.keypoint_analysis: the OKS matrices and the A x T greedy matchings of
@@ -280,16 +278,16 @@ class KeypointEvaluator:
             raise ValueError("evaluate_merged needs at least one (preds, all_boxes, img_path) set")
         ps = [self._kept_persons(*s) for s in sets]
         L, I, dev = len(ps), len(self.image_ids), self.device
-        sizes = [q['preds'].shape[0] for q in ps]
+        sizes = [q.preds.shape[0] for q in ps]
         base = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         N = int(base[-1])
-        cat = lambda k: np.concatenate([q[k] for q in ps])
+        cat = lambda k: np.concatenate([getattr(q, k) for q in ps])
         all_boxes, score_h = cat('all_boxes'), cat('score_h')
         # per position of the sets' grouped orders, one after the other: input row, level, position, image, kept by its set
-        row_g = np.concatenate([base[l] + q['order_h'] for l, q in enumerate(ps)]).astype(np.int64)
+        row_g = np.concatenate([base[l] + q.order_h for l, q in enumerate(ps)]).astype(np.int64)
         lvl_g = np.repeat(np.arange(L, dtype=np.int64), sizes)
         pos_g = np.concatenate([np.arange(n, dtype=np.int64) for n in sizes])
-        img_g = np.concatenate([q['img'][q['order_h']] for q in ps]).astype(np.int64)
+        img_g = np.concatenate([q.img[q.order_h] for q in ps]).astype(np.int64)
         kept_g = cat('keep_h')
         # the merge: kept persons in cells, image-major and level-major, within a cell in the set's own order
         cell_order = np.lexsort((pos_g, lvl_g, img_g))
@@ -297,7 +295,7 @@ class KeypointEvaluator:
         cells = np.concatenate([[0], np.cumsum(np.bincount(img_g[m_idx] * L + lvl_g[m_idx], minlength=I * L))])
         rows_m = row_g[m_idx]
         with torch.cuda.device(dev):
-            kp_g = torch.cat([q['kp_s'] for q in ps])
+            kp_g = torch.cat([q.kp_s for q in ps])
             keep_m, max_m, best_m = oks_merge_grouped(
                 torch.as_tensor(cells.astype(np.int32)), L, kp_g[torch.as_tensor(m_idx).to(dev)],
                 torch.as_tensor(np.ascontiguousarray(all_boxes[rows_m, 4])).to(dev), self._d['nms_sigmas'], min_oks_thres,
@@ -312,15 +310,13 @@ class KeypointEvaluator:
         accepted_g = np.zeros(N, dtype=bool)
         accepted_g[m_idx] = keep_m
         final = np.lexsort((pos_g, lvl_g, -score_h[row_g], img_g))
-        counts = np.sum([q['counts'] for q in ps], axis=0)
+        counts = np.sum([q.counts for q in ps], axis=0)
         with torch.cuda.device(dev):
             kp_s = kp_g[torch.as_tensor(final).to(dev)].contiguous()
-        p = dict(preds=cat('preds'), all_boxes=all_boxes, person_image_id=[i for q in ps for i in q['person_image_id']],
-                 img=cat('img'), order_h=row_g[final], keep_h=accepted_g[final],
-                 offsets=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), counts=counts, kp_s=kp_s,
-                 score_h=score_h, box_score_h=cat('box_score_h'), kpt_score_h=cat('kpt_score_h'))
-        if self.suppression == 'soft':
-            p.update(soft_rank_s=cat('soft_rank_s')[final], soft_score_s=cat('soft_score_s')[final])
+        soft = [cat(k)[final] for k in ('soft_rank_s', 'soft_score_s') if getattr(ps[0], k) is not None]
+        p = KeptPersons(cat('preds'), all_boxes, [i for q in ps for i in q.person_image_id], cat('img'), row_g[final],
+                        accepted_g[final], np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), counts, kp_s, score_h,
+                        cat('box_score_h'), cat('kpt_score_h'), *soft)
         img_path = [path for s in sets for path in s[2]]
         return self._finish(cfg, p, img_path, output_dir, epoch, by_score=self.use_nms or L > 1,
                             extra=dict(level=level, merge_keep=merge_keep, merge_max_oks=merge_max_oks,
@@ -330,11 +326,11 @@ class KeypointEvaluator:
         """Steps 3-5 of evaluate() on what _kept_persons returned: the detections, the matching, the figures, `tables` and
         the results file."""
         import torch
-        preds, all_boxes, person_image_id = p['preds'], p['all_boxes'], p['person_image_id']
+        preds, all_boxes, person_image_id = p.preds, p.all_boxes, p.person_image_id
         N, I, dev = preds.shape[0], len(self.image_ids), self.device
-        order_h, keep_h, offsets, counts, score_h = p['order_h'], p['keep_h'], p['offsets'], p['counts'], p['score_h']
+        order_h, keep_h, offsets, counts, score_h = p.order_h, p.keep_h, p.offsets, p.counts, p.score_h
         # detections: the kept persons of an image by score, at most max_dets
-        img_s = p['img'][order_h]
+        img_s = p.img[order_h]
         rank = np.cumsum(keep_h) - keep_h
         rank = rank - np.repeat(rank[offsets[:-1][counts > 0]], counts[counts > 0])
         dt_pos = np.flatnonzero(keep_h & (rank < self.max_dets))
@@ -342,11 +338,11 @@ class KeypointEvaluator:
         dt_offsets = np.concatenate([[0], np.cumsum(dt_counts)]).astype(np.int32)
         # 3. OKS matrices + the A x T greedy matchings per image
         with torch.cuda.device(dev):
-            dt_kpts = p['kp_s'][torch.as_tensor(dt_pos).to(dev)].contiguous()
+            dt_kpts = p.kp_s[torch.as_tensor(dt_pos).to(dev)].contiguous()
             oks_offsets, oks, dt_matched, dt_ignored = self._match(dt_kpts, dt_counts, self.gt_counts)
             oks_h = oks.cpu().numpy()[:int(oks_offsets[-1])]
             dtm_h, dti_h = dt_matched.cpu().numpy(), dt_ignored.cpu().numpy()
-        box_score_h, kpt_score_h = p['box_score_h'], p['kpt_score_h']
+        box_score_h, kpt_score_h = p.box_score_h, p.kpt_score_h
 
         dt_rows = order_h[dt_pos]
         precision, recall = accumulate(score_h[dt_rows], dtm_h, dti_h, self.npig)
@@ -360,9 +356,9 @@ class KeypointEvaluator:
             oks=[oks_h[oks_offsets[i]:oks_offsets[i + 1]].reshape(int(dt_counts[i]), int(self.gt_counts[i]))
                  for i in range(I)],
             dt_matched=dtm_h, dt_ignored=dti_h, precision=precision, recall=recall, stats=stats)
-        if self.suppression == 'soft':                      # per input row: the round a person was taken in, its live score
+        if p.soft_rank_s is not None:                       # per input row: the round a person was taken in, its live score
             soft_rank, soft_score = np.full(N, -1, dtype=np.int32), np.zeros(N)
-            soft_rank[order_h], soft_score[order_h] = p['soft_rank_s'], p['soft_score_s']
+            soft_rank[order_h], soft_score[order_h] = p.soft_rank_s, p.soft_score_s
             self.tables.update(soft_rank=soft_rank, soft_score=soft_score)
         if extra:
             self.tables.update(extra)

@@ -147,6 +147,16 @@ __device__ __forceinline__ bool out_of_range(double area, const double* __restri
   return area < rng[0] || area > rng[1];
 }
 
+// Area of the extent of a detection's key points dk [K][3], the area COCOeval gives a detection without a box.
+__device__ __forceinline__ double kpt_extent_area(const float* dk, int K) {
+  double x0 = dk[0], x1 = dk[0], y0 = dk[1], y1 = dk[1];
+  for (int j = 1; j < K; ++j) {
+    x0 = fmin(x0, (double)dk[j * 3]); x1 = fmax(x1, (double)dk[j * 3]);
+    y0 = fmin(y0, (double)dk[j * 3 + 1]); y1 = fmax(y1, (double)dk[j * 3 + 1]);
+  }
+  return (x1 - x0) * (y1 - y0);
+}
+
 // One wavefront per image.  (a) the D x G OKS matrix of computeOks; (b) evaluateImg: one lane per (area range,
 // threshold) walks the detections in score order over the ground truths sorted non-ignored first.
 __global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
@@ -159,13 +169,8 @@ __global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
     for (int idx = lane; idx < D * A.n_area * A.n_thr; idx += 64) {
       const int d = idx % D, l = idx / D, a = l / A.n_thr;
       const float* dk = A.dt_kpts + (long)(d0 + d) * K * 3;
-      double x0 = dk[0], x1 = dk[0], y0 = dk[1], y1 = dk[1];
-      for (int j = 1; j < K; ++j) {
-        x0 = fmin(x0, (double)dk[j * 3]); x1 = fmax(x1, (double)dk[j * 3]);
-        y0 = fmin(y0, (double)dk[j * 3 + 1]); y1 = fmax(y1, (double)dk[j * 3 + 1]);
-      }
       A.dt_matched[(long)l * A.dt_total + d0 + d] = 0;
-      A.dt_ignored[(long)l * A.dt_total + d0 + d] = out_of_range((x1 - x0) * (y1 - y0), A.area_rng + 2 * a) ? 1 : 0;
+      A.dt_ignored[(long)l * A.dt_total + d0 + d] = out_of_range(kpt_extent_area(dk, K), A.area_rng + 2 * a) ? 1 : 0;
     }
     return;
   }
@@ -235,13 +240,8 @@ __global__ __launch_bounds__(64) void coco_kpt_match_kernel(KptMatchArgs A) {
     const long o = (long)lane * A.dt_total + d0 + d;
     if (m == -1) {
       const float* dk = A.dt_kpts + (long)(d0 + d) * K * 3;
-      double x0 = dk[0], x1 = dk[0], y0 = dk[1], y1 = dk[1];
-      for (int j = 1; j < K; ++j) {
-        x0 = fmin(x0, (double)dk[j * 3]); x1 = fmax(x1, (double)dk[j * 3]);
-        y0 = fmin(y0, (double)dk[j * 3 + 1]); y1 = fmax(y1, (double)dk[j * 3 + 1]);
-      }
       A.dt_matched[o] = 0;
-      A.dt_ignored[o] = out_of_range((x1 - x0) * (y1 - y0), rng) ? 1 : 0;
+      A.dt_ignored[o] = out_of_range(kpt_extent_area(dk, K), rng) ? 1 : 0;
     } else {
       A.dt_matched[o] = g0 + m + 1;
       A.dt_ignored[o] = m_ig;

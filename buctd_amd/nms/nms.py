@@ -4,6 +4,7 @@ names and return conventions.  None of this runs on the BUCTD path itself (keep 
 evaluation.  The OKS functions evaluate a whole candidate set per step as one numpy expression
 instead of the reference's per-candidate Python loop."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -168,11 +169,47 @@ def soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None):
     return np.array(keep, dtype=np.intp)
 
 
-# ---- OKS suppression on the device (csrc/keypoint_eval.hip)
-def _decay_type(decay):
-    if decay not in ('gaussian', 'linear'):
-        raise ValueError(f"decay is 'gaussian' or 'linear', not {decay!r}")
-    return 0 if decay == 'gaussian' else 1
+# ---- grouped OKS operations on the device (csrc/keypoint_eval.hip, csrc/oks_merge.hip)
+def _pose_set(kpts, areas, sigmas, in_vis_thre, scores=None, offsets=None):
+    """A pose set as every grouped kernel takes it, checked, then staged on kpts.device: kpts float32 [N][K][3], areas /
+    scores fp64 [N], sigmas fp64 [K], offsets int32 [images + 1] (scores, offsets: None stays None), N, K, images (of
+    offsets) and vis, the kernels' (use_vis, in_vis_thre) argument pair."""
+    import torch
+    if kpts.dim() != 3 or kpts.shape[2] != 3:
+        raise ValueError(f"kpts is {tuple(kpts.shape)}, expected [N, K, 3]")
+    N, K = int(kpts.shape[0]), int(kpts.shape[1])
+    sizes = {name: t.numel() for name, t in dict(areas=areas, scores=scores, sigmas=sigmas, offsets=offsets).items()
+             if t is not None}
+    fits = lambda name, n: n >= 1 if name == 'offsets' else n == (K if name == 'sigmas' else N)
+    if not all(fits(name, n) for name, n in sizes.items()):
+        raise ValueError(" / ".join(f"{name} ({n})" for name, n in sizes.items())
+                         + f" do not describe {N} persons with {K} key points")
+    stage = lambda t, dtype: t if t is None else t.to(kpts.device, dtype).contiguous()
+    use_vis = in_vis_thre is not None
+    return SimpleNamespace(N=N, K=K, images=sizes.get('offsets', 0) - 1, kpts=stage(kpts, torch.float32),
+                           areas=stage(areas, torch.float64), scores=stage(scores, torch.float64),
+                           sigmas=stage(sigmas, torch.float64), offsets=stage(offsets, torch.int32),
+                           vis=(int(use_vis), float(in_vis_thre) if use_vis else 0.0))
+
+
+def oks_nms_grouped(offsets, kpts, areas, sigmas, thresh, *, in_vis_thre=None, max_per_image=None):
+    """OKS suppression (oks_nms) of every image at once (buctd_oks_nms_grouped, one wavefront per image).  Device tensors:
+    offsets int32 [images + 1] (CSR of the groups), kpts float32 [N][K][3] and areas fp64 [N] in grouped order, within an
+    image by descending score, sigmas fp64 [K].  max_per_image, the largest group's size, sizes the kernel's LDS bitmap;
+    None reads it from offsets, which waits for the device: a caller that has the counts on the host passes it.  Returns
+    keep int32 [N]: 0 where the OKS to a kept, better-scored person of the image exceeds thresh, else 1."""
+    import torch
+    from .._C import check, lib, ptr, stream_ptr
+    s = _pose_set(kpts, areas, sigmas, in_vis_thre, offsets=offsets)
+    with torch.cuda.device(kpts.device):
+        keep = torch.ones(s.N, dtype=torch.int32, device=kpts.device)
+        if s.N and s.images:
+            if max_per_image is None:
+                max_per_image = (s.offsets[1:] - s.offsets[:-1]).max()
+            check(lib().buctd_oks_nms_grouped(ptr(s.offsets), s.images, int(max_per_image), ptr(s.kpts), ptr(s.areas),
+                                              ptr(s.sigmas), s.K, float(thresh), *s.vis, ptr(keep), stream_ptr()),
+                  "oks_nms_grouped")
+    return keep
 
 
 def soft_oks_nms_grouped(offsets, kpts, areas, scores, sigmas, thresh, *, decay='gaussian', in_vis_thre=None,
@@ -184,67 +221,45 @@ def soft_oks_nms_grouped(offsets, kpts, areas, scores, sigmas, thresh, *, decay=
     round the head is the untaken person with the largest live score, the lowest position among equal ones."""
     import torch
     from .._C import check, lib, ptr, stream_ptr
-    decay_type = _decay_type(decay)
-    if kpts.dim() != 3 or kpts.shape[2] != 3:
-        raise ValueError(f"kpts is {tuple(kpts.shape)}, expected [N, K, 3]")
-    N, K = int(kpts.shape[0]), int(kpts.shape[1])
-    images = int(offsets.numel()) - 1
-    if areas.numel() != N or scores.numel() != N or sigmas.numel() != K or images < 0:
-        raise ValueError(f"areas ({areas.numel()}) / scores ({scores.numel()}) / sigmas ({sigmas.numel()}) / offsets "
-                         f"({offsets.numel()}) do not describe {N} persons with {K} key points")
-    dev = kpts.device
-    with torch.cuda.device(dev):
-        f64 = lambda t: t.to(dev, torch.float64).contiguous()
-        off_t = offsets.to(dev, torch.int32).contiguous()
-        kp_t = kpts.to(torch.float32).contiguous()
-        area_t, score_t, sig_t = f64(areas), f64(scores), f64(sigmas)
-        rank = torch.full((N,), -1, dtype=torch.int32, device=dev)
-        soft_score = score_t.clone()
-        if N and images:
-            use_vis = in_vis_thre is not None
-            check(lib().buctd_soft_oks_nms_grouped(ptr(off_t), images, ptr(kp_t), ptr(area_t), ptr(score_t), ptr(sig_t), K,
-                                                   float(thresh), decay_type, int(use_vis),
-                                                   float(in_vis_thre) if use_vis else 0.0, int(max_keep), ptr(soft_score),
-                                                   ptr(rank), stream_ptr()), "soft_oks_nms_grouped")
+    if decay not in ('gaussian', 'linear'):
+        raise ValueError(f"decay is 'gaussian' or 'linear', not {decay!r}")
+    s = _pose_set(kpts, areas, sigmas, in_vis_thre, scores, offsets)
+    with torch.cuda.device(kpts.device):
+        rank = torch.full((s.N,), -1, dtype=torch.int32, device=kpts.device)
+        soft_score = s.scores.clone()
+        if s.N and s.images:
+            check(lib().buctd_soft_oks_nms_grouped(ptr(s.offsets), s.images, ptr(s.kpts), ptr(s.areas), ptr(s.scores),
+                                                   ptr(s.sigmas), s.K, float(thresh), int(decay == 'linear'), *s.vis,
+                                                   int(max_keep), ptr(soft_score), ptr(rank), stream_ptr()),
+                  "soft_oks_nms_grouped")
     return rank, soft_score
 
 
-def _one_image_group(kpts_db, sigmas, device_id):
-    """The poses of one image on the device, in descending score order (stable): order, offsets, kpts, areas, scores,
-    sigmas."""
+def _db_pose_set(dbs, sigmas, device_id):
+    """Non-empty kpts_db lists, one after the other, as one pose set on the device: kpts float32 [N][K][3], areas and
+    scores fp64 [N], sigmas fp64 [K] (COCO_SIGMAS by default), and the sizes of the lists."""
     import torch
-    scores, kpts, areas = _db_arrays(kpts_db)
-    n = scores.shape[0]
-    kpts = kpts.reshape(n, -1, 3)
+    scores, kpts, areas = (np.concatenate(a) for a in zip(*map(_db_arrays, dbs)))
+    kpts = kpts.reshape(kpts.shape[0], -1, 3)
     sig = COCO_SIGMAS if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(-1)
     if sig.shape[0] != kpts.shape[1]:
         raise ValueError(f"sigmas has {sig.shape[0]} entries, the poses {kpts.shape[1]} key points")
     dev = torch.device("cuda", device_id)
-    with torch.cuda.device(dev):
-        score_t = torch.as_tensor(np.ascontiguousarray(scores, dtype=np.float64)).to(dev)
-        order = torch.argsort(score_t, descending=True, stable=True)
-        kp_t = torch.as_tensor(np.ascontiguousarray(kpts, dtype=np.float32)).to(dev)[order].contiguous()
-        area_t = torch.as_tensor(np.ascontiguousarray(areas, dtype=np.float64)).to(dev)[order].contiguous()
-        off_t = torch.tensor([0, n], dtype=torch.int32, device=dev)
-        return order, off_t, kp_t, area_t, score_t[order].contiguous(), torch.as_tensor(sig).to(dev)
+    t = lambda a, dt: torch.as_tensor(np.array(a, dtype=dt)).to(dev)          # a copy: the caller's array may be read-only
+    return t(kpts, np.float32), t(areas, np.float64), t(scores, np.float64), t(sig, np.float64), [len(db) for db in dbs]
 
 
 def gpu_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0):
-    """oks_nms on the device (buctd_oks_nms_grouped over a one-image group): the kept indices into kpts_db in score
-    order; equal scores in input order.  The key points enter as float32."""
+    """oks_nms on the device (oks_nms_grouped over a one-image group): the kept indices into kpts_db in score order;
+    equal scores in input order.  The key points enter as float32."""
     if len(kpts_db) == 0:
         return []
     import torch
-    from .._C import check, lib, ptr, stream_ptr
-    order, off_t, kp_t, area_t, _, sig_t = _one_image_group(kpts_db, sigmas, device_id)
-    n, K = int(kp_t.shape[0]), int(kp_t.shape[1])
-    with torch.cuda.device(kp_t.device):
-        keep = torch.zeros(n, dtype=torch.int32, device=kp_t.device)
-        use_vis = in_vis_thre is not None
-        check(lib().buctd_oks_nms_grouped(ptr(off_t), 1, n, ptr(kp_t), ptr(area_t), ptr(sig_t), K, float(thresh),
-                                          int(use_vis), float(in_vis_thre) if use_vis else 0.0, ptr(keep), stream_ptr()),
-              "oks_nms_grouped")
-        return [int(i) for i in order[keep != 0].cpu()]
+    kpts, areas, scores, sig, (n,) = _db_pose_set([kpts_db], sigmas, device_id)
+    order = torch.argsort(scores, descending=True, stable=True)
+    keep = oks_nms_grouped(torch.tensor([0, n], dtype=torch.int32), kpts[order], areas[order], sig, thresh,
+                           in_vis_thre=in_vis_thre, max_per_image=n)
+    return [int(i) for i in order[keep != 0].cpu()]
 
 
 def gpu_soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0):
@@ -253,8 +268,10 @@ def gpu_soft_oks_nms(kpts_db, thresh, sigmas=None, in_vis_thre=None, device_id=0
     if len(kpts_db) == 0:
         return []
     import torch
-    order, off_t, kp_t, area_t, score_t, sig_t = _one_image_group(kpts_db, sigmas, device_id)
-    rank, _ = soft_oks_nms_grouped(off_t, kp_t, area_t, score_t, sig_t, thresh, in_vis_thre=in_vis_thre, max_keep=20)
+    kpts, areas, scores, sig, (n,) = _db_pose_set([kpts_db], sigmas, device_id)
+    order = torch.argsort(scores, descending=True, stable=True)
+    rank, _ = soft_oks_nms_grouped(torch.tensor([0, n], dtype=torch.int32), kpts[order], areas[order], scores[order], sig,
+                                   thresh, in_vis_thre=in_vis_thre, max_keep=20)
     taken = torch.nonzero(rank >= 0).reshape(-1)
     taken = taken[torch.argsort(rank[taken])]
     return order[taken].cpu().numpy().astype(np.intp)
@@ -314,27 +331,18 @@ def oks_merge_grouped(cells, levels, kpts, areas, sigmas, thresh, *, in_vis_thre
     fp64 [N], sigmas fp64 [K].  Returns (keep int32 [N], max_oks fp64 [N], best int32 [N])."""
     import torch
     from .._C import check, lib, ptr, stream_ptr
-    if kpts.dim() != 3 or kpts.shape[2] != 3:
-        raise ValueError(f"kpts is {tuple(kpts.shape)}, expected [N, K, 3]")
-    N, K = int(kpts.shape[0]), int(kpts.shape[1])
-    if areas.numel() != N or sigmas.numel() != K:
-        raise ValueError(f"areas ({areas.numel()}) / sigmas ({sigmas.numel()}) do not describe {N} persons with {K} key "
-                         f"points")
-    images, L = _merge_images(cells, levels, N), int(levels)
+    s = _pose_set(kpts, areas, sigmas, in_vis_thre)
+    N, images, L = s.N, _merge_images(cells, levels, s.N), int(levels)
     dev = kpts.device
     with torch.cuda.device(dev):
-        f64 = lambda t: t.to(dev, torch.float64).contiguous()
         cell_t = cells.to(dev, torch.int32).contiguous()
-        kp_t = kpts.to(torch.float32).contiguous()
-        area_t, sig_t = f64(areas), f64(sigmas)
         keep = torch.ones(N, dtype=torch.int32, device=dev)
         max_oks = torch.full((N,), -1.0, dtype=torch.float64, device=dev)
         best = torch.full((N,), -1, dtype=torch.int32, device=dev)
         if N and images:
-            use_vis = in_vis_thre is not None
-            check(lib().buctd_oks_merge_grouped(ptr(cell_t), images, L, N, ptr(kp_t), ptr(area_t), ptr(sig_t), K,
-                                                float(thresh), int(use_vis), float(in_vis_thre) if use_vis else 0.0,
-                                                ptr(keep), ptr(max_oks), ptr(best), stream_ptr()), "oks_merge_grouped")
+            check(lib().buctd_oks_merge_grouped(ptr(cell_t), images, L, N, ptr(s.kpts), ptr(s.areas), ptr(s.sigmas), s.K,
+                                                float(thresh), *s.vis, ptr(keep), ptr(max_oks), ptr(best), stream_ptr()),
+                  "oks_merge_grouped")
     return keep, max_oks, best
 
 
@@ -347,17 +355,8 @@ def gpu_oks_merge(kpts_db_mode0, kpts_db_mode1, min_oks_thres=0.5, sigmas=None, 
     if len(kpts_db_mode0) == 0:
         return kpts_db_mode1
     import torch
-    _, k0, a0 = _db_arrays(kpts_db_mode0)
-    _, k1, a1 = _db_arrays(kpts_db_mode1)
-    n1, n0 = k1.shape[0], k0.shape[0]
-    kpts = np.concatenate([k1, k0]).reshape(n1 + n0, -1, 3)
-    sig = COCO_SIGMAS if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(-1)
-    if sig.shape[0] != kpts.shape[1]:
-        raise ValueError(f"sigmas has {sig.shape[0]} entries, the poses {kpts.shape[1]} key points")
-    dev = torch.device("cuda", device_id)
-    t = lambda a, dt: torch.as_tensor(np.array(a, dtype=dt)).to(dev)
-    keep, _, _ = oks_merge_grouped(torch.tensor([0, n1, n1 + n0], dtype=torch.int32), 2, t(kpts, np.float32),
-                                   t(np.concatenate([a1, a0]), np.float64), t(sig, np.float64), min_oks_thres,
+    kpts, areas, _, sig, (n1, n0) = _db_pose_set([kpts_db_mode1, kpts_db_mode0], sigmas, device_id)
+    keep, _, _ = oks_merge_grouped(torch.tensor([0, n1, n1 + n0], dtype=torch.int32), 2, kpts, areas, sig, min_oks_thres,
                                    in_vis_thre=in_vis_thre)
     for i in np.flatnonzero(keep[n1:].cpu().numpy()):
         kpts_db_mode1.append(kpts_db_mode0[i])

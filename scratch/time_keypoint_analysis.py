@@ -73,7 +73,7 @@ def main():
     _, res["a_instances_s"] = timed(lambda: an.instances(preds, boxes, paths))
     res["num_instances"] = tables['num_instances'].tolist()
     res["AP"] = tables['AP'].tolist()
-    scores = ev._kept_persons(preds, boxes, paths)['score_h']
+    scores = ev._kept_persons(preds, boxes, paths).score_h
     host, res["b_host_accumulate_per_person_s"] = timed(lambda: host_per_person(an, scores))
     res["max_abs_difference_per_person"] = float(np.abs(host - an.instance_tables['stats']).max())
     print(json.dumps(res))

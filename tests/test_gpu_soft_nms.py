@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import oks_nms_cases as hard
 from tests.helpers import soft_nms_cases as cases
 from tests.helpers import soft_nms_ref as S
 
@@ -63,6 +64,29 @@ def test_equal_scores_keep_grouped_order(dev, decay, use_vis):
     assert p0 < p1 and g['scores'][a + p0] == g['scores'][a + p1]
     assert rank[a + p0] > 0 and rank[a + p1] == rank[a + p0] + 1          # not first: the tie survived a decay round
     assert soft[a + p0] == soft[a + p1] == g['scores'][a + p0]            # every factor was exactly 1.0
+
+
+@pytest.mark.parametrize("name", sorted(hard.CONFIGS))
+@pytest.mark.parametrize("use_vis", (False, True))
+def test_hard_grouped_equals_the_host_oks_nms(dev, name, use_vis):
+    """nms.oks_nms_grouped over one multi-image group (0, 1, 2, 63, 64, 65 and 129 persons) against nms.oks_nms per
+    image: the kept sets are equal - the sets hold no OKS within 1e-9 of the threshold (tests/test_soft_nms.py)."""
+    from buctd_amd.nms.nms import oks_nms_grouped
+    c = hard.case(name)
+    off, kp, ar, sig = (torch.as_tensor(np.array(c[k])).to(dev) for k in ('offsets', 'kpts', 'areas', 'sigmas'))
+    vis = hard.VIS_THRE if use_vis else None
+    keep = oks_nms_grouped(off, kp, ar, sig, c['thresh'], in_vis_thre=vis)
+    assert keep.dtype == torch.int32 and keep.shape == ar.shape and keep.device == kp.device
+    assert np.array_equal(keep.cpu().numpy(), c['keep'][use_vis])
+    # the bitmap sized by the caller or read from offsets, and a second run: the same bits
+    sized = oks_nms_grouped(off, kp, ar, sig, c['thresh'], in_vis_thre=vis, max_per_image=max(hard.COUNTS))
+    again = oks_nms_grouped(off, kp, ar, sig, c['thresh'], in_vis_thre=vis)
+    assert keep.cpu().numpy().tobytes() == sized.cpu().numpy().tobytes() == again.cpu().numpy().tobytes()
+    # no person: nothing to keep; no image: every person is kept, nothing ran
+    for offsets in (torch.zeros_like(off), off[:1]):
+        none = oks_nms_grouped(offsets, kp[:0], ar[:0], sig, c['thresh'], in_vis_thre=vis)
+        assert none.dtype == torch.int32 and none.shape == (0,)
+    assert bool((oks_nms_grouped(off[:1], kp, ar, sig, c['thresh'], in_vis_thre=vis) == 1).all())
 
 
 def _db(g, tag):

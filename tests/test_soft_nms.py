@@ -112,6 +112,39 @@ def test_the_sets_cover_every_class():
         assert p0 < p1 and 0 < rank[p0] and rank[p1] == rank[p0] + 1
 
 
+def test_hard_sets_meet_their_input_condition():
+    """Building a set of tests/helpers/oks_nms_cases.py checks that no pair's host OKS lies within 1e-9 of the threshold
+    and that every image of two or more persons has some dropped and some kept; the counts are the ones the kernel's
+    bitmap words make interesting."""
+    from tests.helpers import oks_nms_cases as hard
+    assert hard.COUNTS == (0, 1, 2, 63, 64, 65, 129)
+    for name, (K, _, sigmas) in hard.CONFIGS.items():
+        c = hard.case(name)
+        assert c['kpts'].dtype == np.float32 and c['kpts'].shape == (sum(hard.COUNTS), K, 3)
+        assert np.array_equal(np.diff(c['offsets']), hard.COUNTS) and len(sigmas) == K
+        for a, b in zip(c['offsets'][:-1], c['offsets'][1:]):
+            assert (np.diff(c['scores'][a:b]) < 0).all()                            # descending, no two equal
+        assert not np.array_equal(c['keep'][False], c['keep'][True])                # the joint-score threshold matters
+    assert sorted(K for K, _, _ in hard.CONFIGS.values()) == [3, 17]
+
+
+def test_oks_nms_grouped_refuses_wrong_shapes_before_any_launch():
+    import torch
+    from buctd_amd.nms.nms import oks_nms_grouped
+    from tests.helpers import oks_nms_cases as hard
+    c = hard.case('hard3')
+    N = c['kpts'].shape[0]
+    off, kp, ar, sig = (torch.as_tensor(np.array(c[k])) for k in ('offsets', 'kpts', 'areas', 'sigmas'))
+    good = dict(offsets=off, kpts=kp, areas=ar, sigmas=sig)
+    bad = [dict(kpts=kp[:, :, :2]), dict(kpts=kp.reshape(N, -1)), dict(kpts=kp[:-1]), dict(areas=ar[:-1]),
+           dict(sigmas=sig[:-1]), dict(sigmas=torch.cat([sig, sig])), dict(offsets=off[:0])]
+    for kw in bad:
+        a = dict(good, **kw)
+        for max_per_image in (None, 129):
+            with pytest.raises(ValueError):
+                oks_nms_grouped(a['offsets'], a['kpts'], a['areas'], a['sigmas'], 0.5, max_per_image=max_per_image)
+
+
 def test_refusals_that_need_no_device():
     import buctd_amd.nms.nms as pn
     from buctd_amd.core.keypoint_eval import KeypointEvaluator

@@ -35,6 +35,19 @@ def banded16(t, dev, fill=float("nan"), pad=BAND16):
     return view, big, pad
 
 
+BAND16_2B = 512     # elements of 2 bytes on either side: the same 1024 bytes as BAND16
+
+
+def banded16_2b(t, dev, fill=float("nan"), pad=BAND16_2B):
+    """banded16() for 2-byte element types (torch.bfloat16 activations and filter images)"""
+    assert pad % 8 == 0 and t.element_size() == 2
+    big = torch.full((2 * pad + t.numel(),), fill, dtype=t.dtype, device=dev)
+    view = big[pad:pad + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 0
+    return view, big, pad
+
+
 class Bands:
     """Places the operands of one call.  on=True: read-only operands between NaN bands, outputs between sentinel bands
     (check() asserts the bands are intact); on=False: plain tensors, the unbanded call the banded one must equal."""
@@ -70,3 +83,27 @@ class Bands:
     def check(self, what=""):
         for big, pad, n, fill, name in self.outs:
             assert untouched(big, pad, n, fill), f"{what}: the launch wrote outside {name}"
+
+
+class BandsAny(Bands):
+    """Bands for calls whose operands mix 4-byte and 2-byte element types (the bf16 inference kernels): bands of 1024 bytes
+    on either side whatever the type.  A bf16 output's sentinel is SENTINEL as bf16 stores it."""
+
+    @staticmethod
+    def _banded(t, dev, fill):
+        return banded16_2b(t, dev, fill) if t.element_size() == 2 else banded16(t, dev, fill)
+
+    def ro(self, t):
+        if t is None or not self.on:
+            return super().ro(t)
+        view, big, _ = self._banded(t, self.dev, float("nan") if t.dtype.is_floating_point else -(1 << 30))
+        self.keep.append(big)
+        return view
+
+    def out(self, init, name="output"):
+        if not self.on:
+            return super().out(init, name)
+        fill = SENTINEL if init.dtype.is_floating_point else -12345
+        view, big, pad = self._banded(init, self.dev, fill)
+        self.outs.append((big, pad, init.numel(), fill, name))
+        return view

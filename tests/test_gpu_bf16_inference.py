@@ -135,20 +135,35 @@ def _tile_mt(M, Co):
     return 4 if -(-M // 256) * nn_ >= 1024 else 2 if -(-M // 128) * nn_ >= 1024 else 1
 
 
-# batch-8+ sizes: the MT = 2 / MT = 4 tiles of both the vector (Ci % 8 == 0) and the gather (stem, Ci = 3) paths
-LARGE_CASES = [
-    ((1, 1, 64, 256, 4, 128, 128, True, True, False), 4),
-    ((3, 1, 32, 96, 1, 256, 256, True, True, False), 2),
-    ((3, 2, 3, 64, 10, 384, 288, False, True, False), 4),
-    ((3, 2, 3, 64, 8, 384, 288, False, True, False), 2),
-]
+def _large_cases():
+    """The MT = 2 / MT = 4 tiles of every channel tile (NT 2 / 3 / 4) of both the vector (Ci % 8 == 0) and the gather paths:
+    the small-operand cases of tests/helpers/bf16_cases.py (Ci <= 17, the smallest M that meets the block threshold), as
+    (case of this file, MT, instance name)."""
+    from tests.helpers import bf16_cases as B
+    out = []
+    for c in B.CONV_LARGE:
+        R, stride, pad, Ci, Co, N, H, W, res, relu, head = c
+        assert pad == R // 2
+        mt, nt, vec = B.conv_instance(c)
+        out.append(((R, stride, Ci, Co, N, H, W, bool(res), bool(relu), bool(head)), mt, B.inst_name(mt, nt, vec)[5:]))
+    return out
 
 
-@pytest.mark.parametrize("case,mt", LARGE_CASES, ids=lambda c: str(c))
-def test_bf16_conv_large_tiles_match_fp64(dev, case, mt):
+LARGE_CASES = _large_cases()
+
+
+def test_large_cases_name_every_large_tile_instance():
+    assert sorted(n for _, _, n in LARGE_CASES) == sorted(
+        f"MT{mt}-NT{nt}-{v}" for mt in (2, 4) for nt in (2, 3, 4) for v in ("vec", "gather"))
+
+
+@pytest.mark.parametrize("case,mt,inst", LARGE_CASES, ids=[n for _, _, n in LARGE_CASES])
+def test_bf16_conv_large_tiles_match_fp64(dev, case, mt, inst):
     R, stride, Ci, Co, N, H, W = case[:7]
     Ho, Wo = (H + 2 * (R // 2) - R) // stride + 1, (W + 2 * (R // 2) - R) // stride + 1
     assert _tile_mt(N * Ho * Wo, Co) == mt, "the case no longer selects the tile it is meant to cover"
+    nt = 2 if Co <= 32 else 3 if (Co % 64 != 0 and Co % 48 == 0) else 4
+    assert inst == f"MT{mt}-NT{nt}-{'vec' if Ci % 8 == 0 else 'gather'}"
     test_bf16_conv_matches_fp64_on_the_same_bf16_operands(dev, case)
 
 
